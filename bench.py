@@ -16,10 +16,14 @@ independent, so ranks shard them with no data-path collective (weak scaling: S p
 one all-reduce of the metric accumulators after the rollouts.
 
 Printed by rank 0: ONE JSON line on stdout — the LAST line of stdout, < 4 KB (SHORT_LINE_LIMIT): metric, value = whole-job
-agent-steps/s, roofline of the dominant KERNEL (HIP events on the launch stream during the timed region), cpu_baseline = the
-CPU oracle timed on this box's host cores on a bounded sample, the parity spot check, the sampled shader clock / socket power.
-Everything else — per-kernel rows of both streams, the class view, satellites against the HBM roof, per-class attention rows,
-phases, per-rank times, notes — goes to the detail file (--detail-file, default bench_detail.json) and, prefixed, to stderr.
+agent-steps/s, ms_per_step, dtype.  A plain run does only what that figure needs: set-up, warm-up, the timed steps, the guard
+counter of the rollouts, --dump-outputs if given, the line.  With --full it also reports the roofline of the dominant KERNEL (HIP
+events on every launch during the timed region), cpu_baseline = the CPU oracle timed on the host cores on a bounded sample, the
+parity spot check, the sampled shader clock / socket power, the rollout metrics, the bf16x6 fallback price.  Everything else —
+per-kernel rows of both streams, the class view, satellites against the HBM roof, per-class attention rows, phases, per-rank times,
+notes — goes to the detail file (--detail-file, default bench_detail.json) and, prefixed, to stderr.
+`--dump-outputs DIR` writes what the last timed step computed (tokens, RTG bins, states, collision flags, focal groups of its
+slice; a fixed sample of its scenarios when the slice exceeds MAX_DUMP_BYTES) as DIR/<name>.npy, float32 / float64.
 `python bench.py --gpus N` without a launcher starts the N ranks itself.
 """
 import argparse
@@ -93,7 +97,14 @@ def main():
                          "ranks, barriers, the MAX / gather of the elapsed time, the SUM all-reduce of the metric vector, the parting barrier, "
                          "rank 0's CPU sample after the others left — through the same code as a real run.  The line it prints is marked "
                          "dry_run and is never a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-kernel HIP-event timing and the roofline, phases, clock / power samples, "
+                         "the parity spot check, the per-class attention slice, rollout metrics, the bf16x6 fallback price, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's slice; at most MAX_DUMP_BYTES)")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        raise SystemExit("bench.py: --dump-outputs needs a real run (a dry run rolls nothing)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: --gpus MEANS N.  Re-exec this same command line as N ranks, one per GPU, through
@@ -226,11 +237,12 @@ def main():
 
     bench_steps(0, args.warmup)
     barrier()
-    if not dry:
+    full = bool(args.full)
+    if full and not dry:
         lib.ctrlsim_prof_enable(1)
-    eng.record_phases, eng.phase_events = not args.pipeline, []
+    eng.record_phases, eng.phase_events = full and not args.pipeline, []
     eng.full_pass_contexts = np.zeros(len(eng.sizes), np.int64)
-    clocks = _ClockSampler(local_rank) if (rank == 0 and not dry and not args.no_clock_samples) else None
+    clocks = _ClockSampler(local_rank) if (full and rank == 0 and not dry and not args.no_clock_samples) else None
     t0 = time.perf_counter()
     bench_steps(0, K)
     t_own = time.perf_counter() - t0                          # this rank's own time to its last kernel (before it waits for the others)
@@ -241,31 +253,38 @@ def main():
     cached_s, sliding_s = eng.phase_times()
     if dry:
         return _finish_dry(args, dist, rank, world, eng, cfg, scns, ids, elapsed, t_own, max_ctx_asked, coll_device, gather_scalar, metrics, tilt)
-    ncls = int(lib.ctrlsim_prof_classes())
-    # Launch intervals (HIP events on the launch stream).  The engine runs the big kernels of both lanes back to back on ONE
-    # stream (the current one) and, underneath them on the lanes' side streams, the few-row kernels of the second pass, the
-    # simulator step and the grouping: intervals on different streams overlap in time, so the per-class rates below are taken
-    # from the launches of the main stream (> 98 % of the FLOPs) and the side-stream launches are reported next to them.
-    nsub = int(lib.ctrlsim_prof_subclasses())
-    kms = (C.c_double * nsub)(); kcnt = (C.c_int64 * nsub)(); kfl = (C.c_double * nsub)(); kby = (C.c_double * nsub)()
-    ms = (C.c_double * ncls)(); cnt = (C.c_int64 * ncls)(); fl = (C.c_double * ncls)(); by = (C.c_double * ncls)()
-    sms = (C.c_double * ncls)(); scnt = (C.c_int64 * ncls)(); sfl = (C.c_double * ncls)(); sby = (C.c_double * ncls)()
-    main_stream = _lib.stream_ptr()
-    _lib.check(lib.ctrlsim_prof_collect_stream(main_stream, 1, ms, cnt, fl, by), "prof_collect")
-    _lib.check(lib.ctrlsim_prof_collect_stream(main_stream, 0, sms, scnt, sfl, sby), "prof_collect")
-    _lib.check(lib.ctrlsim_prof_collect_sub(main_stream, 1, kms, kcnt, kfl, kby), "prof_collect_sub")
-    skms = (C.c_double * nsub)(); skcnt = (C.c_int64 * nsub)(); skfl = (C.c_double * nsub)(); skby = (C.c_double * nsub)()
-    _lib.check(lib.ctrlsim_prof_collect_sub(main_stream, 0, skms, skcnt, skfl, skby), "prof_collect_sub")
-    for i in range(2, ncls):                                  # satellites: wherever they ran
-        ms[i] += sms[i]; cnt[i] += scnt[i]; fl[i] += sfl[i]; by[i] += sby[i]
-    lib.ctrlsim_prof_enable(0)
+    if full:
+        ncls = int(lib.ctrlsim_prof_classes())
+        # Launch intervals (HIP events on the launch stream).  The engine runs the big kernels of both lanes back to back on ONE
+        # stream (the current one) and, underneath them on the lanes' side streams, the few-row kernels of the second pass, the
+        # simulator step and the grouping: intervals on different streams overlap in time, so the per-class rates below are taken
+        # from the launches of the main stream (> 98 % of the FLOPs) and the side-stream launches are reported next to them.
+        nsub = int(lib.ctrlsim_prof_subclasses())
+        kms = (C.c_double * nsub)(); kcnt = (C.c_int64 * nsub)(); kfl = (C.c_double * nsub)(); kby = (C.c_double * nsub)()
+        ms = (C.c_double * ncls)(); cnt = (C.c_int64 * ncls)(); fl = (C.c_double * ncls)(); by = (C.c_double * ncls)()
+        sms = (C.c_double * ncls)(); scnt = (C.c_int64 * ncls)(); sfl = (C.c_double * ncls)(); sby = (C.c_double * ncls)()
+        main_stream = _lib.stream_ptr()
+        _lib.check(lib.ctrlsim_prof_collect_stream(main_stream, 1, ms, cnt, fl, by), "prof_collect")
+        _lib.check(lib.ctrlsim_prof_collect_stream(main_stream, 0, sms, scnt, sfl, sby), "prof_collect")
+        _lib.check(lib.ctrlsim_prof_collect_sub(main_stream, 1, kms, kcnt, kfl, kby), "prof_collect_sub")
+        skms = (C.c_double * nsub)(); skcnt = (C.c_int64 * nsub)(); skfl = (C.c_double * nsub)(); skby = (C.c_double * nsub)()
+        _lib.check(lib.ctrlsim_prof_collect_sub(main_stream, 0, skms, skcnt, skfl, skby), "prof_collect_sub")
+        for i in range(2, ncls):                              # satellites: wherever they ran
+            ms[i] += sms[i]; cnt[i] += scnt[i]; fl[i] += sfl[i]; by[i] += sby[i]
+        lib.ctrlsim_prof_enable(0)
     elapsed, rank_times, rank_ctx = _reduce_times(dist, elapsed, t_own, args.max_ctx, coll_device, gather_scalar)
+
+    # ---- guard counter of the timed rollouts, then what the last timed step computed (before any untimed extra roll overwrites a slice)
+    if eng.nonfinite(reset=False):
+        raise FloatingPointError("guard events during the rollout (csrc/split.h: activation range; csrc/sim.hip: contact table)")
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(eng, cuts[K - 1], cuts[K], ids, args.dump_outputs)
 
     # ---- parity spot check (untimed): a few scenarios of the batch are rolled again, ALONE, by a second engine (one lane, small model
     # batches, no other scenario in their forward chunks): tokens, RTG bins, collision flags and float32 trajectories must be
     # BIT-identical to what the timed rollout left in HBM — a regression of the batching / lane / class machinery shows here
     spot = None
-    if rank == 0 and args.spot_check > 0:
+    if full and rank == 0 and args.spot_check > 0:
         pick = sorted({int(x) for x in np.linspace(0, S - 1, args.spot_check)})
         tl = tilt[pick] if isinstance(tilt, np.ndarray) else tilt
         e2 = RolloutEngine(cfg, w, device, max_ctx=64, seed=args.seed, tilt=tl, lanes=1, model=eng.model)
@@ -291,7 +310,7 @@ def main():
     # accounting on (one atomic per workgroup: not inside the timed region) — where the largest single kernel spends its time
     attn_by_class = None
     full_ctx = np.asarray(eng.full_pass_contexts, np.int64).copy()
-    if rank == 0 and not args.no_class_profile:
+    if full and rank == 0 and not args.no_class_profile:
         a, b = cuts[0], cuts[1]
         _lib.check(lib.ctrlsim_attn_class_prof(1, None), "attn_class_prof")
         eng.reset(a, b)
@@ -322,23 +341,26 @@ def main():
     # ---- metrics: the evaluator's accumulators are built on the device (ctrlsim_metrics_pack: rank-side work independent of S)
     # and combined by ONE all-reduce of that ~10 KB vector — the only collective of the job.  The synthetic
     # scenes' "log" is the constant-velocity continuation of the initial state.
+    # A plain run has no collective after the timed region but the time reduction above.
     res = {"n_groups": eng.groups_per_step}
-    f64 = lambda a: np.stack([np.asarray(getattr(s, a), np.float64) for s in scns])
-    x0, y0, hd, sp = f64("x"), f64("y"), f64("heading"), f64("speed")
-    tt = np.arange(R + 1)[None, None, :] * cfg.nocturne.dt
-    gt = np.stack([x0[..., None] + (sp * np.cos(hd))[..., None] * tt, y0[..., None] + (sp * np.sin(hd))[..., None] * tt,
-                   np.broadcast_to(hd[..., None], (S, N, R + 1)), np.broadcast_to(sp[..., None], (S, N, R + 1)),
-                   np.ones((S, N, R + 1))], -1)
-    goals4 = np.concatenate([f64("goal_pos"), f64("goal_heading")[..., None], f64("goal_speed")[..., None]], -1)
-    vec = eng.metrics_pack(gt, goals4)
-    torch.cuda.synchronize()
-    if eng.nonfinite(reset=False):
-        raise FloatingPointError("guard events during the rollout (csrc/split.h: activation range; csrc/sim.hip: contact table)")
-    vec = vec.to(coll_device)
-    if dist is not None:
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-    acc = metrics.MetricAccumulators().unpack(vec.cpu().numpy())
-    n_vec = int(vec.numel())
+    acc = n_vec = None
+    if full:
+        f64 = lambda a: np.stack([np.asarray(getattr(s, a), np.float64) for s in scns])
+        x0, y0, hd, sp = f64("x"), f64("y"), f64("heading"), f64("speed")
+        tt = np.arange(R + 1)[None, None, :] * cfg.nocturne.dt
+        gt = np.stack([x0[..., None] + (sp * np.cos(hd))[..., None] * tt, y0[..., None] + (sp * np.sin(hd))[..., None] * tt,
+                       np.broadcast_to(hd[..., None], (S, N, R + 1)), np.broadcast_to(sp[..., None], (S, N, R + 1)),
+                       np.ones((S, N, R + 1))], -1)
+        goals4 = np.concatenate([f64("goal_pos"), f64("goal_heading")[..., None], f64("goal_speed")[..., None]], -1)
+        vec = eng.metrics_pack(gt, goals4)
+        torch.cuda.synchronize()
+        if eng.nonfinite(reset=False):                        # (the untimed extra rolls above included)
+            raise FloatingPointError("guard events during the rollout (csrc/split.h: activation range; csrc/sim.hip: contact table)")
+        vec = vec.to(coll_device)
+        if dist is not None:
+            dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+        acc = metrics.MetricAccumulators().unpack(vec.cpu().numpy())
+        n_vec = int(vec.numel())
     backend = dist.get_backend() if dist is not None else "none (single process)"
     if dist is not None:                      # every collective of the job is done: the ranks part here, rank 0 goes on to the (untimed)
         dist.barrier()                        # CPU baseline and the report without holding seven idle ranks in a process group
@@ -349,156 +371,158 @@ def main():
         agent_steps = S * N * R * world
         value = agent_steps / elapsed
         ctx_per_rollout = int(res["n_groups"].sum())
-        dom = 0 if ms[0] >= ms[1] else 1
         f16 = eng.scheme == 1
         nprod, scheme = (3, "two fp16 planes, 3") if f16 else (6, "three bf16 planes, 6")
-        PEAK_FP32_EQUIV_TFLOPS = PEAK_16BIT_MFMA_TFLOPS / nprod
-        names = ("inproj_rs_kernel + gemm_ws256_kernel + gemm_nt_bf16x6_kernel + ffn_fused_bf16x6_kernel (every nn.Linear incl. fused LayerNorm / K-V image epilogues and the fused "
-                 f"feed-forward block; split-operand MFMA 32x32x16: {scheme} partial products per fp32 product)",
-                 "attention_bf16x6_kernel (all multi-head attention; split-operand MFMA flash attention, structured mask)")
+        roof = None
+        if full:
+            dom = 0 if ms[0] >= ms[1] else 1
+            PEAK_FP32_EQUIV_TFLOPS = PEAK_16BIT_MFMA_TFLOPS / nprod
+            names = ("inproj_rs_kernel + gemm_ws256_kernel + gemm_nt_bf16x6_kernel + ffn_fused_bf16x6_kernel (every nn.Linear incl. fused LayerNorm / K-V image epilogues and the fused "
+                     f"feed-forward block; split-operand MFMA 32x32x16: {scheme} partial products per fp32 product)",
+                     "attention_bf16x6_kernel (all multi-head attention; split-operand MFMA flash attention, structured mask)")
 
-        # HBM bytes per launch from the PMC counters: rocprofv3 cannot run inside this process, so they come from separate --pmc passes over
-        # a smaller run of this same command (tools/pmc_traffic.sh), committed under profiles/ PER KERNEL with ONE counter convention for
-        # every file of the round: FETCH_SIZE x 2 (gfx950 tallies its 128-byte read requests at 64 B — calibrated in round 5 on known-byte
-        # launches of every access pattern and of each hot kernel: profiles/r05_pmc_calibration.json) + WRITE_SIZE x 1.
-        pmc, pmc_src = {}, None
-        for cand in ("r06_pmc_traffic.json", "r05w_pmc_traffic.json", "r05_pmc_traffic.json"):
-            pmc_path = os.path.join(ROOT, "profiles", cand)
-            if os.path.exists(pmc_path):
-                pmc, pmc_src = json.load(open(pmc_path)), "profiles/" + cand
-                break
-        KIND_KEYS = ("other", "linear_kv_images", "linear_residual_layernorm", "linear_plain", "ffn_fused", "attention_causal", "attention_keypad")
-        CLASS_KINDS = ((0, 1, 2, 3, 4), (5, 6))             # kinds of the Linear class / the attention class
+            # HBM bytes per launch from the PMC counters: rocprofv3 cannot run inside this process, so they come from separate --pmc passes over
+            # a smaller run of this same command (tools/pmc_traffic.sh), committed under profiles/ PER KERNEL with ONE counter convention for
+            # every file of the round: FETCH_SIZE x 2 (gfx950 tallies its 128-byte read requests at 64 B — calibrated in round 5 on known-byte
+            # launches of every access pattern and of each hot kernel: profiles/r05_pmc_calibration.json) + WRITE_SIZE x 1.
+            pmc, pmc_src = {}, None
+            for cand in ("r06_pmc_traffic.json", "r05w_pmc_traffic.json", "r05_pmc_traffic.json"):
+                pmc_path = os.path.join(ROOT, "profiles", cand)
+                if os.path.exists(pmc_path):
+                    pmc, pmc_src = json.load(open(pmc_path)), "profiles/" + cand
+                    break
+            KIND_KEYS = ("other", "linear_kv_images", "linear_residual_layernorm", "linear_plain", "ffn_fused", "attention_causal", "attention_keypad")
+            CLASS_KINDS = ((0, 1, 2, 3, 4), (5, 6))             # kinds of the Linear class / the attention class
 
-        def kind_ratio(kind):
-            """measured HBM bytes / algorithmic bytes of kernel kind `kind` in the PMC run (same kernels and shapes per context, smaller
-            launches: counter passes serialise the kernels); None when the profile has no entry for it."""
-            e = pmc.get("kernels", {}).get(KIND_KEYS[kind])
-            return e.get("hbm_over_algorithmic") if e else None
+            def kind_ratio(kind):
+                """measured HBM bytes / algorithmic bytes of kernel kind `kind` in the PMC run (same kernels and shapes per context, smaller
+                launches: counter passes serialise the kernels); None when the profile has no entry for it."""
+                e = pmc.get("kernels", {}).get(KIND_KEYS[kind])
+                return e.get("hbm_over_algorithmic") if e else None
 
-        def kind_bytes(kind, main_only=True):
-            """algorithmic bytes and launches of a kind in THIS run (main stream; full-row + few-row launches)."""
-            b = kby[2 * kind] + kby[2 * kind + 1] + (0.0 if main_only else skby[2 * kind] + skby[2 * kind + 1])
-            n = kcnt[2 * kind] + kcnt[2 * kind + 1] + (0 if main_only else skcnt[2 * kind] + skcnt[2 * kind + 1])
-            return b, n
+            def kind_bytes(kind, main_only=True):
+                """algorithmic bytes and launches of a kind in THIS run (main stream; full-row + few-row launches)."""
+                b = kby[2 * kind] + kby[2 * kind + 1] + (0.0 if main_only else skby[2 * kind] + skby[2 * kind + 1])
+                n = kcnt[2 * kind] + kcnt[2 * kind + 1] + (0 if main_only else skcnt[2 * kind] + skcnt[2 * kind + 1])
+                return b, n
 
-        def traffic(i, alg_per_launch):
-            """HBM bytes per launch of class i: every kind's measured-over-algorithmic ratio applied to THIS run's algorithmic bytes of
-            that kind, summed over the class's kinds, per launch of the class."""
-            tot_alg = tot_meas = 0.0
-            for kind in CLASS_KINDS[i]:
-                b, _ = kind_bytes(kind)
-                r = kind_ratio(kind)
-                if b <= 0:
-                    continue
-                if r is None:
+            def traffic(i, alg_per_launch):
+                """HBM bytes per launch of class i: every kind's measured-over-algorithmic ratio applied to THIS run's algorithmic bytes of
+                that kind, summed over the class's kinds, per launch of the class."""
+                tot_alg = tot_meas = 0.0
+                for kind in CLASS_KINDS[i]:
+                    b, _ = kind_bytes(kind)
+                    r = kind_ratio(kind)
+                    if b <= 0:
+                        continue
+                    if r is None:
+                        return None
+                    tot_alg += b
+                    tot_meas += r * b
+                return (tot_meas / tot_alg) * alg_per_launch if tot_alg > 0 else None
+
+            def traffic_measured(i):
+                return {KIND_KEYS[k]: pmc.get("kernels", {}).get(KIND_KEYS[k]) for k in CLASS_KINDS[i] if KIND_KEYS[k] in pmc.get("kernels", {})} or None
+
+            def cls(i):
+                a = fl[i] / (ms[i] * 1e-3) / 1e12 if ms[i] > 0 else None
+                n = max(cnt[i], 1)
+                return {"kernel": names[i], "achieved": a, "peak": PEAK_FP32_EQUIV_TFLOPS, "unit": "TFLOP/s",
+                        "frac": a / PEAK_FP32_EQUIV_TFLOPS if a else None, "avg_launch_ms": ms[i] / n,
+                        "launches": int(cnt[i]), "time_share_of_step": ms[i] * 1e-3 / elapsed,
+                        "mfma_executed_tflops": nprod * a if a else None, "mfma_peak_tflops": PEAK_16BIT_MFMA_TFLOPS,
+                        "algorithmic_flops_per_launch": fl[i] / n, "algorithmic_hbm_bytes_per_launch": by[i] / n,
+                        "traffic": traffic(i, by[i] / n), "traffic_source": pmc_src, "traffic_convention": pmc.get("_convention"),
+                        "traffic_measured": traffic_measured(i),
+                        "hbm_rate_at_algorithmic_bytes_TBps": by[i] / (ms[i] * 1e-3) / 1e12 if ms[i] > 0 else None,
+                        "side_stream": {"launches": int(scnt[i]), "event_ms_total": sms[i], "flop_share": sfl[i] / max(fl[i] + sfl[i], 1.0),
+                                        "algorithmic_hbm_bytes_total": sby[i],
+                                        "note": "few-row launches of the second pass, run on the lanes' side streams underneath the "
+                                                "main stream's kernels (their intervals overlap those above and are not in them)"}}
+
+            def sat(i):                                           # satellite kernels: algorithmic bytes / event time vs the HBM roof
+                if cnt[i] == 0 or ms[i] <= 0:
                     return None
-                tot_alg += b
-                tot_meas += r * b
-            return (tot_meas / tot_alg) * alg_per_launch if tot_alg > 0 else None
+                rate = by[i] / (ms[i] * 1e-3) / 1e12
+                row = {"achieved": rate, "peak": PEAK_HBM_TBPS, "unit": "TB/s", "frac": rate / PEAK_HBM_TBPS,
+                       "avg_launch_ms": ms[i] / cnt[i], "launches": int(cnt[i]), "time_share_of_step": ms[i] * 1e-3 / elapsed,
+                       "algorithmic_hbm_bytes_per_launch": by[i] / cnt[i]}
+                mp_path = os.path.join(ROOT, "profiles", "r06_c_pmc_map_pool.json")
+                if CLASS_KEYS[i] == "map_pool" and os.path.exists(mp_path):
+                    # map_pool is a VECTOR-pipe kernel (no HBM roof: it moves its bytes once, at 0.1 TB/s): its roof is the vector pipe's time.
+                    # Busy SIMD-cycles per polyline from the SQ counter passes (SQ_ACTIVE_INST_VALU, profiles/r06_c_pmc_map_pool.md: a wave64
+                    # v_fma_f32 holds a SIMD's vector pipe for 2 cycles, a v_pk_fma_f32 for 4), time from this run's HIP events.
+                    mp = json.load(open(mp_path))
+                    polylines = fl[i] / 1.5e6                          # launch_map_pool tags 1.5 MFLOP per polyline
+                    busy_rate = polylines * mp["valu_busy_simd_cycles_per_polyline"] / (ms[i] * 1e-3)
+                    peak_rate = mp["simds"] * 2.4e9                    # 1024 SIMDs x the 2.4 GHz maximum clock
+                    row["vector_pipe"] = {"bound": "valu", "achieved": busy_rate / 1e12, "peak": peak_rate / 1e12, "unit": "T busy SIMD-cycles/s",
+                                          "frac": busy_rate / peak_rate, "kernel": mp["kernel"], "valu_insts_per_polyline": mp["valu_insts_per_polyline"],
+                                          "active_lanes_per_instruction": mp["active_lanes_per_valu_inst"],
+                                          "counter_frac_at_profiled_clock": mp["valu_busy_frac_measured"], "source": "profiles/r06_c_pmc_map_pool.md",
+                                          "note": "peak at the 2.4 GHz maximum clock; the counters' own cycle count (profiled run) gives "
+                                                  "counter_frac_at_profiled_clock = 0.87: the kernel is at its FMA count (packed FMAs, round 6)"}
+                return row
+            KNAMES = ("other", "Linear + K/V-image epilogue (QKV, memory K/V): inproj_rs_kernel (row-stationary; weight-stationary gemm_ws256_kernel<..,KV> / tiled gemm_nt_bf16x6_kernel<2,2,2,..,KVIMG> by option or when K != 256)",
+                      "Linear + residual + LayerNorm epilogue (attention out-projections, MLP layers): gemm_ws256_kernel<..,LN> (weight-stationary; tiled gemm_nt_bf16x6_kernel<1,4,2,..,LN> when K != 256)",
+                      "plain Linear (cross-attention query projection, heads, map / embedding layers): gemm_ws256_kernel (256 -> 256) / gemm_nt_bf16x6_kernel<2,2,2>",
+                      "fused feed-forward block: ffn_fused_bf16x6_kernel",
+                      "causal self-attention: attention_bf16x6_kernel<1,true,true> (masks from the per-class table; <1,true,false> for the few-row launches)",
+                      "key-padded scene / cross attention: attention_bf16x6_kernel<0,true>")
 
-        def traffic_measured(i):
-            return {KIND_KEYS[k]: pmc.get("kernels", {}).get(KIND_KEYS[k]) for k in CLASS_KINDS[i] if KIND_KEYS[k] in pmc.get("kernels", {})} or None
-
-        def cls(i):
-            a = fl[i] / (ms[i] * 1e-3) / 1e12 if ms[i] > 0 else None
-            n = max(cnt[i], 1)
-            return {"kernel": names[i], "achieved": a, "peak": PEAK_FP32_EQUIV_TFLOPS, "unit": "TFLOP/s",
-                    "frac": a / PEAK_FP32_EQUIV_TFLOPS if a else None, "avg_launch_ms": ms[i] / n,
-                    "launches": int(cnt[i]), "time_share_of_step": ms[i] * 1e-3 / elapsed,
-                    "mfma_executed_tflops": nprod * a if a else None, "mfma_peak_tflops": PEAK_16BIT_MFMA_TFLOPS,
-                    "algorithmic_flops_per_launch": fl[i] / n, "algorithmic_hbm_bytes_per_launch": by[i] / n,
-                    "traffic": traffic(i, by[i] / n), "traffic_source": pmc_src, "traffic_convention": pmc.get("_convention"),
-                    "traffic_measured": traffic_measured(i),
-                    "hbm_rate_at_algorithmic_bytes_TBps": by[i] / (ms[i] * 1e-3) / 1e12 if ms[i] > 0 else None,
-                    "side_stream": {"launches": int(scnt[i]), "event_ms_total": sms[i], "flop_share": sfl[i] / max(fl[i] + sfl[i], 1.0),
-                                    "algorithmic_hbm_bytes_total": sby[i],
-                                    "note": "few-row launches of the second pass, run on the lanes' side streams underneath the "
-                                            "main stream's kernels (their intervals overlap those above and are not in them)"}}
-
-        def sat(i):                                           # satellite kernels: algorithmic bytes / event time vs the HBM roof
-            if cnt[i] == 0 or ms[i] <= 0:
-                return None
-            rate = by[i] / (ms[i] * 1e-3) / 1e12
-            row = {"achieved": rate, "peak": PEAK_HBM_TBPS, "unit": "TB/s", "frac": rate / PEAK_HBM_TBPS,
-                   "avg_launch_ms": ms[i] / cnt[i], "launches": int(cnt[i]), "time_share_of_step": ms[i] * 1e-3 / elapsed,
-                   "algorithmic_hbm_bytes_per_launch": by[i] / cnt[i]}
-            mp_path = os.path.join(ROOT, "profiles", "r06_c_pmc_map_pool.json")
-            if CLASS_KEYS[i] == "map_pool" and os.path.exists(mp_path):
-                # map_pool is a VECTOR-pipe kernel (no HBM roof: it moves its bytes once, at 0.1 TB/s): its roof is the vector pipe's time.
-                # Busy SIMD-cycles per polyline from the SQ counter passes (SQ_ACTIVE_INST_VALU, profiles/r06_c_pmc_map_pool.md: a wave64
-                # v_fma_f32 holds a SIMD's vector pipe for 2 cycles, a v_pk_fma_f32 for 4), time from this run's HIP events.
-                mp = json.load(open(mp_path))
-                polylines = fl[i] / 1.5e6                          # launch_map_pool tags 1.5 MFLOP per polyline
-                busy_rate = polylines * mp["valu_busy_simd_cycles_per_polyline"] / (ms[i] * 1e-3)
-                peak_rate = mp["simds"] * 2.4e9                    # 1024 SIMDs x the 2.4 GHz maximum clock
-                row["vector_pipe"] = {"bound": "valu", "achieved": busy_rate / 1e12, "peak": peak_rate / 1e12, "unit": "T busy SIMD-cycles/s",
-                                      "frac": busy_rate / peak_rate, "kernel": mp["kernel"], "valu_insts_per_polyline": mp["valu_insts_per_polyline"],
-                                      "active_lanes_per_instruction": mp["active_lanes_per_valu_inst"],
-                                      "counter_frac_at_profiled_clock": mp["valu_busy_frac_measured"], "source": "profiles/r06_c_pmc_map_pool.md",
-                                      "note": "peak at the 2.4 GHz maximum clock; the counters' own cycle count (profiled run) gives "
-                                              "counter_frac_at_profiled_clock = 0.87: the kernel is at its FMA count (packed FMAs, round 6)"}
-            return row
-        KNAMES = ("other", "Linear + K/V-image epilogue (QKV, memory K/V): inproj_rs_kernel (row-stationary; weight-stationary gemm_ws256_kernel<..,KV> / tiled gemm_nt_bf16x6_kernel<2,2,2,..,KVIMG> by option or when K != 256)",
-                  "Linear + residual + LayerNorm epilogue (attention out-projections, MLP layers): gemm_ws256_kernel<..,LN> (weight-stationary; tiled gemm_nt_bf16x6_kernel<1,4,2,..,LN> when K != 256)",
-                  "plain Linear (cross-attention query projection, heads, map / embedding layers): gemm_ws256_kernel (256 -> 256) / gemm_nt_bf16x6_kernel<2,2,2>",
-                  "fused feed-forward block: ffn_fused_bf16x6_kernel",
-                  "causal self-attention: attention_bf16x6_kernel<1,true,true> (masks from the per-class table; <1,true,false> for the few-row launches)",
-                  "key-padded scene / cross attention: attention_bf16x6_kernel<0,true>")
-
-        def kernel_rows(kms=kms, kcnt=kcnt, kfl=kfl, kby=kby):
-            """Launches by kernel (2 * kind + few-row flag, include/ctrlsim.h: ctrlsim_prof_collect_sub): main stream by default."""
-            rows = []
-            for i in range(nsub):
-                if kcnt[i] == 0 or kms[i] <= 0:
-                    continue
-                a = kfl[i] / (kms[i] * 1e-3) / 1e12
-                r = kind_ratio(i // 2)
-                rows.append({"kernel": KNAMES[i // 2] + (" — few-row launches (last layer on the queried rows, second pass, cached steps)" if i % 2 else ""),
-                             "kind": KIND_KEYS[i // 2],
-                             "achieved": a, "frac": a / PEAK_FP32_EQUIV_TFLOPS, "unit": "TFLOP/s", "avg_launch_ms": kms[i] / kcnt[i],
-                             "launches": int(kcnt[i]), "time_share_of_step": kms[i] * 1e-3 / elapsed,
-                             "algorithmic_hbm_bytes_per_launch": kby[i] / kcnt[i],
-                             "traffic": None if r is None else r * kby[i] / kcnt[i],
-                             "hbm_rate_at_algorithmic_bytes_TBps": kby[i] / (kms[i] * 1e-3) / 1e12})
-            return sorted(rows, key=lambda r: -r["time_share_of_step"])
-        e2e = (sum(fl[i] for i in range(ncls)) + sfl[0] + sfl[1]) / elapsed / 1e12
-        roof = {"bound": "mfma", **cls(dom),
-                "note": "achieved = algorithmic fp32 FLOPs (2MNK per Linear; 128 per visible (q,k) pair and head) / summed "
-                        f"HIP-event time of the class; peak = dense 16-bit MFMA peak / {nprod} because each fp32 product costs {nprod} "
-                        f"MFMA products ({scheme} products, fp32-class accuracy: csrc/split.h); the f32-input MFMA path (157.3 TF peak) is "
-                        "selectable per engine (ctrlsim_bind_options); traffic = HBM bytes per launch: per KERNEL (2 x FETCH_SIZE + WRITE_SIZE) / algorithmic "
-                        "bytes measured by separate rocprofv3 --pmc passes over a smaller run of this workload (traffic_measured, committed "
-                        "under profiles/ with the calibration of the counter factors) x this run's algorithmic bytes of that kernel",
-                "mfma_sustained_measured": _sustained(nprod, ms, fl, dom),
-                "other": cls(1 - dom),
-                "satellite": {CLASS_KEYS[i]: sat(i) for i in range(2, ncls)},
-                "satellite_note": "HBM-side kernels (SURVEY 8d): algorithmic bytes (DESIGN.md 4) / HIP-event time vs the 8 TB/s HBM "
-                                  "peak; sim_step is latency-bound (one workgroup per scenario, alone on its CU) and runs on the lane's "
-                                  "side stream " + ("underneath the other lane's grouping / context kernels — with --sim-guard a forward pass "
-                                                    "waits for every pending simulator step, so it never runs beside matrix kernels"
-                                                    if args.sim_guard else
-                                                    "underneath the other lane's kernels, matrix kernels included (the co-residency hazard that "
-                                                    "forbade this in round 2 is gone from the build: DESIGN.md section 4)"),
-                "kernels": kernel_rows(),
-                "kernel_bytes_all_streams": {KIND_KEYS[k]: {"launches": int(kind_bytes(k, False)[1]), "algorithmic_hbm_bytes": kind_bytes(k, False)[0]}
-                                             for k in range(1, len(KIND_KEYS)) if kind_bytes(k, False)[1]},
-                "causal_attention_by_size_class": attn_by_class,
-                "causal_attention_by_size_class_note": "untimed extra roll of the first slice with ctrlsim_attn_class_prof: share of the causal "
-                                                        "kernel's workgroup cycles (full-row launches) per context size class; cycles per 1e6 visible "
-                                                        "(query, key) pairs and head = the per-class efficiency (lower is better; the plain 24-slot "
-                                                        "class is the reference)",
-                "kernels_on_side_streams": kernel_rows(skms, skcnt, skfl, skby),
-                "kernels_note": "main-stream launches run back to back and own the chip: their event intervals are kernel times; the "
-                                "few-row launches on the lanes' side streams run UNDERNEATH them (their intervals overlap those and "
-                                "each other: time_share is event time / wall time, not a share of the critical path)",
-                "end_to_end": {"achieved": e2e, "peak": PEAK_FP32_EQUIV_TFLOPS, "unit": "TFLOP/s", "frac": e2e / PEAK_FP32_EQUIV_TFLOPS,
-                               "note": "ALL algorithmic fp32 FLOPs of the timed region (both MFMA classes on every stream + the folded map "
-                                       "encoder) / wall time of the timed region / the split-operand roof"}}
+            def kernel_rows(kms=kms, kcnt=kcnt, kfl=kfl, kby=kby):
+                """Launches by kernel (2 * kind + few-row flag, include/ctrlsim.h: ctrlsim_prof_collect_sub): main stream by default."""
+                rows = []
+                for i in range(nsub):
+                    if kcnt[i] == 0 or kms[i] <= 0:
+                        continue
+                    a = kfl[i] / (kms[i] * 1e-3) / 1e12
+                    r = kind_ratio(i // 2)
+                    rows.append({"kernel": KNAMES[i // 2] + (" — few-row launches (last layer on the queried rows, second pass, cached steps)" if i % 2 else ""),
+                                 "kind": KIND_KEYS[i // 2],
+                                 "achieved": a, "frac": a / PEAK_FP32_EQUIV_TFLOPS, "unit": "TFLOP/s", "avg_launch_ms": kms[i] / kcnt[i],
+                                 "launches": int(kcnt[i]), "time_share_of_step": kms[i] * 1e-3 / elapsed,
+                                 "algorithmic_hbm_bytes_per_launch": kby[i] / kcnt[i],
+                                 "traffic": None if r is None else r * kby[i] / kcnt[i],
+                                 "hbm_rate_at_algorithmic_bytes_TBps": kby[i] / (kms[i] * 1e-3) / 1e12})
+                return sorted(rows, key=lambda r: -r["time_share_of_step"])
+            e2e = (sum(fl[i] for i in range(ncls)) + sfl[0] + sfl[1]) / elapsed / 1e12
+            roof = {"bound": "mfma", **cls(dom),
+                    "note": "achieved = algorithmic fp32 FLOPs (2MNK per Linear; 128 per visible (q,k) pair and head) / summed "
+                            f"HIP-event time of the class; peak = dense 16-bit MFMA peak / {nprod} because each fp32 product costs {nprod} "
+                            f"MFMA products ({scheme} products, fp32-class accuracy: csrc/split.h); the f32-input MFMA path (157.3 TF peak) is "
+                            "selectable per engine (ctrlsim_bind_options); traffic = HBM bytes per launch: per KERNEL (2 x FETCH_SIZE + WRITE_SIZE) / algorithmic "
+                            "bytes measured by separate rocprofv3 --pmc passes over a smaller run of this workload (traffic_measured, committed "
+                            "under profiles/ with the calibration of the counter factors) x this run's algorithmic bytes of that kernel",
+                    "mfma_sustained_measured": _sustained(nprod, ms, fl, dom),
+                    "other": cls(1 - dom),
+                    "satellite": {CLASS_KEYS[i]: sat(i) for i in range(2, ncls)},
+                    "satellite_note": "HBM-side kernels (SURVEY 8d): algorithmic bytes (DESIGN.md 4) / HIP-event time vs the 8 TB/s HBM "
+                                      "peak; sim_step is latency-bound (one workgroup per scenario, alone on its CU) and runs on the lane's "
+                                      "side stream " + ("underneath the other lane's grouping / context kernels — with --sim-guard a forward pass "
+                                                        "waits for every pending simulator step, so it never runs beside matrix kernels"
+                                                        if args.sim_guard else
+                                                        "underneath the other lane's kernels, matrix kernels included (the co-residency hazard that "
+                                                        "forbade this in round 2 is gone from the build: DESIGN.md section 4)"),
+                    "kernels": kernel_rows(),
+                    "kernel_bytes_all_streams": {KIND_KEYS[k]: {"launches": int(kind_bytes(k, False)[1]), "algorithmic_hbm_bytes": kind_bytes(k, False)[0]}
+                                                 for k in range(1, len(KIND_KEYS)) if kind_bytes(k, False)[1]},
+                    "causal_attention_by_size_class": attn_by_class,
+                    "causal_attention_by_size_class_note": "untimed extra roll of the first slice with ctrlsim_attn_class_prof: share of the causal "
+                                                            "kernel's workgroup cycles (full-row launches) per context size class; cycles per 1e6 visible "
+                                                            "(query, key) pairs and head = the per-class efficiency (lower is better; the plain 24-slot "
+                                                            "class is the reference)",
+                    "kernels_on_side_streams": kernel_rows(skms, skcnt, skfl, skby),
+                    "kernels_note": "main-stream launches run back to back and own the chip: their event intervals are kernel times; the "
+                                    "few-row launches on the lanes' side streams run UNDERNEATH them (their intervals overlap those and "
+                                    "each other: time_share is event time / wall time, not a share of the critical path)",
+                    "end_to_end": {"achieved": e2e, "peak": PEAK_FP32_EQUIV_TFLOPS, "unit": "TFLOP/s", "frac": e2e / PEAK_FP32_EQUIV_TFLOPS,
+                                   "note": "ALL algorithmic fp32 FLOPs of the timed region (both MFMA classes on every stream + the folded map "
+                                           "encoder) / wall time of the timed region / the split-operand roof"}}
         cpu = None
-        if not args.no_cpu_baseline:                          # rank 0's host cores, whatever the world size
+        if full and not args.no_cpu_baseline:                 # rank 0's host cores, whatever the world size
             cpu = cpu_baseline(cfg, w, scns, args)
-        m, _ = acc.compute()
+        m = acc.compute()[0] if full else None
         sizes = sorted({cuts[i + 1] - cuts[i] for i in range(K)})
         shape = (N, R, args.polylines)
         cfg_tag = ("configs[4] (reward-tilt sweep: 8 tilt values x 1024 scenarios)" if (args.tilt_sweep and S * world == 8192 and shape == (64, 90, 512)) else
@@ -532,7 +556,7 @@ def main():
                        "scenarios_per_gpu": S, "scenarios_per_step": sizes, "agents": N, "rollout_steps": R,
                        "polylines": args.polylines, "model_batch_contexts": args.max_ctx, "lanes": args.lanes,
                        "lanes_pipelined": bool(args.pipeline),
-                       "phases": None if args.pipeline else {"cached_s": cached_s, "sliding_s": sliding_s,
+                       "phases": None if (args.pipeline or not full) else {"cached_s": cached_s, "sliding_s": sliding_s,
                                   "note": "main-stream time of the timed rollouts until the last lane of a slice left its K/V-cached steps "
                                           "(t < 32: few-row kernels only, on the side streams) / after it (full recompute per step)"},
                        "model_batch_reduced": any(c != max_ctx_asked for c in rank_ctx), "model_batch_contexts_requested": max_ctx_asked,
@@ -545,13 +569,14 @@ def main():
                        "size_classes": list(eng.sizes),
                        "few_row_kernels_on_side_streams": {"second_pass": eng.pass2_on_side, "first_pass_tail": eng.tail_on_side,
                                                            "cached_steps": eng.cached_on_side},
-                       "collective": (f"one all-reduce (SUM) of the {n_vec}-double metric vector + barriers, backend {backend}, world {world}"),
+                       "collective": (f"one all-reduce (SUM) of the {n_vec}-double metric vector + barriers, backend {backend}, world {world}" if full else
+                                      f"barriers + the gather / MAX all-reduce of the ranks' times, backend {backend}, world {world}"),
                        "parallelism": f"scenario-sharded x{world}"},
             "roofline": roof, "cpu_baseline": cpu, "parity_spot_check": spot,
             "clock_power_during_timed_region": clock_samples,
-            "rollout_metrics": {k: (None if v != v else v) for k, v in m.items()},
+            "rollout_metrics": None if m is None else {k: (None if v != v else v) for k, v in m.items()},
         }
-        if args.fallback_slice and f16:
+        if full and args.fallback_slice and f16:
             out["fallback_bf16x6"] = _fallback_price(args, cfg, w, device, tilt, scns, cuts, R, N, value, eng)
         _emit(out, args.detail_file)
 
@@ -685,6 +710,31 @@ def _emit(out, detail_path):
     sys.stdout.flush()
 
 
+MAX_DUMP_BYTES = 64 * 10**6      # --dump-outputs: every file of the directory together
+
+
+def _dump_outputs(eng, a, b, ids, out_dir):
+    """--dump-outputs: what a caller of the timed path receives for the LAST timed step's slice [a, b) of the resident batch
+    (RolloutEngine.results() restricted to it) — tokens [s,N,R], RTG bins [s,N,R,3], states [s,N,R+1,8], collision flags [s,N,R+1,2], focal
+    groups per step [s,R] as float32 (the integers are small: exact), and the global ids of those scenarios as float64.  A slice larger than
+    MAX_DUMP_BYTES is represented by a fixed sample of its scenarios (RandomState(0), in slice order): the same for every run with the same
+    arguments, so that two builds can be compared output for output."""
+    per = {"tokens": eng.hist_tok, "rtg_bins": eng.hist_rtg, "states": eng.hist_states, "coll": eng.coll}
+    one = 4 * (sum(t[0].numel() for t in per.values()) + eng.groups_per_step.shape[0]) + 8      # bytes per scenario, all files
+    cap = (MAX_DUMP_BYTES - 6 * 1024) // one                                                     # (npy headers)
+    if cap < 1:
+        raise SystemExit(f"bench.py: one scenario's outputs ({one} bytes) exceed --dump-outputs' limit of {MAX_DUMP_BYTES} bytes")
+    n = b - a
+    pick = np.arange(a, b) if n <= cap else a + np.sort(np.random.RandomState(0).choice(n, cap, replace=False))
+    ix = torch.from_numpy(pick).to(eng.device)
+    arrays = {name: t.index_select(0, ix).float().cpu().numpy() for name, t in per.items()}
+    arrays["n_groups"] = np.ascontiguousarray(eng.groups_per_step[:, pick].T, np.float32)
+    arrays["scenario_ids"] = np.asarray(ids, np.float64)[pick]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def _fallback_price(args, cfg, w, device, tilt, scns, cuts, R, N, value, eng):
     """Untimed: the first slice once more on the bf16x6 operand split (three bf16 planes, six MFMA products per fp32 product) — what a
     checkpoint whose activations trip the fp16 range guard of the default split pays after the automatic fallback (engine.check_finite).
@@ -789,19 +839,22 @@ class _DryEngine:
 
 
 def _finish_dry(args, dist, rank, world, eng, cfg, scns, ids, elapsed, t_own, max_ctx_asked, coll_device, gather_scalar, metrics, tilt):
-    """The tail of main() for --dry-run: the same collectives in the same order as the real run (time reduction, SUM all-reduce of the
-    metric vector, parting barrier, destroy), then rank 0 alone takes its CPU sample (here: a sleep) and prints."""
+    """The tail of main() for --dry-run: the same collectives in the same order as the real run (time reduction; with --full the SUM
+    all-reduce of the metric vector; parting barrier, destroy), then with --full rank 0 alone takes its CPU sample (here: a sleep) and prints."""
     elapsed, rank_times, rank_ctx = _reduce_times(dist, elapsed, t_own, args.max_ctx, coll_device, gather_scalar)
-    vec = eng.fake_metric_vector(metrics).to(coll_device)
-    if dist is not None:
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+    vec = None
+    if args.full:
+        vec = eng.fake_metric_vector(metrics).to(coll_device)
+        if dist is not None:
+            dist.all_reduce(vec, op=dist.ReduceOp.SUM)
     backend = dist.get_backend() if dist is not None else "none (single process)"
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if rank != 0:
         return
-    time.sleep(float(os.environ.get("CTRLSIM_BENCH_DRY_CPU_S", "0")))     # rank 0's CPU baseline: the other ranks have left already
+    if args.full:
+        time.sleep(float(os.environ.get("CTRLSIM_BENCH_DRY_CPU_S", "0")))     # rank 0's CPU baseline: the other ranks have left already
     S, N, R, K = args.scenarios, args.agents, args.rollout_steps, args.steps
     tl = np.asarray(tilt, np.float64)
     detail = {"dry_run": True, "metric": "DRY RUN of the rank flow — not a measurement", "value": None, "n_gpus": world, "steps": K,
@@ -809,8 +862,9 @@ def _finish_dry(args, dist, rank, world, eng, cfg, scns, ids, elapsed, t_own, ma
               "config": {"scenario_ids_rank0": ids, "tilt_rank0": tl[:, 0].tolist() if tl.ndim == 2 else tl.tolist(),
                          "model_batch_contexts_requested": max_ctx_asked, "model_batch_contexts_per_rank": rank_ctx,
                          "model_batch_reduced": any(c != max_ctx_asked for c in rank_ctx), "rank_elapsed_s": rank_times,
-                         "collective": f"one all-reduce (SUM) of the {int(vec.numel())}-double metric vector + barriers, backend {backend}, world {world}"},
-              "agent_steps_counted": S * N * R * world, "metric_vector": vec.cpu().numpy().tolist()}
+                         "collective": (f"one all-reduce (SUM) of the {int(vec.numel())}-double metric vector + barriers, backend {backend}, world {world}"
+                                        if args.full else f"barriers + the gather / MAX all-reduce of the ranks' times, backend {backend}, world {world}")},
+              "agent_steps_counted": S * N * R * world, "metric_vector": None if vec is None else vec.cpu().numpy().tolist()}
     # the same split as a real run: the bulky part (here the 1250-double metric vector and the per-rank lists) goes to the detail file,
     # the stdout line stays under SHORT_LINE_LIMIT whatever the world size
     with open(args.detail_file, "w") as f:

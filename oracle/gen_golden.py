@@ -40,11 +40,28 @@ LOOP = dict(dataset__waymo__max_num_agents=6, dataset__waymo__train_context_leng
             nocturne__steps=20)
 
 
+PART_BYTES = 900 * 1024          # a committed file stays under 1 MiB: larger fixtures are written as <name>.part<k>.npz (tests/helpers.py: golden)
+
+
 def save(name, **arrs):
     os.makedirs(GOLD, exist_ok=True)
     path = os.path.join(GOLD, name + ".npz")
+    for old in [path] + [os.path.join(GOLD, f) for f in os.listdir(GOLD) if f.startswith(name + ".part") and f.endswith(".npz")]:
+        if os.path.exists(old):
+            os.remove(old)
     np.savez_compressed(path, **arrs)
-    print(f"wrote {path}: {os.path.getsize(path) / 1024:.1f} KB")
+    size = os.path.getsize(path)
+    if size <= PART_BYTES:
+        print(f"wrote {path}: {size / 1024:.1f} KB")
+        return
+    os.remove(path)
+    n = -(-size // (PART_BYTES * 3 // 4))                 # parts of about 3/4 of the limit; arrays dealt out largest first
+    keys = sorted(arrs, key=lambda k: -np.asarray(arrs[k]).nbytes)
+    for k in range(n):
+        part = os.path.join(GOLD, f"{name}.part{k}.npz")
+        np.savez_compressed(part, **{key: arrs[key] for key in keys[k::n]})
+        assert os.path.getsize(part) <= PART_BYTES, part
+        print(f"wrote {part}: {os.path.getsize(part) / 1024:.1f} KB")
 
 
 # --------------------------------------------------------------------------------------------- G1-G3
@@ -980,6 +997,83 @@ def gen_contacts():
     save("contacts", **out)
 
 
+# the scripted scenes of the oracle's live-reference tests (tests/test_oracle_pinned.py): run against the real library where oracle/_ref is
+# built, against its recorded results (gen_physics_live -> tests/golden/physics_live.npz) everywhere else
+LIVE_CONTACT_CASES = [(kind, seed) for kind in ("headon", "tbone", "pairs") for seed in range(20, 32)] + \
+                     [("crowd", seed) for seed in range(20, 32)] + [("dense", seed) for seed in range(20, 26)]
+
+
+def script_set_position(sim_cls, ref_states=None):
+    """Vehicle::set_position at ARBITRARY targets (vehicle.cc:75-87): a vehicle dropped onto another one mid-run, a second one moved away
+    and back.  The targets follow the REFERENCE's states: ref_states[t] (recorded) when given, else the simulator's own.
+    -> states [17,6,6], vehicle / edge collision flags [17,6]."""
+    scn = scenarios.make_scenario(5, 1, n_agents=6, n_polylines=12, n_points=10, extent=30.0)
+    sm = sim_cls(scn.length, scn.width, scn.x, scn.y, scn.heading, scn.speed, scn.edge_segments)
+    rs = np.random.RandomState(3)
+    out = [sm.state()]
+    for t in range(16):
+        acts = np.stack([rs.uniform(-3, 3, 6), rs.uniform(-0.3, 0.3, 6)], 1)
+        st0 = out[t][0] if ref_states is None else ref_states[t]
+        if t == 5:
+            sm.set_position(2, float(st0[0, 0]) + 0.5, float(st0[0, 1]) + 0.25)      # onto vehicle 0
+        if t == 8:
+            sm.set_position(4, 500.0, -300.0)
+        if t == 11:
+            sm.set_position(4, float(st0[1, 0]) - 1.0, float(st0[1, 1]))             # back, onto vehicle 1
+        for i in range(6):
+            sm.set_action(i, float(acts[i, 0]), float(acts[i, 1]))
+        sm.step(0.1)
+        out.append(sm.state())
+    sm.close()
+    return tuple(np.stack([o[k] for o in out]) for k in range(3))
+
+
+def script_expert(sim_cls, ref_states=None):
+    """Scenario::Step with expert-controlled objects (nocturne/cpp/src/scenario.cc:272-284): two of six vehicles follow a log that drives
+    one of them THROUGH a policy vehicle (that log follows the REFERENCE's states: ref_states[t] when given, else the simulator's own), a
+    third switches between expert and free control mid-run, one expert stands still.  -> states [25,6,6], vehicle / edge collision flags
+    [25,6], Box2D bodies [25,6,6], the log of vehicle 3 [24,4]."""
+    scn = scenarios.make_scenario(11, 2, n_agents=6, n_polylines=12, n_points=10, extent=30.0)
+    sm = sim_cls(scn.length, scn.width, scn.x, scn.y, scn.heading, scn.speed, scn.edge_segments)
+    rs = np.random.RandomState(7)
+    T = 24
+    # logs: vehicle 1 drives a straight line through vehicle 0's start position; vehicle 3 circles; vehicle 5 stands still
+    tt = np.arange(1, T + 1, dtype=np.float32)
+    log = {1: np.stack([scn.x[0] - 6.0 + 0.6 * tt, np.full(T, scn.y[0] + 0.3, np.float32), np.full(T, 0.05, np.float32), np.full(T, 6.0, np.float32)], 1),
+           3: np.stack([scn.x[3] + 4 * np.cos(0.2 * tt), scn.y[3] + 4 * np.sin(0.2 * tt), 0.2 * tt + np.float32(np.pi / 2), np.full(T, 0.8, np.float32)], 1),
+           5: np.stack([np.full(T, scn.x[5]), np.full(T, scn.y[5]), np.full(T, scn.heading[5]), np.zeros(T, np.float32)], 1)}
+    out, body = [sm.state()], [sm.body()]
+    for t in range(T):
+        acts = np.stack([rs.uniform(-3, 3, 6), rs.uniform(-0.3, 0.3, 6)], 1)
+        st0 = out[t][0] if ref_states is None else ref_states[t]
+        if 5 <= t < 12:                                         # the log of vehicle 1 runs over vehicle 0 for a while
+            log[1][t, 0], log[1][t, 1] = st0[0, 0] + np.float32(1.5 - 0.4 * (t - 5)), st0[0, 1] + np.float32(0.3)
+        for i in range(6):
+            sm.set_action(i, float(acts[i, 0]), float(acts[i, 1]))
+        for i, lg in log.items():
+            if i == 3 and 8 <= t < 14:
+                continue                                        # free control for a while, then expert again
+            sm.set_expert(i, float(lg[t, 0]), float(lg[t, 1]), float(lg[t, 2]), float(lg[t, 3]))
+        sm.step(0.1)
+        out.append(sm.state())
+        body.append(sm.body())
+    sm.close()
+    return tuple(np.stack([o[k] for o in out]) for k in range(3)) + (np.stack(body), log[3].astype(np.float32))
+
+
+def gen_physics_live():
+    """The REAL FreeCar + Box2D on the scripted scenes of the oracle's live-reference tests: trajectories, collision flags, bodies (the
+    pile-ups and lots in a file of their own: each file well under the size limit of a committed file)."""
+    out, crowd = {}, {}
+    for k, (kind, seed) in enumerate(LIVE_CONTACT_CASES):
+        o = crowd if kind in ("crowd", "dense") else out
+        o[f"c{k}_traj"], o[f"c{k}_coll_veh"], o[f"c{k}_body"] = run_scripted(RefSim, contact_scene(kind, seed))
+    out["setpos_states"], out["setpos_coll_veh"], out["setpos_coll_edge"] = script_set_position(RefSim)
+    out["expert_states"], out["expert_coll_veh"], out["expert_coll_edge"], out["expert_body"], _ = script_expert(RefSim)
+    save("physics_live", **out)
+    save("physics_live_crowd", **crowd)
+
+
 def gen_collision():
     geo = ref_geo()
     rs = np.random.RandomState(6)
@@ -1488,7 +1582,8 @@ def gen_dt_loop():
 ALL = dict(model=gen_model, model_trained=gen_model_trained, closed_loop_trained=gen_closed_loop_trained, closed_loop_wide_trained=gen_closed_loop_wide_trained, features=gen_features, sampling=gen_sampling, physics=gen_physics,
            collision=gen_collision, closed_loop=gen_closed_loop, closed_loop_full=gen_closed_loop_full, closed_loop_wide=gen_closed_loop_wide, metrics=gen_metrics, interesting=gen_interesting, preprocessed=gen_preprocessed, ingest_gt=gen_ingest_gt, state_dict=gen_state_dict, bicycle=gen_bicycle, contacts=gen_contacts,
            planner_adversary=gen_planner_adversary, ingest=gen_ingest,
-           variants=gen_variants, dense_reward=gen_dense_reward, dt_loop=gen_dt_loop, own_return=gen_own_return, model_flags=gen_model_flags)
+           variants=gen_variants, dense_reward=gen_dense_reward, dt_loop=gen_dt_loop, own_return=gen_own_return, model_flags=gen_model_flags,
+           physics_live=gen_physics_live)
 
 if __name__ == "__main__":
     assert ref_shims.available(), "the reference tree is required to (re)generate golden vectors"

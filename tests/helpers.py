@@ -14,8 +14,26 @@ LOOP = dict(dataset__waymo__max_num_agents=6, dataset__waymo__train_context_leng
 WIDE = dict(dataset__waymo__max_num_agents=64, dataset__waymo__max_num_road_polylines=512)
 
 
+class _Parts(dict):
+    """The arrays of a fixture stored in parts, with the `files` list of an NpzFile."""
+    @property
+    def files(self):
+        return list(self)
+
+
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
+    """tests/golden/<name>.npz, or the parts <name>.part<k>.npz of a fixture larger than a committed file may be (oracle/gen_golden.py:
+    save) merged into one mapping."""
+    path = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(path):
+        return np.load(path)
+    parts = sorted(f for f in os.listdir(GOLDEN) if f.startswith(name + ".part") and f.endswith(".npz"))
+    assert parts, f"no fixture {name} under tests/golden"
+    out = _Parts()
+    for f in parts:
+        with np.load(os.path.join(GOLDEN, f)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def cfg_of(kind, variant=None):

@@ -158,6 +158,53 @@ def test_bench_short_line_of_a_full_report_stays_under_the_limit():
     assert s["config"]["workload"].startswith("BASELINE.json configs[2]") and "model" not in s["config"] and s["dtype"].startswith("f32")
 
 
+def test_bench_plain_dry_run_has_no_full_report():
+    """Without --full the rank flow ends after the time reduction: no metric all-reduce, no CPU sample on rank 0 (CTRLSIM_BENCH_DRY_CPU_S
+    is a --full cost), the same line otherwise."""
+    out, wall = _bench_dry(2, 3, {"CTRLSIM_BENCH_DRY_CPU_S": "30"})
+    assert out["n_gpus"] == 2 and out["agent_steps_counted"] == 3 * 4 * 20 * 2 and out["config"]["scenario_ids_rank0"] == [0, 2, 4]
+    assert out["metric_vector"] is None and "metric vector" not in out["config"]["collective"] and "world 2" in out["config"]["collective"]
+    assert wall < 30
+
+
+def test_bench_dump_outputs_is_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """bench._dump_outputs on a stand-in engine (CPU tensors of the engine's result layout): the slice [a, b) whole when it fits, else a
+    sample of it that is the same on every call, float32 / float64 files within MAX_DUMP_BYTES that hold exactly the engine's rows."""
+    import sys
+    import types
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    S, N, R = 40, 5, 7
+    g = torch.Generator().manual_seed(0)
+    eng = types.SimpleNamespace(device=torch.device("cpu"),
+                                hist_tok=torch.randint(0, 130, (S, N, R), generator=g, dtype=torch.int32),
+                                hist_rtg=torch.randint(0, 350, (S, N, R, 3), generator=g, dtype=torch.int32),
+                                hist_states=torch.randn(S, N, R + 1, 8, generator=g),
+                                coll=torch.randint(0, 2, (S, N, R + 1, 2), generator=g, dtype=torch.uint8),
+                                groups_per_step=np.random.RandomState(1).randint(1, 4, (R, S)).astype(np.int32))
+    ids = list(range(100, 100 + S))
+
+    def dump(d, a, b):
+        bench._dump_outputs(eng, a, b, ids, str(tmp_path / d))
+        return {f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))}
+
+    whole = dump("whole", 30, 40)
+    assert whole["scenario_ids"].tolist() == ids[30:40] and whole["scenario_ids"].dtype == np.float64
+    assert np.array_equal(whole["tokens"], eng.hist_tok[30:40].float().numpy()) and whole["states"].dtype == np.float32
+    assert np.array_equal(whole["rtg_bins"], eng.hist_rtg[30:40].float().numpy())
+    assert np.array_equal(whole["coll"], eng.coll[30:40].float().numpy())
+    assert np.array_equal(whole["n_groups"], eng.groups_per_step[:, 30:40].T.astype(np.float32))
+    one = 4 * (N * R + N * R * 3 + N * (R + 1) * 8 + N * (R + 1) * 2 + R) + 8
+    monkeypatch.setattr(bench, "MAX_DUMP_BYTES", 6 * 1024 + 7 * one)            # room for 7 scenarios
+    s1, s2 = dump("s1", 0, 30), dump("s2", 0, 30)
+    picked = s1["scenario_ids"].astype(int) - 100
+    assert len(picked) == 7 and np.all(np.diff(picked) > 0) and picked.min() >= 0 and picked.max() < 30
+    for k in s1:
+        assert np.array_equal(s1[k], s2[k]), k
+    assert np.array_equal(s1["states"], eng.hist_states[torch.from_numpy(picked)].numpy())
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= bench.MAX_DUMP_BYTES
+
+
 def test_bench_rank_flow_dry_run_world_8():
     """Round 5 (round-4 review, item 7): no 8-GPU node is available to the builder, so everything rank-dependent in bench.py is rehearsed on
     the CPU at world size 8 over gloo, launched as the driver launches it: interleaved scenario ids, the tilt sweep following the GLOBAL
@@ -166,7 +213,7 @@ def test_bench_rank_flow_dry_run_world_8():
     1250-double metric vector, the parting barrier, and rank 0 alone spending seconds on its CPU sample AFTER the others have left the
     process group (no collective is pending, so no rendezvous timeout can fire)."""
     from ctrlsim_amd.dist import TILT_SWEEP
-    out, wall = _bench_dry(8, 6, {"CTRLSIM_BENCH_DRY_OOM_RANKS": "3,5", "CTRLSIM_BENCH_DRY_CPU_S": "4"}, ("--tilt-sweep",))
+    out, wall = _bench_dry(8, 6, {"CTRLSIM_BENCH_DRY_OOM_RANKS": "3,5", "CTRLSIM_BENCH_DRY_CPU_S": "4"}, ("--tilt-sweep", "--full"))
     c = out["config"]
     assert out["dry_run"] is True and out["value"] is None and out["n_gpus"] == 8
     assert c["scenario_ids_rank0"] == [0, 8, 16, 24, 32, 40]
@@ -178,6 +225,6 @@ def test_bench_rank_flow_dry_run_world_8():
     assert "world 8" in c["collective"] and "gloo" in c["collective"]
     assert out["agent_steps_counted"] == 6 * 4 * 20 * 8
     # the reduced metric vector equals ONE process rolling the union of the ids (0 .. 47), whatever the sharding
-    one, _ = _bench_dry(1, 48)
+    one, _ = _bench_dry(1, 48, extra_args=("--full",))
     np.testing.assert_allclose(out["metric_vector"], one["metric_vector"], rtol=1e-12, atol=1e-12)
     assert one["config"]["scenario_ids_rank0"] == list(range(48))

@@ -6,6 +6,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -14,18 +15,22 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(extra_env, *args):
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+SMALL = ["--agents", "12", "--polylines", "40", "--rollout-steps", "8", "--max-ctx", "32"]
+
+
+def _bench(extra_env, *args, full=True):
     env = dict(os.environ, **extra_env)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scenarios", "6", "--steps", "2", "--warmup", "0",
-                        "--agents", "12", "--polylines", "40", "--rollout-steps", "8", "--max-ctx", "32", "--no-cpu-baseline",
-                        "--spot-check", "2", "--detail-file", os.path.join(ROOT, "gpurun_out", "bench_detail_test.json"), *args], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return _short_and_detail(r.stdout)
+    with tempfile.TemporaryDirectory() as td:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scenarios", "6", "--steps", "2", "--warmup", "0", *SMALL,
+                            *(["--full", "--no-cpu-baseline", "--spot-check", "2"] if full else []),
+                            "--detail-file", os.path.join(td, "bench_detail_test.json"), *args],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return _short_and_detail(r.stdout, full)
 
 
-def _short_and_detail(stdout):
+def _short_and_detail(stdout, full=True):
     """The run's ONE stdout line (what the driver parses: short, complete) and, returned, the detail file it names."""
     lines = [ln for ln in stdout.splitlines() if ln.strip()]
     # exactly one JSON line, and it is the LAST line of stdout (RCCL's version banner, printed through C stdio, must not follow it)
@@ -41,7 +46,11 @@ def _short_and_detail(stdout):
     with open(os.path.join(ROOT, short["detail_file"])) as f:
         detail = json.load(f)
     assert short["value"] == pytest.approx(detail["value"], rel=1e-5) and short["n_gpus"] == detail["n_gpus"]
-    assert short["parity_spot_check"]["identical"] == detail["parity_spot_check"]["identical"]
+    if full:
+        assert short["parity_spot_check"]["identical"] == detail["parity_spot_check"]["identical"]
+    else:                            # a plain run: the headline figure alone
+        assert short["parity_spot_check"] is None and short["cpu_baseline"] is None and short["roofline"]["achieved"] is None
+        assert detail["roofline"] is None and detail["rollout_metrics"] is None and detail["clock_power_during_timed_region"] is None
     return detail
 
 
@@ -61,7 +70,7 @@ def test_bench_collective_runs_through_rccl_at_world_size_one():
         assert len(out["config"]["size_classes"]) == 16
 
 
-def test_bench_at_world_size_two_on_the_one_gpu_that_exists():
+def test_bench_at_world_size_two_on_the_one_gpu_that_exists(tmp_path):
     """Round 4: bench.py's rank > 0 branches — interleaved scenario ids, the MAX all-reduce of the elapsed time, the SUM
     all-reduce of the metric vector, the parting barrier — run with TWO ranks, launched exactly as the driver launches N > 1
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port P bench.py --gpus 2 ...`), both on
@@ -70,12 +79,11 @@ def test_bench_at_world_size_two_on_the_one_gpu_that_exists():
     count both ranks, rank 0 alone prints the JSON line and both ranks exit cleanly (the reference's equivalent is a merge-less file
     partition, evaluators/policy_evaluator.py:466-490,578-593)."""
     import socket
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    common = ["--steps", "1", "--warmup", "0", "--agents", "12", "--polylines", "40", "--rollout-steps", "8", "--max-ctx", "32",
-              "--no-cpu-baseline", "--spot-check", "2", "--detail-file", os.path.join(ROOT, "gpurun_out", "bench_detail_test2.json")]
+    common = ["--steps", "1", "--warmup", "0", *SMALL, "--full", "--no-cpu-baseline", "--spot-check", "2",
+              "--detail-file", os.path.join(str(tmp_path), "bench_detail_test2.json")]
     env = dict(os.environ, CTRLSIM_BENCH_DEBUG_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -93,3 +101,31 @@ def test_bench_at_world_size_two_on_the_one_gpu_that_exists():
     for k, v in one["rollout_metrics"].items():
         assert two["rollout_metrics"][k] == pytest.approx(v, rel=1e-12, abs=1e-15), k
     assert two["parity_spot_check"]["identical"] is True
+
+
+def test_bench_plain_run_and_dumped_outputs():
+    """A plain run (no --full) prints the headline line without the --full report, and --dump-outputs writes what its last timed step
+    computed: float32 / float64 arrays within bench.MAX_DUMP_BYTES, identical from run to run, and identical to a --full run's, whose
+    untimed extra rolls of the first slice (here the only one) come after the dump."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    with tempfile.TemporaryDirectory() as td:
+        dirs = [os.path.join(td, x) for x in ("plain1", "plain2", "full")]
+        plain = _bench({}, "--steps", "1", "--dump-outputs", dirs[0], full=False)
+        _bench({}, "--steps", "1", "--dump-outputs", dirs[1], full=False)
+        _bench({}, "--steps", "1", "--dump-outputs", dirs[2])
+        assert plain["steps"] == 1 and plain["value"] == pytest.approx(6 * 12 * 8 / (plain["ms_per_step"] / 1e3), rel=1e-6)
+        names = ["coll.npy", "n_groups.npy", "rtg_bins.npy", "scenario_ids.npy", "states.npy", "tokens.npy"]
+        for d in dirs:
+            assert sorted(os.listdir(d)) == names, d
+            assert sum(os.path.getsize(os.path.join(d, n)) for n in names) <= bench.MAX_DUMP_BYTES
+        got = [{n: np.load(os.path.join(d, n)) for n in names} for d in dirs]
+        for n in names:
+            assert got[0][n].dtype in (np.float32, np.float64), n
+            for other in got[1:]:
+                assert np.array_equal(got[0][n], other[n]), n
+        assert got[0]["scenario_ids.npy"].tolist() == [0, 1, 2, 3, 4, 5]
+        assert got[0]["tokens.npy"].shape == (6, 12, 8) and got[0]["rtg_bins.npy"].shape == (6, 12, 8, 3)
+        assert got[0]["states.npy"].shape == (6, 12, 9, 8) and got[0]["coll.npy"].shape == (6, 12, 9, 2)
+        assert got[0]["n_groups.npy"].shape == (6, 8) and got[0]["n_groups.npy"].sum() > 0 and np.abs(got[0]["states.npy"]).max() > 0

@@ -169,10 +169,10 @@ def test_sim_oracle_bit_exact_vs_reference_physics_fixture():
     assert g["traj"][-1, 0, 3] == 0.0 and abs(g["traj"][-1, 1, 3] - 50.0) < 1e-4
 
 
-@pytest.mark.skipif(not sim_libs.RefSim.available(), reason="oracle/_ref not built (needs /root/reference)")
 def test_sim_oracle_bit_exact_vs_live_reference_physics():
+    """The C oracle against the real FreeCar + Box2D, live where oracle/_ref is built, else against its recorded run (physics.npz)."""
     g = golden("physics")
-    a = _run_scripted(sim_libs.RefSim, g)
+    a = _run_scripted(sim_libs.RefSim, g) if sim_libs.RefSim.available() else (g["traj"], g["coll_veh"], g["coll_edge"])
     b = _run_scripted(sim_libs.OracleSim, g)
     assert np.array_equal(a[0], g["traj"])
     for x, y in zip(a, b):
@@ -211,30 +211,29 @@ def test_sim_oracle_contacts_bit_exact_vs_reference_fixture():
         assert np.array_equal(body.view(np.int32), g[f"c{k}_body"].view(np.int32)), k
 
 
-@pytest.mark.skipif(not sim_libs.RefSim.available(), reason="oracle/_ref not built (needs /root/reference)")
 def test_sim_oracle_contacts_bit_exact_vs_live_reference():
-    """Fresh random encounters against the real Box2D, live: two-car collisions (alone or several per world), pile-ups of
-    8-16 cars and lots of 32-48 cars that overlap from the start — all bit-exact (the order in which contacts of one step
-    are created comes from the restated b2DynamicTree)."""
+    """Fresh random encounters against the real Box2D: two-car collisions (alone or several per world), pile-ups of 8-16 cars and lots
+    of 32-48 cars that overlap from the start — all bit-exact (the order in which contacts of one step are created comes from the
+    restated b2DynamicTree).  Live where oracle/_ref is built (and then the recording must be that run), else against the reference's
+    recorded runs (physics_live.npz, physics_live_crowd.npz: oracle/gen_golden.py::gen_physics_live)."""
     import gen_golden
+    live = sim_libs.RefSim.available()
+    rec = {**golden("physics_live"), **golden("physics_live_crowd")}
     n_coll = 0
     same = lambda x, y: np.array_equal(x.view(x.dtype if x.dtype == np.uint8 else np.int32),
                                        y.view(y.dtype if y.dtype == np.uint8 else np.int32))
-    for kind in ("headon", "tbone", "pairs"):
-        for seed in range(20, 32):
-            sc = gen_golden.contact_scene(kind, seed)
-            a = _run_scripted_body(sim_libs.RefSim, sc)
-            b = _run_scripted_body(sim_libs.OracleSim, sc)
-            n_coll += int(a[1].sum())
-            assert all(same(x, y) for x, y in zip(a, b)), (kind, seed)
-    assert n_coll > 100
-    for kind, seeds in (("crowd", range(20, 32)), ("dense", range(20, 26))):
-        for seed in seeds:
-            sc = gen_golden.contact_scene(kind, seed)
-            a = _run_scripted_body(sim_libs.RefSim, sc)
-            b = _run_scripted_body(sim_libs.OracleSim, sc)
+    for k, (kind, seed) in enumerate(gen_golden.LIVE_CONTACT_CASES):
+        sc = gen_golden.contact_scene(kind, seed)
+        r = tuple(rec[f"c{k}_{key}"] for key in ("traj", "coll_veh", "body"))
+        a = _run_scripted_body(sim_libs.RefSim, sc) if live else r
+        assert all(same(x, y) for x, y in zip(a, r)), (kind, seed)
+        b = _run_scripted_body(sim_libs.OracleSim, sc)
+        if kind in ("crowd", "dense"):
             assert a[1].sum() > 20
-            assert all(same(x, y) for x, y in zip(a, b)), (kind, seed)
+        else:
+            n_coll += int(a[1].sum())
+        assert all(same(x, y) for x, y in zip(a, b)), (kind, seed)
+    assert n_coll > 100
 
 
 def test_collision_oracle_matches_reference_geometry():
@@ -577,36 +576,22 @@ def test_rollout_oracle_matches_reference_decision_transformer_loop():
     assert g["loop_rtgs"][:, -1, 1].max() < 90.0               # the vehicle-distance RTG is being spent
 
 
-@pytest.mark.skipif(not sim_libs.RefSim.available(), reason="oracle/_ref not built (needs /root/reference)")
 def test_oracle_general_set_position_matches_real_box2d_live():
     """Vehicle::set_position at an ARBITRARY target (vehicle.cc:75-87 -> BaseCar::SetPosition = b2Body::SetTransform at the current
     angle, physics/BaseCar.cpp:28-32) — not only the (-1e6, -1e6) parking the rollout uses: a vehicle is dropped onto another one
-    mid-run, a second one moved away and back.  The C oracle against the real FreeCar + Box2D, bit-exact, through the contacts
-    that follow."""
-    scn = scenarios.make_scenario(5, 1, n_agents=6, n_polylines=12, n_points=10, extent=30.0)
-    sims = [cls(scn.length, scn.width, scn.x, scn.y, scn.heading, scn.speed, scn.edge_segments) for cls in (sim_libs.RefSim, sim_libs.OracleSim)]
-    rs = np.random.RandomState(3)
-    hit = 0
-    for t in range(16):
-        acts = np.stack([rs.uniform(-3, 3, 6), rs.uniform(-0.3, 0.3, 6)], 1)
-        st0 = sims[0].state()[0]
-        for sm in sims:
-            if t == 5:
-                sm.set_position(2, float(st0[0, 0]) + 0.5, float(st0[0, 1]) + 0.25)      # onto vehicle 0
-            if t == 8:
-                sm.set_position(4, 500.0, -300.0)
-            if t == 11:
-                sm.set_position(4, float(st0[1, 0]) - 1.0, float(st0[1, 1]))             # back, onto vehicle 1
-            for i in range(6):
-                sm.set_action(i, float(acts[i, 0]), float(acts[i, 1]))
-            sm.step(0.1)
-        (a, av, ae), (b, bv, be) = sims[0].state(), sims[1].state()
-        assert np.array_equal(a, b), t
-        assert np.array_equal(av, bv) and np.array_equal(ae, be), t
-        hit += int(av.sum())
-    assert hit > 0
-    for sm in sims:
-        sm.close()
+    mid-run, a second one moved away and back (oracle/gen_golden.py::script_set_position).  The C oracle against the real FreeCar +
+    Box2D, bit-exact, through the contacts that follow: live where oracle/_ref is built (and then the recording must be that run), else
+    against the reference's recorded run (physics_live.npz)."""
+    import gen_golden
+    g = golden("physics_live")
+    rec = (g["setpos_states"], g["setpos_coll_veh"], g["setpos_coll_edge"])
+    ref = gen_golden.script_set_position(sim_libs.RefSim) if sim_libs.RefSim.available() else rec
+    for x, y in zip(ref, rec):
+        assert np.array_equal(x, y)
+    ora = gen_golden.script_set_position(sim_libs.OracleSim, ref_states=ref[0])
+    for t in range(len(ref[0])):
+        assert all(np.array_equal(x[t], y[t]) for x, y in zip(ref, ora)), t
+    assert ref[1].sum() > 0
 
 
 def test_oracle_expert_controlled_vehicles_match_real_box2d_live():
@@ -614,38 +599,19 @@ def test_oracle_expert_controlled_vehicles_match_real_box2d_live():
     expert vehicle is put on the LOGGED position, heading and speed through Vehicle::set_position / set_heading / set_speed
     (vehicle.cc:75-105: two b2Body::SetTransform — proxy synchronisation, new-contact search at the top of the next step — and
     SetLinearVelocity, which wakes the body).  Two of six vehicles follow a log that drives one of them THROUGH a policy vehicle, a third
-    switches between expert and free control mid-run, one expert stands still (zero velocity: not woken).  The C oracle against the real
-    FreeCar + Box2D, bit for bit, collision flags included."""
-    scn = scenarios.make_scenario(11, 2, n_agents=6, n_polylines=12, n_points=10, extent=30.0)
-    sims = [cls(scn.length, scn.width, scn.x, scn.y, scn.heading, scn.speed, scn.edge_segments) for cls in (sim_libs.RefSim, sim_libs.OracleSim)]
-    rs = np.random.RandomState(7)
-    T = 24
-    # logs: vehicle 1 drives a straight line through vehicle 0's start position; vehicle 3 circles; vehicle 5 stands still
-    tt = np.arange(1, T + 1, dtype=np.float32)
-    log = {1: np.stack([scn.x[0] - 6.0 + 0.6 * tt, np.full(T, scn.y[0] + 0.3, np.float32), np.full(T, 0.05, np.float32), np.full(T, 6.0, np.float32)], 1),
-           3: np.stack([scn.x[3] + 4 * np.cos(0.2 * tt), scn.y[3] + 4 * np.sin(0.2 * tt), 0.2 * tt + np.float32(np.pi / 2), np.full(T, 0.8, np.float32)], 1),
-           5: np.stack([np.full(T, scn.x[5]), np.full(T, scn.y[5]), np.full(T, scn.heading[5]), np.zeros(T, np.float32)], 1)}
-    hit = 0
-    for t in range(T):
-        acts = np.stack([rs.uniform(-3, 3, 6), rs.uniform(-0.3, 0.3, 6)], 1)
-        st0 = sims[0].state()[0]
-        if 5 <= t < 12:                                         # the log of vehicle 1 runs over vehicle 0 for a while
-            log[1][t, 0], log[1][t, 1] = st0[0, 0] + np.float32(1.5 - 0.4 * (t - 5)), st0[0, 1] + np.float32(0.3)
-        for sm in sims:
-            for i in range(6):
-                sm.set_action(i, float(acts[i, 0]), float(acts[i, 1]))
-            for i, lg in log.items():
-                if i == 3 and 8 <= t < 14:
-                    continue                                    # free control for a while, then expert again
-                sm.set_expert(i, float(lg[t, 0]), float(lg[t, 1]), float(lg[t, 2]), float(lg[t, 3]))
-            sm.step(0.1)
-        (a, av, ae), (b, bv, be) = sims[0].state(), sims[1].state()
-        assert np.array_equal(a, b), t
-        assert np.array_equal(av, bv) and np.array_equal(ae, be), t
-        assert np.array_equal(sims[0].body(), sims[1].body()), t
-        if not (8 <= t < 14):
-            assert np.array_equal(a[3, :4], log[3][t].astype(np.float32)), t      # an expert vehicle reads back its log
-        hit += int(av.sum())
-    assert hit > 0
-    for sm in sims:
-        sm.close()
+    switches between expert and free control mid-run, one expert stands still (zero velocity: not woken): oracle/gen_golden.py::
+    script_expert.  The C oracle against the real FreeCar + Box2D, bit for bit, collision flags and bodies included: live where oracle/_ref
+    is built (and then the recording must be that run), else against the reference's recorded run (physics_live.npz)."""
+    import gen_golden
+    g = golden("physics_live")
+    rec = (g["expert_states"], g["expert_coll_veh"], g["expert_coll_edge"], g["expert_body"])
+    ref = gen_golden.script_expert(sim_libs.RefSim)[:4] if sim_libs.RefSim.available() else rec
+    for x, y in zip(ref, rec):
+        assert np.array_equal(x, y)
+    ora = gen_golden.script_expert(sim_libs.OracleSim, ref_states=ref[0])
+    log3 = ora[4]
+    for t in range(len(ref[0])):
+        assert all(np.array_equal(x[t], y[t]) for x, y in zip(ref, ora[:4])), t
+        if t >= 1 and not (8 <= t - 1 < 14):
+            assert np.array_equal(ref[0][t][3, :4], log3[t - 1]), t                 # an expert vehicle reads back its log
+    assert ref[1].sum() > 0

@@ -1,11 +1,13 @@
 #!/bin/bash
 # One GPU-box call that produces everything tools/make_profile_summary.py needs for round $1 (e.g. r02):
 #   an un-profiled bench line, the rocprofv3 --kernel-trace --stats summary of the same command, and the two PMC passes
-#   (FETCH_SIZE / WRITE_SIZE, separate, no tracing flags) over a smaller run of the same workload.
+#   (FETCH_SIZE / WRITE_SIZE, separate, no tracing flags) over a smaller run of the same workload.  Every bench command runs with --full:
+#   the summaries read its per-kernel rows and algorithmic byte counts.
 # usage (from the repo root, on the GPU box):  bash tools/profile_round.sh r02
 R=${1:-r02}
-CMD="python bench.py --scenarios 204 --steps 2 --warmup 1 --spot-check 0 --no-class-profile --fallback-slice 0"
+CMD="python bench.py --full --scenarios 204 --steps 2 --warmup 1 --spot-check 0 --no-class-profile --fallback-slice 0"
 PMC="python bench.py --scenarios 102 --steps 1 --warmup 0 --no-cpu-baseline --spot-check 0 --no-class-profile --fallback-slice 0 --detail-file gpurun_out/pmc_$R/detail.json"
+PMC="$PMC --full"
 mkdir -p gpurun_out/prof_$R gpurun_out/pmc_$R
 $CMD --detail-file gpurun_out/bench_$R.json > gpurun_out/bench_$R.short.json 2> gpurun_out/bench_$R.err     # (the detail file is what the summaries read)
 echo "$CMD --no-cpu-baseline" > gpurun_out/prof_$R/command.txt
