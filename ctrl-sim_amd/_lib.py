@@ -35,6 +35,11 @@ class Ctx(C.Structure):
                                            "road_pts", "road_types")]
 
 
+class LossCfg(C.Structure):
+    """ctrlsim_loss_cfg (include/ctrlsim.h)."""
+    _fields_ = [(k, C.c_int) for k in ("supervise_moving", "local_frame_predictions", "fused", "pad_")]
+
+
 P, I, L, D, F = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_float
 U64 = C.c_uint64
 
@@ -106,6 +111,11 @@ SIGNATURES = {
     "ctrlsim_dt_forward_actions": (I, [P, I, I, C.POINTER(Ctx), P, P, P]),
     "ctrlsim_map_pool": (I, [P, I, P, P, P, P]),
     "ctrlsim_forward_all": (I, [P, I, I, C.POINTER(Ctx), P, P, P, P, P]),
+    "ctrlsim_forward_loss_workspace_bytes": (L, [C.POINTER(Dims), I, I]),
+    "ctrlsim_forward_loss": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), P, P, P, P, P]),
+    "ctrlsim_head_ce": (I, [P, I, P, P, P, I, I, I, P, P]),
+    "ctrlsim_loss_scratch_bytes": (L, [I, I, I]),
+    "ctrlsim_loss_from_preds": (I, [C.POINTER(Dims), I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), P, P, P, P, P, P, P, P]),
     "ctrlsim_dt_forward_pass2": (I, [P, I, I, I, I, I, C.POINTER(Ctx), P, P, P, P, I, P]),
     "ctrlsim_dt_forward_pass1_cached": (I, [P, I, I, C.POINTER(Ctx), P, P, P]),
     "ctrlsim_sample_rtg": (I, [P, I, I, P, P, P, P, P, P, U64, P, I, P, I, I, I, P]),

@@ -8,9 +8,9 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# sources -> extra flags.  The three split-operand kernel files are compiled ONCE PER SCHEME (csrc/split.h: -DCTRLSIM_F16X3=1 two fp16
+# sources -> extra flags.  The split-operand kernel files are compiled ONCE PER SCHEME (csrc/split.h: -DCTRLSIM_F16X3=1 two fp16
 # planes, =0 three bf16 planes; each build lives in its own namespace) and dispatch.hip picks one at run time.
-SPLIT_SRCS = ("gemm_bf16x6", "ffn_fused", "attention_bf16x6")
+SPLIT_SRCS = ("gemm_bf16x6", "ffn_fused", "attention_bf16x6", "loss")
 # EVERY source is compiled with -fno-slp-vectorize (COMMON below).  With clang's SLP vectoriser on — it stitches neighbouring scalar
 # float operations into packed-fp32 instructions with operand swizzles (v_pk_mul_f32 ... op_sel:[1,0], v_pk_mov_b32) and neighbouring
 # LDS accesses into 64 / 128-bit ones — a workgroup that SHARES ITS CU with matrix-pipe workgroups of ANOTHER kernel now and then
@@ -59,7 +59,8 @@ def compile_cmd(name, extra, obj):
     return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj] + COMMON.split() + extra.split()
 
 
-HOST_ONLY = ("dispatch", "api")            # objects without device code: an EMPTY disassembly is expected there and nowhere else
+# objects without device code: an EMPTY disassembly is expected there and nowhere else (loss.hip's kernels exist in the two-plane build only)
+HOST_ONLY = ("dispatch", "api", "loss_s0")
 
 
 def _llvm_tool(name):

@@ -35,6 +35,8 @@
   int launch_kv_split_rows_classes(const float*, const float*, int, int, const KvRowsHost*, void*, hipStream_t);                  \
   int launch_kv_zero_tail(int, int, int, int, void*, hipStream_t);                                                                \
   int launch_kv_zero_tails(int, const KvTailHost*, int, void* const*, hipStream_t);                                               \
+  int launch_head_ce(const float*, int, const void*, const float*, const int*, int, long, long, int, int, int, int, float*, int,  \
+                     hipStream_t);                                                                                                \
   }
 SPLIT_LAUNCHERS(s1)
 SPLIT_LAUNCHERS(s0)
@@ -110,4 +112,9 @@ int launch_kv_zero_tail(int B, int key0, int n, int nkt, void* img, hipStream_t 
 }
 int launch_kv_zero_tails(int n, const KvTailHost* t, int nimg, void* const* imgs, hipStream_t st) {
   return PICK(launch_kv_zero_tails(n, t, nimg, imgs, st));
+}
+// (loss.hip) returns 1 — nothing launched — under the three-bf16-plane scheme: the caller takes the from-memory path
+int launch_head_ce(const float* A, int lda, const void* Wblk, const float* bias, const int* tgt, int tgt_stride, long tgt_shift, long tgt_rows,
+                   int M, int nsm, int bps, int valid, float* LT, int sm0, hipStream_t st) {
+  return PICK(launch_head_ce(A, lda, Wblk, bias, tgt, tgt_stride, tgt_shift, tgt_rows, M, nsm, bps, valid, LT, sm0, st));
 }

@@ -56,6 +56,10 @@ int launch_row_copy(const float*, int, float*, int, const int*, int, int, int, h
 int launch_gemm256_rows(const float*, int, const void*, int, int, const float*, float*, int, const int*, int, hipStream_t);
 int launch_attention(int, const float*, int, long, const float*, const float*, int, long, float*, int, long, const int*,
                      const unsigned char*, int, int, int, int, hipStream_t);
+int launch_head_ce(const float*, int, const void*, const float*, const int*, int, long, long, int, int, int, int, float*, int, hipStream_t);
+int launch_row_lse(const float*, long, int, int, int, const int*, int, long, long, long, int, float*, int, hipStream_t);
+int launch_loss_reduce(const float*, const float*, const unsigned char*, const float*, const float*, float*, double*, double*, int, int, int,
+                       int, int, int, int, int, hipStream_t);
 struct EmbedTables { const float *act, *rtg_g, *rtg_v, *rtg_r, *rtg_bias, *tstep, *agent, *ln_g, *ln_b; int rtg_linear, flags; };
 int launch_assemble_tokens(int, int, int, int, const float*, const float*, const float*, const int*, const int*, const int*,
                            EmbedTables, float*, float*, int, int, unsigned char*, hipStream_t);
@@ -111,6 +115,9 @@ struct ctrlsim_model {
   std::vector<DecLayer> dec;
   Mlp head_action, head_rtg, head_fut;
   bool has_fut = false;
+  // cross-entropy images of the action / return heads' last Linear (pack.py:head_ce_image; two-fp16-plane scheme) and their padded biases
+  const void *ce_act = nullptr, *ce_rtg = nullptr;
+  const float *ce_act_b = nullptr, *ce_rtg_b = nullptr;
   hipEvent_t ev_tail = nullptr;           // orders the few-row tail of a first pass behind its full-row part when the tail runs on another stream
   int zero_rtg[3];
 };
@@ -221,6 +228,10 @@ extern "C" int ctrlsim_model_create(const ctrlsim_dims* dims, const float* dev_w
     m->head_fut = mlp("decoder.predict_future_states");                 // auxiliary head, only read by ctrlsim_forward_all
     m->has_fut = true;
   }
+  m->ce_act = PX("decoder.predict_action.mlp.3.weight#ce#pl1");
+  m->ce_act_b = static_cast<const float*>(PX("decoder.predict_action.mlp.3.bias#ce"));
+  m->ce_rtg = PX("decoder.predict_rtg.mlp.3.weight#ce#pl1");
+  m->ce_rtg_b = static_cast<const float*>(PX("decoder.predict_rtg.mlp.3.bias#ce"));
   m->zero_rtg[0] = 0; m->zero_rtg[1] = 35; m->zero_rtg[2] = 35;
   if (!ok) { delete m; return CTRLSIM_EINVAL; }
   if (hipEventCreateWithFlags(&m->ev_tail, hipEventDisableTiming) != hipSuccess) { delete m; return CTRLSIM_ELAUNCH; }
@@ -771,9 +782,47 @@ namespace {
 // CtRL-Sim: predict_rtg on the state tokens of the current step; IL: predict_action on the same rows; Trajeglish:
 // predict_action on the action tokens (decoder.py:55-77).
 struct AllOut { float *act, *rtg, *fut; };       // ctrlsim_forward_all: heads on every token, rows (b, tt, a)
+// ctrlsim_forward_loss: the same heads reduced to the sums and counts of CtRLSim.compute_loss.  Everything behind the forward's own
+// workspace: LT [rows][4][2] (log-sum-exp, target logit) per softmax, fut [rows][2T], a chunk of logits rows (from-memory path only)
+struct LossReq {
+  const unsigned char* moving; ctrlsim_loss_cfg cfg; double *sums, *per_ctx; float* row_nll;
+  float *LT, *fut, *chunk; double* per_ctx_ws; int chunk_rows;
+};
+struct LossWs { size_t LT, fut, chunk, per_ctx, bytes; int chunk_rows; };
+LossWs loss_carve(const ctrlsim_dims& d, size_t base, int B, int Tq) {
+  LossWs l;
+  size_t off = (base + 255) & ~size_t(255);
+  auto take = [&](size_t n) { const size_t o = off; off += (n + 255) & ~size_t(255); return o; };
+  const size_t rows = (size_t)B * Tq * d.A;
+  const int wide = d.V > d.R * d.C ? d.V : d.R * d.C;
+  l.chunk_rows = rows < 8192 ? (int)rows : 8192;
+  l.LT = take(rows * 8 * sizeof(float));
+  l.fut = take(rows * 2 * d.T * sizeof(float));
+  l.per_ctx = take((size_t)B * 10 * sizeof(double));
+  l.chunk = take((size_t)l.chunk_rows * wide * sizeof(float));
+  l.bytes = off;
+  return l;
+}
+// One head's (log-sum-exp, target logit) pairs for `rows` rows h_in (leading dimension 3 * DM): Linear + LayerNorm + ReLU as mlp_tail, then the
+// last Linear with the cross-entropy epilogue (two-plane scheme, image present, cfg.fused) or, a chunk of rows at a time, the generic Linear
+// into memory + the row kernel.  nsm softmaxes of n classes; targets tgt[(row + shift) * nsm + s].
+int head_ce(const Mlp& h, const void* ce_blk, const float* ce_bias, const float* h_in, int rows, float* hid, int n, int nsm, const int* tgt,
+            long shift, const LossReq& lq, int sm0, hipStream_t st) {
+  CHK(gemm_ln(h.l0, h.ln, h_in, 3 * DM, nullptr, 0, hid, DM, hid, rows, DM, 1, st));
+  if (lq.cfg.fused && ce_blk && ce_bias && ctrlsim_option(OPT_SPLIT) && ctrlsim_option(OPT_GEMM_IMPL) == 1) {
+    const int r = launch_head_ce(hid, DM, ce_blk, ce_bias, tgt, nsm, shift, rows, rows, nsm, (n + 31) / 32, n, lq.LT, sm0, st);
+    if (r != 1) return r;
+  }
+  for (int r0 = 0; r0 < rows; r0 += lq.chunk_rows) {
+    const int nr = rows - r0 < lq.chunk_rows ? rows - r0 : lq.chunk_rows;
+    CHK(gemm(h.l3, hid + (size_t)r0 * DM, DM, nullptr, 0, lq.chunk, n * nsm, nr, n * nsm, DM, 0, st));
+    CHK(launch_row_lse(lq.chunk, n * nsm, n, nsm, nsm, tgt, nsm, shift, rows, r0, nr, lq.LT, sm0, st));
+  }
+  return 0;
+}
 int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, const ctrlsim_ctx* ctx, int Tq, void* workspace,
                  float* logits, float* dbg_seg_emb, hipStream_t st, const AllOut* all = nullptr, hipStream_t st_tail = nullptr,
-                 bool split_tail = false) {
+                 bool split_tail = false, const LossReq* loss = nullptr) {
   const ctrlsim_dims& d = m->d;
   // d.variant: token layout / heads (tok_variant: 4 = CtRL-Sim tokens) and, one to one, the attention mask mode 1 + d.variant
   const int variant = tok_variant(d.variant), amode = 1 + d.variant, qoff = variant == 2 ? 2 : 0;
@@ -844,6 +893,17 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
     // type is a strided view of X (leading dimension 3*DM).  Action head: the rtg token (CtRL-Sim), the state token (IL, and DT,
     // whose token order is rtg, state, action), the action token (Trajeglish); rtg head: state tokens; future states: action tokens.
     const int rows = rL / 3, k_act = variant == 0 ? 1 : variant == 2 ? 2 : 0;
+    if (loss) {
+      // Trajeglish (models/ctrl_sim.py:50-67): the logits of step tt against the action of step tt + 1 — the target d.A rows further on
+      const ctrlsim_ctx* c = bt.c[0].ctx;
+      CHK(head_ce(m->head_action, m->ce_act, m->ce_act_b, w.X + k_act * DM, rows, w.att, d.V, 1, c->act_tok, variant == 2 ? d.A : 0, *loss, 0, st));
+      if (variant == 0)
+        CHK(head_ce(m->head_rtg, m->ce_rtg, m->ce_rtg_b, w.X, rows, w.att, d.R, d.C, c->rtg_bin, 0, *loss, 1, st));
+      if (m->has_fut) CHK(mlp_tail(m->head_fut, w.X + 2 * DM, rows, w.att, loss->fut, 2 * d.T, st, 3 * DM));
+      return launch_loss_reduce(loss->LT, c->exist, loss->moving, c->st12, m->has_fut ? loss->fut : nullptr, loss->row_nll,
+                                loss->per_ctx ? loss->per_ctx : loss->per_ctx_ws, loss->sums, bt.c[0].B, Tq, d.A, d.T, variant == 0,
+                                variant == 2, loss->cfg.supervise_moving, loss->cfg.local_frame_predictions, st);
+    }
     CHK(mlp_tail(m->head_action, w.X + k_act * DM, rows, w.att, all->act, d.V, st, 3 * DM));
     if (all->rtg) CHK(mlp_tail(m->head_rtg, w.X, rows, w.att, all->rtg, d.R * d.C, st, 3 * DM));
     if (all->fut) CHK(mlp_tail(m->head_fut, w.X + 2 * DM, rows, w.att, all->fut, 2 * d.T, st, 3 * DM));
@@ -892,6 +952,59 @@ extern "C" int ctrlsim_forward_all(const ctrlsim_model* m, int B, int Tq, const 
   const int A = m->d.A;
   const AllOut all{action_preds, rtg_preds, state_preds};
   return forward_full(m, 1, &B, &A, c, Tq, workspace, nullptr, nullptr, st, &all);
+}
+
+// Open-loop evaluation: CtRLSim.compute_loss of the teacher-forced forward (models/ctrl_sim.py:48-189,217-228) as sums and counts; no logits
+// tensor exists on the fused path (csrc/loss.hip).  Workspace: the forward's own, then loss_carve's buffers.
+extern "C" int64_t ctrlsim_forward_loss_workspace_bytes(const ctrlsim_dims* d, int B, int Tq) {
+  const int64_t base = ctrlsim_forward_workspace_bytes(d, B, Tq);
+  if (base < 0) return base;
+  return (int64_t)loss_carve(*d, (size_t)base, B, Tq).bytes;
+}
+extern "C" int ctrlsim_forward_loss(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                    const ctrlsim_loss_cfg* cfg, void* workspace, double* sums, double* per_ctx, float* row_nll,
+                                    hipStream_t st) {
+  if (!m || !c || !cfg || !workspace || !sums || B < 1 || Tq < 1 || Tq > m->d.T) return CTRLSIM_EINVAL;
+  if (tok_variant(m->d.variant) == 0 && m->d.C != 3) return CTRLSIM_EINVAL;      // goal / vehicle / road-edge returns: three softmaxes
+  const int A = m->d.A;
+  const int64_t base = ctrlsim_forward_workspace_bytes(&m->d, B, Tq);
+  if (base < 0) return (int)base;
+  const LossWs l = loss_carve(m->d, (size_t)base, B, Tq);
+  char* ws = static_cast<char*>(workspace);
+  const LossReq lq{moving, *cfg, sums, per_ctx, row_nll, reinterpret_cast<float*>(ws + l.LT), reinterpret_cast<float*>(ws + l.fut),
+                   reinterpret_cast<float*>(ws + l.chunk), reinterpret_cast<double*>(ws + l.per_ctx), l.chunk_rows};
+  const AllOut all{nullptr, nullptr, nullptr};
+  return forward_full(m, 1, &B, &A, c, Tq, workspace, nullptr, nullptr, st, &all, nullptr, false, &lq);
+}
+// The same sums and counts from logits in memory — compute_loss(data, preds) on the tensors of ctrlsim_forward_all (token-row order
+// [B,Tq,A,.]; rtg_preds / state_preds NULL for a model without the head).  scratch: B * Tq * A * 8 floats + B * 10 doubles.
+extern "C" int64_t ctrlsim_loss_scratch_bytes(int B, int Tq, int A) {
+  if (B < 1 || Tq < 1 || A < 1) return CTRLSIM_EINVAL;
+  return (int64_t)(((size_t)B * Tq * A * 8 * sizeof(float) + 255) & ~size_t(255)) + (int64_t)B * 10 * sizeof(double);
+}
+extern "C" int ctrlsim_loss_from_preds(const ctrlsim_dims* d, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                       const ctrlsim_loss_cfg* cfg, const float* action_preds, const float* rtg_preds,
+                                       const float* state_preds, void* scratch, double* sums, double* per_ctx, float* row_nll,
+                                       hipStream_t st) {
+  if (!d || !c || !cfg || !action_preds || !scratch || !sums || B < 1 || Tq < 1 || Tq > d->T) return CTRLSIM_EINVAL;
+  const int variant = tok_variant(d->variant);
+  if (rtg_preds && (variant != 0 || d->C != 3)) return CTRLSIM_EINVAL;
+  const int rows = B * Tq * d->A;
+  float* LT = static_cast<float*>(scratch);
+  double* pc = reinterpret_cast<double*>(static_cast<char*>(scratch) + (((size_t)rows * 8 * sizeof(float) + 255) & ~size_t(255)));
+  CHK(launch_row_lse(action_preds, d->V, d->V, 1, 1, c->act_tok, 1, variant == 2 ? d->A : 0, rows, 0, rows, LT, 0, st));
+  if (rtg_preds) CHK(launch_row_lse(rtg_preds, (long)d->R * d->C, d->R, d->C, d->C, c->rtg_bin, d->C, 0, rows, 0, rows, LT, 1, st));
+  return launch_loss_reduce(LT, c->exist, moving, c->st12, state_preds, row_nll, per_ctx ? per_ctx : pc, sums, B, Tq, d->A, d->T,
+                            rtg_preds != nullptr, variant == 2, cfg->supervise_moving, cfg->local_frame_predictions, st);
+}
+
+// Component-level entry (tests): the cross-entropy Linear alone on M hidden rows H [M,256]; returns 1 — nothing launched — where the kernel does
+// not apply (three-bf16-plane scheme selected).
+extern "C" int ctrlsim_head_ce(const float* H, int ldh, const void* Wce, const float* bias_ce, const int* tgt, int M, int n, int nsm,
+                               float* lt, hipStream_t st) {
+  if (!H || !Wce || !bias_ce || !tgt || !lt || M < 1 || n < 1 || nsm < 1 || nsm > 4) return CTRLSIM_EINVAL;
+  if (!ctrlsim_option(OPT_SPLIT)) return 1;
+  return launch_head_ce(H, ldh, Wce, bias_ce, tgt, nsm, 0, M, M, nsm, (n + 31) / 32, n, lt, 0, st);
 }
 
 // Component-level entry (tests, micro-benchmarks): the folded point MLP + seed-attention pooling of B*P polylines,

@@ -46,3 +46,14 @@ def allreduce_metrics(acc, device="cpu"):
     vec = torch.from_numpy(acc.pack()).to(device)
     dist.all_reduce(vec, op=dist.ReduceOp.SUM)
     return acc.unpack(vec.cpu().numpy())
+
+
+def allreduce_loss_sums(sums: torch.Tensor):
+    """In-place SUM over all ranks of the ten doubles of the open-loop loss ([5, 2] float64: (sum, count) of loss_actions, loss_rtg_goal,
+    loss_rtg_veh, loss_rtg_road, loss_state; include/ctrlsim.h: ctrlsim_forward_loss) — sums and counts combine across shards, means do
+    not.  No-op without an initialised process group."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return sums
+    dist.all_reduce(sums, op=dist.ReduceOp.SUM)
+    return sums

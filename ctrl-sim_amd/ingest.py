@@ -265,3 +265,98 @@ def load_preprocessed(src, w):
     allr = np.concatenate([x[:, :, None] * ex for x in (goal, head, speed, vv, ve)], -1)
     rtgs = np.cumsum(allr[:, ::-1], axis=1)[:, ::-1]
     return {"rtgs": rtgs, "road_points": src["road_points"], "road_types": src["road_types"]}
+
+
+# ---- training-mode windows (the validation loader's half of RLWaymoDatasetCtRLSim.get_data, dataset_ctrl_sim.py:99-160)
+def _se2(coords, translation, yaw):
+    """utils/geometry.py apply_se2_transform: (coords - translation) rotated counter-clockwise by yaw, as np.dot(R, x.T).T."""
+    c = coords - translation
+    R = np.array([[np.cos(yaw), -np.sin(yaw)], [np.sin(yaw), np.cos(yaw)]])
+    return np.dot(R, c.reshape(-1, 2).T).T.reshape(c.shape)
+
+
+def _angle_sub(current, target):
+    d = (target - current) % (2 * np.pi)
+    return np.where(d > np.pi, -(2 * np.pi - d), d)
+
+
+def _window_tables(pre, cfg):
+    w = cfg.dataset.waymo
+    rt = np.asarray(load_preprocessed(pre, w)["rtgs"], np.float64)
+    rt = np.concatenate([rt[:, :, :1], rt[:, :, 3:5]], axis=2)                      # goal position, vehicle, road edge (:99)
+    for c, (lo, hi) in enumerate(((w.min_rtg_pos, w.max_rtg_pos), (w.min_rtg_veh, w.max_rtg_veh), (w.min_rtg_road, w.max_rtg_road))):
+        rt[:, :, c] = (np.clip(rt[:, :, c], lo, hi) - lo) / (hi - lo)
+    ag_data, goals = np.asarray(pre["ag_data"], np.float64), np.asarray(pre["ag_goals"], np.float64)
+    moving_ids = np.where(np.linalg.norm(ag_data[:, 0, :2] - goals[:, 0, :2], axis=1) > w.moving_threshold)[0]
+    max_t = max(0, int(np.max(np.asarray(pre["last_exist_timesteps"])[moving_ids])) - (w.train_context_length - 1))
+    return rt, ag_data, goals, moving_ids, max_t
+
+
+def window_choices(pre, cfg, seed):
+    """A seeded default for the reference's two random draws (dataset_ctrl_sim.py:116 and :30-35): -> (origin_t, origin_agent), the
+    window's first step and an index into pre['filtered_ag_ids'] of a moving agent that exists at that step."""
+    rs = np.random.RandomState(seed)
+    _, ag_data, _, moving_ids, max_t = _window_tables(pre, cfg)
+    fil = list(pre["filtered_ag_ids"])
+    origin_t = int(rs.randint(0, max_t + 1))
+    valid = np.where((ag_data[fil, origin_t, -1] == 1) * np.isin(fil, moving_ids))[0]
+    return origin_t, int(valid[rs.choice(len(valid))])
+
+
+def training_window(pre, cfg, origin_t, origin_agent):
+    """One training-mode sample of RLWaymoDatasetCtRLSim.get_data (dataset_ctrl_sim.py:99-160) from the dictionary preprocess_scene
+    produces, with the reference's two random draws as ARGUMENTS (origin_t: first step of the window, :116; origin_agent: index into
+    pre['filtered_ag_ids'] of the agent the frame is centred on, a moving agent that exists at the window's first step, :30-35):
+    return normalisation, moving ids, the window cut, select_relevant_agents at window index 0 (dataset.py:278-319; agents in ascending
+    id order — the validation / test splits; the train split's extra shuffle is not reproduced), discretisation, normalize_scene
+    (dataset.py:390-428).  -> the window in the reference layout without the batch axis (evaluators/open_loop_evaluator.py), float64 /
+    int64 like the reference's NumPy path.  A Decision-Transformer cfg keeps the returns continuous."""
+    from .discretize import discretize_actions
+    w = cfg.dataset.waymo
+    T, A = int(w.train_context_length), int(w.max_num_agents)
+    rt, ag_data, goals_all, moving_ids, max_t = _window_tables(pre, cfg)
+    fil = list(pre["filtered_ag_ids"])
+    if not 0 <= origin_t <= max_t:
+        raise ValueError(f"origin_t {origin_t} outside [0, {max_t}]")
+    st = ag_data[fil, origin_t:origin_t + T]
+    types = np.asarray(pre["ag_types"], np.float64)[fil]
+    act = np.asarray(pre["ag_actions"], np.float64)[fil, origin_t:origin_t + T]
+    rt = rt[fil, origin_t:origin_t + T]
+    goals = goals_all[fil, 0]
+    moving = np.isin(fil, moving_ids)
+    if not (st[origin_agent, 0, -1] == 1 and moving[origin_agent]):
+        raise ValueError("the origin agent must move and exist at the window's first step")
+    dist = np.linalg.norm(st[origin_agent, 0, :2].reshape(1, -1) - st[:, 0, :2], axis=-1)
+    ids = np.intersect1d(np.argsort(dist)[:A], np.where(dist < w.agent_dist_threshold)[0])
+    n = len(ids)
+    pad = lambda x, fill: np.concatenate([x[ids], np.full((A - n,) + x.shape[1:], fill, np.float64)])
+    st, types, act, rt, goals = pad(st, 0.0), pad(types, -1.0), pad(act, 0.0), pad(rt, 0.0), pad(goals, 0.0)
+    mv = np.zeros(A)
+    mv[:n] = moving[ids]
+    slot = int(np.where(ids == origin_agent)[0][0])
+    tok = discretize_actions(act, w)
+    if not bool(cfg.model.get("decision_transformer", False)):
+        rt = np.round(rt * (w.rtg_discretization - 1))
+    # normalize_scene: the origin agent at the origin, heading up
+    yaw = st[slot, 0, 4]
+    rot = (np.pi / 2) + np.sign(-yaw) * np.abs(yaw)
+    tr = st[slot, 0, :2].copy()
+    st[:, :, :2] = _se2(st[:, :, :2], tr[None, None, :], rot)
+    st[:, :, 2:4] = _se2(st[:, :, 2:4], np.zeros((1, 1, 2)), rot)
+    st[:, :, 4] = _angle_sub(st[:, :, 4], -rot)
+    goals[:, :2] = _se2(goals[:, :2], tr[None, :], rot)
+    goals[:, 2:4] = _se2(goals[:, 2:4], np.zeros((1, 2)), rot)
+    goals[:, 4] = _angle_sub(goals[:, 4], -rot)
+    rp = np.array(pre["road_points"], np.float64)
+    rty = np.asarray(pre["road_types"], np.float64)
+    rp[:, :, :2] = _se2(rp[:, :, :2], tr[None, None, :], rot)
+    P = int(w.max_num_road_polylines)
+    if len(rp) > P:
+        keep = np.argsort((np.linalg.norm(rp[:, :, :2], axis=-1) * rp[:, :, -1]).max(1))[:P]
+        frp, frt = rp[keep], rty[keep]
+    else:
+        frp = np.zeros((P,) + rp.shape[1:]); frp[:len(rp)] = rp
+        frt = -np.ones((P, rty.shape[1])); frt[:len(rp)] = rty
+    timesteps = np.repeat((np.arange(T) + origin_t)[None, :, None], A, 0)
+    return dict(agent_states=st, agent_types=types, goals=goals, actions=tok, rtgs=rt, timesteps=timesteps, moving_agent_mask=mv,
+                road_points=frp, road_types=frt)

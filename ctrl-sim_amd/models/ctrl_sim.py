@@ -5,7 +5,8 @@ The reference class is a LightningModule whose only rollout-relevant members are
 Lightning checkpoint whose `hyper_parameters` carry the cfg (eval_sim.py:52, policies/policy.py:28-29).
 Here the object owns the packed device weights (`HipModel`); the HIP forward is driven by the policy/engine through
 the C ABI; `forward` on reference-layout tensors is the reference's return contract ([B,A,T,.] logits of every head,
-teacher-forced), or — with `token_index` — the two-pass logits of one timestep, the slice AutoregressivePolicy reads."""
+teacher-forced), or — with `token_index` — the two-pass logits of one timestep, the slice AutoregressivePolicy reads.
+`compute_loss` / `validation_step` (models/ctrl_sim.py:48-189,217-228) score logged windows: ctrlsim_forward_loss, no logits tensor."""
 from __future__ import annotations
 
 import numpy as np
@@ -107,3 +108,85 @@ class CtRLSim:
                                                 hist.data_ptr(), ws.data_ptr(), act.data_ptr(), 0, st))
         torch.cuda.synchronize()
         return {"rtg_preds": rtg, "action_preds": act}
+
+    # ---- open-loop evaluation (reference: models/ctrl_sim.py:48-189, 217-228)
+    LOSS_KEYS = ("loss_actions", "loss_rtg_goal", "loss_rtg_veh", "loss_rtg_road", "loss_state")
+    VAL_NAMES = {"loss_actions": "val_loss", "loss_rtg_goal": "val_rtg_goal_loss", "loss_rtg_veh": "val_rtg_veh_loss",
+                 "loss_rtg_road": "val_rtg_road_loss", "loss_state": "val_state_loss"}
+
+    def loss_keys(self):
+        """The terms this model's heads provide, in the order of the packed sums."""
+        m = self.cfg.model
+        keys = ["loss_actions"]
+        if self.dims.VARIANT == 0 and bool(m.get("predict_rtg", True)):
+            keys += ["loss_rtg_goal", "loss_rtg_veh", "loss_rtg_road"]
+        if bool(m.get("predict_future_states", True)) and "decoder.predict_future_states.mlp.0.weight" in self.weights:
+            keys.append("loss_state")
+        return keys
+
+    def loss_cfg(self, fused=True):
+        from .. import _lib
+        m = self.cfg.model
+        return _lib.LossCfg(int(bool(m.get("supervise_moving", True))), int(bool(m.get("local_frame_predictions", False))), int(bool(fused)), 0)
+
+    def losses_from_sums(self, sums):
+        """[5,2] (sum, count) per term -> the reference's loss dictionary: sum / count, the actions times loss_action_coef, the state
+        term over 100 * 2 * count (models/ctrl_sim.py:84,146).  A term whose count is 0 is NaN, as 0 / 0 is in the reference."""
+        sums = np.asarray(sums, np.float64).reshape(5, 2)
+        coef = float(self.cfg.model.get("loss_action_coef", 1.0))
+        out = {}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for k in self.loss_keys():
+                i = self.LOSS_KEYS.index(k)
+                s, n = sums[i]
+                out[k] = float(np.float64(coef * s if i == 0 else s) / np.float64(200.0 * n if i == 4 else n))
+        return out
+
+    def loss_sums(self, data, preds=None, fused=True, per_ctx=False, row_nll=False):
+        """One teacher-forced forward over the reference-layout windows `data` -> device tensors (sums [5,2] float64, per_ctx [B,5,2] or
+        None, row_nll [B,T,A,4] or None).  preds (the dictionary `forward` returns): the reduction over those logits instead."""
+        import ctypes as C
+        import torch
+        from .. import _lib
+        from ..engine import ctx_from_reference_layout
+        d, dev = self.dims, self.device
+        arrs = self._arrays(data)
+        B = arrs["agent_states"].shape[0]
+        ag = data["agent"]
+        mv = ag.get("moving_agent_mask") if isinstance(ag, dict) else getattr(ag, "moving_agent_mask", None)
+        moving = None
+        if mv is not None:
+            mv = np.asarray(mv.cpu() if hasattr(mv, "cpu") else mv)
+            moving = torch.from_numpy(np.ascontiguousarray(mv != 0).astype(np.uint8)).to(dev)
+        lib, st = _lib.lib(), _lib.stream_ptr()
+        cb = ctx_from_reference_layout(d, arrs, d.T, dev)
+        cb.slot_gid.copy_(torch.arange(d.A, dtype=torch.int32, device=dev).expand(B, d.A))
+        sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
+        pc = torch.zeros(B, 5, 2, dtype=torch.float64, device=dev) if per_ctx else None
+        rn = torch.zeros(B, d.T, d.A, 4, device=dev) if row_nll else None
+        cfg = self.loss_cfg(fused)
+        if preds is None:
+            n = lib.ctrlsim_forward_loss_workspace_bytes(C.byref(self.hip.cdims), B, d.T)
+            if n < 0:
+                raise RuntimeError(f"loss workspace query failed: {n}")
+            ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
+            _lib.check(lib.ctrlsim_forward_loss(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), ws.data_ptr(),
+                                                sums.data_ptr(), _lib.ptr(pc), _lib.ptr(rn), st), "forward_loss")
+        else:
+            rows = lambda k: (preds[k].to(dev).float().permute(0, 2, 1, 3).contiguous() if preds.get(k) is not None else None)
+            act, rtg, fut = rows("action_preds"), rows("rtg_preds"), rows("state_preds")
+            scratch = torch.empty(int(lib.ctrlsim_loss_scratch_bytes(B, d.T, d.A)), dtype=torch.uint8, device=dev)
+            _lib.check(lib.ctrlsim_loss_from_preds(C.byref(self.hip.cdims), B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg),
+                                                   _lib.ptr(act), _lib.ptr(rtg), _lib.ptr(fut), scratch.data_ptr(), sums.data_ptr(),
+                                                   _lib.ptr(pc), _lib.ptr(rn), st), "loss_from_preds")
+        return sums, pc, rn                 # enqueued on the current stream; reading the tensors waits for it
+
+    def compute_loss(self, data, preds=None):
+        """The reference's loss dictionary (models/ctrl_sim.py:48-189) of the windows in `data`.  preds None: the fused forward + loss
+        (no logits); preds = model(data): the reduction over those tensors, the reference's call shape."""
+        sums, _, _ = self.loss_sums(data, preds)
+        return self.losses_from_sums(sums.cpu().numpy())
+
+    def validation_step(self, data, batch_idx=0):
+        """The values the reference logs per validation batch (models/ctrl_sim.py:217-228), under its names."""
+        return {self.VAL_NAMES[k]: v for k, v in self.compute_loss(data).items()}

@@ -145,6 +145,27 @@ def row_blocks(W: np.ndarray, scheme=None) -> np.ndarray:
     return np.ascontiguousarray(p1.transpose(1, 0, 3, 4, 2, 5))           # [cb][p][ks][half][col][e]
 
 
+CE_MAX_BLOCKS = 40        # csrc/loss.hip: CE_MAXB
+
+
+def head_ce_image(W: np.ndarray, b: np.ndarray, nsm: int = 1, scheme=1):
+    """Operand image of an MLP head's last Linear for the cross-entropy kernel (csrc/loss.hip: head_ce_kernel): -> (blocks, bias).
+    W [n * nsm, K] holds nsm interleaved softmaxes of n classes each, row e * nsm + s = class e of softmax s (the action head: nsm = 1;
+    the return head: bin-major, component-minor, policies/policy.py:108-127).  The image is SOFTMAX-major, every softmax padded with zero
+    rows to bps = ceil(n / 32) blocks of 32 columns, so that a column block belongs to one softmax: row_blocks of [nsm][32 bps][K];
+    bias likewise, float32 [nsm * 32 * bps].  The kernel masks the pad columns by index."""
+    W = np.asarray(W, np.float32)
+    b = np.asarray(b, np.float32)
+    n = W.shape[0] // nsm
+    assert W.shape[0] == n * nsm and b.shape == (W.shape[0],)
+    bps = (n + 31) // 32
+    Wp = np.zeros((nsm, bps * 32, W.shape[1]), np.float32)
+    bp = np.zeros((nsm, bps * 32), np.float32)
+    Wp[:, :n] = W.reshape(n, nsm, -1).transpose(1, 0, 2)
+    bp[:, :n] = b.reshape(n, nsm).T
+    return row_blocks(Wp.reshape(nsm * bps * 32, -1), scheme), bp.reshape(-1)
+
+
 def ffn_planes(W1: np.ndarray, W2: np.ndarray, scheme=None):
     """Operand images of the fused FFN kernel (csrc/ffn_fused.hip), one 48 KB block per 32 hidden units hb:
       W1p[hb][p 3][ks K/16][half 2][row 32][8]   = plane_p(W1)[32 hb + row, 16 ks + 8 half + e]
@@ -255,6 +276,17 @@ def pack(dims: Dims, w: dict):
                 allw[k + "#blk" + PLANES_SUFFIX[1]] = row_blocks(np.asarray(w[k], np.float32), 1).reshape(-1).view(np.float32)
             except FloatingPointError:
                 pass                                               # out of the fp16 range: that model runs with bf16 planes
+    # cross-entropy images of the action / return heads' last Linear (two-fp16-plane scheme: csrc/loss.hip, the open-loop loss)
+    for k, nsm in (("decoder.predict_action.mlp.3", 1), ("decoder.predict_rtg.mlp.3", dims.C)):
+        if k + ".weight" in w and np.asarray(w[k + ".weight"]).shape[1] == 256:
+            n = np.asarray(w[k + ".weight"]).shape[0] // nsm
+            if 2 <= nsm * ((n + 31) // 32) <= CE_MAX_BLOCKS:
+                try:
+                    blk, bias = head_ce_image(w[k + ".weight"], w[k + ".bias"], nsm, 1)
+                except FloatingPointError:
+                    continue
+                allw[k + ".weight#ce" + PLANES_SUFFIX[1]] = blk.reshape(-1).view(np.float32)
+                allw[k + ".bias#ce"] = bias
     names, offsets, chunks = [], [], []
     off = 0
     for k, v in allw.items():

@@ -208,6 +208,38 @@ int ctrlsim_map_pool(const ctrlsim_model* m, int B, const float* road_pts, float
  * Training-time / debugging contract — the rollout reads one timestep and uses the pass1 / pass2 entry points. */
 int ctrlsim_forward_all(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, void* workspace, float* action_preds,
                         float* rtg_preds, float* state_preds, hipStream_t stream);
+/* Open-loop evaluation — replaces CtRLSim.compute_loss / validation_step (models/ctrl_sim.py:48-189,217-228) behind one teacher-forced
+ * forward over B logged windows: cross-entropy of the action head and of the three return heads against the tokens the context itself
+ * holds (ctx.act_tok, ctx.rtg_bin: teacher forcing scores its own inputs), the future-state MSE, masked by existence and (moving
+ * [B,A] uint8, NULL = every agent) supervise_moving.  sums [5][2] += (sum, count) of loss_actions, loss_rtg_goal, loss_rtg_veh,
+ * loss_rtg_road, loss_state over the batch — means of shards do not combine, sums and counts do: loss = sum / count
+ * (x loss_action_coef for the actions), loss_state = sum / (100 * 2 * count) (:146); a term whose count is 0 is 0 / 0 = NaN in the
+ * reference and here.  per_ctx [B,5,2] (nullable) the same per context; row_nll [B,Tq,A,4] (nullable) lse - logit[target] per row and
+ * softmax (actions, goal, veh, road; unmasked).  By dims.variant: 0 / 4 all five terms (state only with the predict_future_states head);
+ * 1 (IL) / 3 (DT) the action term, from the state tokens (decoder.py:55-64); 2 (Trajeglish) the action term with the reference's shift:
+ * logits of step i against the action of step i + 1 under the existence of step i + 1 (:50-67).  local_frame_predictions: state targets
+ * translated to the agent's position at step i and rotated by minus its yaw (:151-187; as there, without the moving mask).
+ * fused != 0: the heads' last Linear runs with a cross-entropy epilogue (csrc/loss.hip) and no logits are written — two-fp16-plane
+ * scheme; under the three-bf16-plane scheme, or with fused == 0, the generic Linear writes a chunk of rows at a time and a row kernel
+ * reduces it (same results up to summation order).  The batch totals are reduced by fixed trees: identical bits from run to run.
+ * Workspace: ctrlsim_forward_loss_workspace_bytes (the forward's own + 8 floats per row + the state predictions + a logits chunk). */
+typedef struct ctrlsim_loss_cfg {
+  int supervise_moving;          /* cfg.model.supervise_moving */
+  int local_frame_predictions;   /* cfg.model.local_frame_predictions */
+  int fused;                     /* 1 = cross-entropy epilogue, 0 = logits through memory */
+  int pad_;
+} ctrlsim_loss_cfg;
+int64_t ctrlsim_forward_loss_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq);
+int ctrlsim_forward_loss(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                         const ctrlsim_loss_cfg* cfg, void* workspace, double* sums, double* per_ctx, float* row_nll,
+                         hipStream_t stream);
+/* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
+ * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
+ * scratch: ctrlsim_loss_scratch_bytes. */
+int64_t ctrlsim_loss_scratch_bytes(int B, int Tq, int A);
+int ctrlsim_loss_from_preds(const ctrlsim_dims* dims, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                            const ctrlsim_loss_cfg* cfg, const float* action_preds, const float* rtg_preds, const float* state_preds,
+                            void* scratch, double* sums, double* per_ctx, float* row_nll, hipStream_t stream);
 /* pass 2 (same workspace, after ctrlsim_sample_rtg wrote hist_rtg[...,t,:]): act_logits [B,A,V].
  * cached = 1 pairs with ctrlsim_dt_forward_pass1_cached (workspace sized with Tq = T, ctx = last min(Tq,2) window rows). */
 int ctrlsim_dt_forward_pass2(const ctrlsim_model* m, int B, int Tq, int t, int N, int Tmax, const ctrlsim_ctx* ctx,
@@ -311,6 +343,12 @@ int ctrlsim_gemm_nt_kv(const float* A, int lda, const void* W3, int n_total, int
  * plain Linear (N a multiple of 32 in [64, 768]; kv_L / kv_nkt / kv_col0 ignored), all N columns as fp32 rows of C. */
 int ctrlsim_gemm_kv_blocks(const float* A, int lda, const void* Wblk, const float* bias, float* C, int ldc, int M, int N,
                            void* kv_img, int kv_L, int kv_nkt, int kv_col0, hipStream_t stream);
+/* The last Linear of an MLP head with a cross-entropy epilogue (csrc/loss.hip; two-fp16-plane scheme, returns 1 — nothing launched —
+ * otherwise): H [M,256] hidden rows, Wce / bias_ce = ctrlsim_amd/pack.py:head_ce_image of the Linear (nsm interleaved softmaxes of n classes,
+ * nsm <= 4), tgt [M,nsm] target classes; lt [M,4,2] receives (log-sum-exp, target logit) of softmax s at [row, s, :].  Nothing of size
+ * n is written.  F.cross_entropy(reduction='none') of models/ctrl_sim.py:65,82,95-105 is lt[..., 0] - lt[..., 1]. */
+int ctrlsim_head_ce(const float* H, int ldh, const void* Wce, const float* bias_ce, const int* tgt, int M, int n, int nsm, float* lt,
+                    hipStream_t stream);
 /* Post-LN feed-forward block of nn.TransformerEncoderLayer / DecoderLayer as one kernel:
  * Y = LayerNorm(X + W2 relu(W1 X + b1) + b2) * gamma + beta, rows of 256, F hidden units (multiple of 32); W1p / W2p are the
  * operand images of ctrlsim_amd/pack.py:ffn_planes; Y may alias X.  The hidden activation never touches memory. */
