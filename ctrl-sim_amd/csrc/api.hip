@@ -1,61 +1,9 @@
 // extern "C" exports of the C ABI declared in include/ctrlsim.h (thin wrappers over the kernel launchers).
-#include "common.h"
-#include "classes.h"
+#include <vector>
+
+#include "launchers.h"
 #include "../../include/ctrlsim.h"
 
-int launch_gemm_nt(const float*, int, const float*, int, const float*, const float*, int, float*, int, int, int, int, int,
-                   hipStream_t);
-int launch_gemm_nt_bf16x6(const float*, int, const void*, int, int, const float*, const float*, int, float*, int, int, int,
-                          int, int, const float*, const float*, hipStream_t);
-int launch_gemm_nt_bf16x6_kv(const float*, int, const void*, int, int, const float*, const float*, int, float*, int, int, int,
-                             int, int, const float*, const float*, void*, int, int, int, int, int, hipStream_t);
-int launch_gemm256_rows(const float*, int, const void*, int, int, const float*, float*, int, const int*, int, hipStream_t);
-int launch_inproj_rs(const float*, int, const void*, const float*, float*, int, int, int, void*, int, int, const KvClassHost*,
-                     hipStream_t);
-int launch_layernorm256(const float*, int, const float*, int, const float*, const float*, float*, int, int, int,
-                        hipStream_t);
-int launch_attention(int, const float*, int, long, const float*, const float*, int, long, float*, int, long, const int*,
-                     const unsigned char*, int, int, int, int, hipStream_t);
-int launch_kv_split(const float*, const float*, int, long, int, int, int, void*, hipStream_t);
-int launch_kv_split_rows(const float*, const float*, int, long, const int*, int, int, int, void*, hipStream_t);
-int launch_attention_bf16x6_pre(int, const float*, int, long, const void*, int, float*, int, long, const int*,
-                                const unsigned char*, int, int, int, int, int, int, int, const void*, hipStream_t);
-int launch_attn_mask_tables(int, const AttnClassHost*, hipStream_t);
-size_t attn_mask_table_bytes(int, int);
-int launch_ffn_fused_bf16x6(const float*, int, const void*, const float*, const void*, const float*, const float*, const float*,
-                            float*, int, int, int, hipStream_t);
-int launch_ffn_fused_pre(const float*, int, const float*, int, const void*, const float*, const float*, const float*, const void*, const float*,
-                         const void*, const float*, const float*, const float*, float*, int, int, int, hipStream_t);
-int launch_outproj_ln_q(const float*, int, const float*, int, const void*, const float*, const float*, const float*, const void*, const float*,
-                        float*, int, float*, int, int, hipStream_t);
-int launch_sim_init(int, int, int, const float*, const float*, const float*, const unsigned char*, float*, float*,
-                    unsigned char*, int, float*, hipStream_t);
-int launch_sim_set_position(int, int, const float*, float*, hipStream_t);
-int launch_sim_step(int, int, int, const int*, const double*, const double*, const float*, const float*,
-                    const unsigned char*, float*, float*, unsigned char*, double*, int, int, float, int, float*, const float*,
-                    hipStream_t);
-int launch_group_build(int, int, int, int, int, int, double, const float*, const int*, int, unsigned long long*, int*, int*,
-                       unsigned long long*, unsigned long long*, int*, int*, unsigned char*, hipStream_t);
-int launch_ctx_index(int, int, int, const int*, const int*, const unsigned long long*, const int*, const int*, int*, int*,
-                     int*, int*, int*, int*, int*, hipStream_t);
-int launch_groups_changed(int, int, const int*, const int*, const unsigned long long*, const int*, const int*,
-                          const unsigned long long*, int*, hipStream_t);
-struct CtxOut { float *st12, *exist, *goal5; int *act_tok, *rtg_bin, *tstep, *slot_gid; float *road_pts, *road_types; };
-int launch_build_context_classes(int, const int*, const int*, const CtxOut*, int, int, int, int, int, int, int, int, int, int, const int*,
-                                 const int*, const int*, const unsigned long long*, const float*, const int*, const int*,
-                                 const double*, const float*, const float*, const float*, const int*, hipStream_t);
-int launch_build_context(int, int, int, int, int, int, int, int, int, int, int, int, const int*, const int*, const int*,
-                         const unsigned long long*, const float*, const int*, const int*, const double*, const float*,
-                         const float*, const float*, const int*, CtxOut, hipStream_t);
-int launch_sample_rtg(const float*, int, int, const int*, const int*, const int*, const unsigned char*, const double*, const double*,
-                      const float*, uint64_t, const int64_t*, int, int*, int, int, int, hipStream_t);
-int launch_group_size_hist(int, int, const int*, const unsigned long long*, int, const int*, int*, hipStream_t);
-int launch_ctx_index_classes(int, int, int, int, const int*, const unsigned long long*, const int*, const int*, int, const int*, int*,
-                             int*, int*, int*, int*, int*, int*, int*, hipStream_t);
-int launch_sample_action(const float*, int, int, const int*, const int*, const int*, float, double, const float*, uint64_t,
-                         const int64_t*, int, int*, int*, int, int, int, int, hipStream_t);
-
-#include <vector>
 namespace {
 struct ProfRec { hipEvent_t a, b; int cls; double flops, bytes; hipStream_t st; int sub; };
 bool g_prof_on = false;
@@ -347,17 +295,18 @@ int ctrlsim_groups_changed(int S, int N, const int* n_groups, const int* grp_foc
   return launch_groups_changed(S, N, n_groups, grp_focal, (const unsigned long long*)grp_ids, ref_n, ref_focal,
                                (const unsigned long long*)ref_ids, flag, st);
 }
+static CtxOut ctx_out(const ctrlsim_ctx& c) {    // the output tensors of a context struct of the ABI as the kernels' argument
+  return CtxOut{c.st12, c.exist, c.goal5, c.act_tok, c.rtg_bin, c.tstep, c.slot_gid, c.road_pts, c.road_types};
+}
 int ctrlsim_build_context(int B, int N, int A, int T, int t, int Tq, int tt_first, int Tmax1, int Tmax, int P_all, int P, int NP,
                           const int* ctx_scn, const int* ctx_grp, const int* grp_focal, const uint64_t* grp_ids,
                           const float* hist_states, const int* hist_tok, const int* hist_rtg, const double* goals,
                           const float* types, const float* roads, const float* road_types, const int* zero4,
                           const ctrlsim_ctx* out, hipStream_t st) {
   if (!out || !zero4) return CTRLSIM_EINVAL;
-  CtxOut o{out->st12, out->exist, out->goal5, out->act_tok, out->rtg_bin, out->tstep, out->slot_gid, out->road_pts,
-           out->road_types};
   return launch_build_context(B, N, A, T, t, Tq, tt_first, Tmax1, Tmax, P_all, P, NP, ctx_scn, ctx_grp, grp_focal,
                               (const unsigned long long*)grp_ids, hist_states, hist_tok, hist_rtg, goals, types, roads,
-                              road_types, zero4, o, st);
+                              road_types, zero4, ctx_out(*out), st);
 }
 int ctrlsim_build_context_c(int n, const int* B, const int* A, const ctrlsim_ctx* out, int N, int T, int t, int Tq, int tt_first,
                             int Tmax1, int Tmax, int P_all, int P, int NP, const int* ctx_scn, const int* ctx_grp,
@@ -366,9 +315,7 @@ int ctrlsim_build_context_c(int n, const int* B, const int* A, const ctrlsim_ctx
                             const float* road_types, const int* zero4, hipStream_t st) {
   if (!out || !zero4 || !B || !A || n < 1 || n > MAXC) return CTRLSIM_EINVAL;
   CtxOut o[MAXC];
-  for (int k = 0; k < n; ++k)
-    o[k] = CtxOut{out[k].st12, out[k].exist, out[k].goal5, out[k].act_tok, out[k].rtg_bin, out[k].tstep, out[k].slot_gid,
-                  out[k].road_pts, out[k].road_types};
+  for (int k = 0; k < n; ++k) o[k] = ctx_out(out[k]);
   return launch_build_context_classes(n, B, A, o, N, T, t, Tq, tt_first, Tmax1, Tmax, P_all, P, NP, ctx_scn, ctx_grp, grp_focal,
                                       (const unsigned long long*)grp_ids, hist_states, hist_tok, hist_rtg, goals, types, roads,
                                       road_types, zero4, st);

@@ -22,7 +22,7 @@
 //
 // Queries may be a gathered subset (q_pos != nullptr): Q/O are then compact [B*Lq, .] buffers and q_pos[i] gives the
 // token position used by the mask (pass-2 / last-layer evaluation of the current-timestep tokens only).
-#include "common.h"
+#include "launchers.h"
 
 #ifndef KT
 #define KT 64
@@ -234,9 +234,6 @@ __global__ __launch_bounds__(256, ATT_WPS) void attention_f32_kernel(
     if (gq < Lq) O[(size_t)b * o_batch_stride + (size_t)gq * ldo + h * HD + l31] = ot[q * 33 + l31];
   }
 }
-
-int launch_attention_bf16x6(int, const float*, int, long, const float*, const float*, int, long, float*, int, long, const int*,
-                            const unsigned char*, int, int, int, int, hipStream_t);
 
 int launch_attention(int mode, const float* Q, int ldq, long q_batch_stride, const float* K, const float* V, int ldkv,
                      long kv_batch_stride, float* O, int ldo, long o_batch_stride, const int* q_pos,

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 namespace SPLIT_NS {
+#include "split_launchers.inc"      // this file's launchers are declared there
 
 #define ATT_PMAX 32768.0f     // row-sum bound of the speculative softmax path: every probability then fits the fp16 plane
 

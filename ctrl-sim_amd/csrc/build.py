@@ -125,7 +125,8 @@ def isa_guard(obj):
 
 
 def build(force=False, verbose=False):
-    deps = [os.path.join(HERE, "common.h"), os.path.join(HERE, "split.h"), os.path.join(HERE, "classes.h"), os.path.join(HERE, "..", "..", "include", "ctrlsim.h")]
+    deps = [os.path.join(HERE, h) for h in ("common.h", "split.h", "classes.h", "launchers.h", "split_launchers.inc")]
+    deps.append(os.path.join(HERE, "..", "..", "include", "ctrlsim.h"))
     objs = []
     procs = []
     try:

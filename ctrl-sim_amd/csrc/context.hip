@@ -13,7 +13,7 @@
 // Vehicle sets are 64-bit masks (N <= 64 vehicles per scenario = one wavefront; ballot gives the set, popcount the slot).
 // All geometry is float64 exactly as in the reference, results are rounded once to float32 (`.float()` in
 // modules/encoder.py:85,91-92,114 and modules/map_encoder.py:35-36).
-#include "common.h"
+#include "launchers.h"      // CtxOut
 
 #define TWO_PI_D 6.283185307179586476925286766559
 #define PI_D 3.14159265358979323846
@@ -295,18 +295,6 @@ __global__ __launch_bounds__(256) void ctx_index_classes_kernel(int s0, int s1, 
 }
 
 // ------------------------------------------------------------------------------------------------ context tensors
-struct CtxOut {
-  float* st12;            // [B, Tq, A, 12]  x,y,vx,vy,yaw,len,wid + 5 type one-hot (-1 padded slots)
-  float* exist;           // [B, Tq, A]
-  float* goal5;           // [B, A, 5]
-  int* act_tok;           // [B, Tq, A]
-  int* rtg_bin;           // [B, Tq, A, 3]
-  int* tstep;             // [B, Tq]
-  int* slot_gid;          // [B, A]   global vehicle index per slot, -1 = padded
-  float* road_pts;        // [B, P, NP, 3]
-  float* road_types;      // [B, P, 8]
-};
-
 // Up to MAXC classes of contexts (different slot counts A, separate output arrays) in ONE launch: class k holds the contexts
 // [c0[k], c0[k+1]) of the batch's context list.  One launch per class left most of the chip idle — a class of a model batch is
 // 50-150 contexts = workgroups, and a workgroup's float64 chain takes ~150 us whatever the grid.

@@ -13,7 +13,7 @@
 // This kernel is the fused gather + add + mask + LayerNorm: one wavefront per (b, tt, a), 4 channels per lane, rows
 // written as 1 KiB contiguous stores.  The pre-LN masked state row of window index 0 is also written to the scene
 // encoder's source buffer as that agent's "initial state" token (encoder.py:108-109,137-139), with its padding flag.
-#include "common.h"
+#include "launchers.h"      // EmbedTables
 
 __device__ __forceinline__ f32x4 ln256(f32x4 v, const f32x4 g, const f32x4 b) {
   const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / 256.f);
@@ -21,24 +21,6 @@ __device__ __forceinline__ f32x4 ln256(f32x4 v, const f32x4 g, const f32x4 b) {
   const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / 256.f);
   return d * (1.0f / sqrtf(var + 1e-5f)) * g + b;
 }
-
-struct EmbedTables {
-  const float* act;        // [V,256]      encoder.embed_action.weight
-  const float* rtg_g;      // [R,256]      E_goal @ W_rtg[:, 0:256]^T   (folded)
-  const float* rtg_v;      // [R,256]
-  const float* rtg_r;      // [R,256]
-  const float* rtg_bias;   // [256]
-  const float* tstep;      // [MAXT,256]   encoder.embed_timestep.weight
-  const float* agent;      // [A,256]      encoder.embed_agent_id.weight
-  const float* ln_g;       // [256]        encoder.embed_ln
-  const float* ln_b;
-  int rtg_linear;          // Decision Transformer: the RTGs are continuous (float bits in rtg_bin) and rtg_g/v/r are single
-                           // rows: embed_rtg(cat_c Linear_c(r_c)) = r_0 g + r_1 v + r_2 r + rtg_bias (pack.py fold)
-  int flags;               // ctrlsim_dims.flags (include/ctrlsim.h): bit 0 = cfg.model.no_actions — the action embeddings (with their timestep
-                           // and agent-id parts) are multiplied by zero before embed_ln (modules/encoder.py:129-130): an action row is
-                           // LayerNorm(0) = the norm's bias; bit 2 = encode_initial_state False — the vehicles' initial-state rows are no
-                           // keys of the scene encoder / the decoder's memory (modules/encoder.py:159-166): their padding byte is always 1
-};
 
 // Compact contexts (forward.hip): the context tensors hold A slots per step, of which the first Areg are "regular" and — when
 // Areg < A — the last one is the representative of the padded slots; a context's L token rows are the regular ones,

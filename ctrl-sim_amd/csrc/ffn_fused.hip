@@ -33,6 +33,7 @@
 #include <type_traits>
 
 namespace SPLIT_NS {
+#include "split_launchers.inc"      // this file's launchers are declared there
 
 namespace {
 

@@ -13,67 +13,16 @@
 //     cached per-layer K/V of pass 1 (the sampled RTG only changes tokens that are visible to the same agent's
 //     RTG/action tokens of that timestep: SURVEY.md §8a M6 corollary);
 //   * map encoder / embedding linear chains are folded at pack time (map_encoder.hip, embed.hip).
-// Everything is fp32; GEMMs and attention run on the f32-input MFMA.  No allocation, no synchronisation: the caller
-// provides the workspace (ctrlsim_forward_workspace_bytes) and a stream.
+// Activations, accumulation and results are fp32.  The shipped path runs every GEMM and attention product on the 16-bit matrix pipe as
+// partial products of split operand planes (split.h; the launchers behind dispatch.hip); the f32-input MFMA family (gemm.hip, attention.hip)
+// is the run-time selectable A/B fallback.  No allocation, no synchronisation: the caller provides the workspace
+// (ctrlsim_forward_workspace_bytes) and a stream.
 #include <string>
 #include <unordered_map>
 #include <vector>
 
-#include "common.h"
-#include "classes.h"
+#include "launchers.h"
 #include "../../include/ctrlsim.h"
-
-// launchers from the other translation units
-int launch_gemm_nt(const float*, int, const float*, int, const float*, const float*, int, float*, int, int, int, int, int,
-                   hipStream_t);
-int launch_gemm_nt_bf16x6(const float*, int, const void*, int, int, const float*, const float*, int, float*, int, int, int,
-                          int, int, const float*, const float*, hipStream_t);
-int launch_layernorm256(const float*, int, const float*, int, const float*, const float*, float*, int, int, int,
-                        hipStream_t);
-int launch_gemm_nt_bf16x6_kv(const float*, int, const void*, int, int, const float*, const float*, int, float*, int, int, int,
-                             int, int, const float*, const float*, void*, int, int, int, int, int, hipStream_t);
-int launch_kv_zero_tail(int, int, int, int, void*, hipStream_t);
-int launch_kv_zero_tails(int, const KvTailHost*, int, void* const*, hipStream_t);
-int launch_kv_split_rows_classes(const float*, const float*, int, int, const KvRowsHost*, void*, hipStream_t);
-int launch_outproj_ln_q(const float*, int, const float*, int, const void*, const float*, const float*, const float*, const void*, const float*,
-                        float*, int, float*, int, int, hipStream_t);
-int launch_ffn_fused_pre(const float*, int, const float*, int, const void*, const float*, const float*, const float*, const void*, const float*,
-                         const void*, const float*, const float*, const float*, float*, int, int, int, hipStream_t);
-int launch_ffn_fused_bf16x6(const float*, int, const void*, const float*, const void*, const float*, const float*, const float*,
-                            float*, int, int, int, hipStream_t);
-int launch_kv_split(const float*, const float*, int, long, int, int, int, void*, hipStream_t);
-int launch_kv_split_rows(const float*, const float*, int, long, const int*, int, int, int, void*, hipStream_t);
-int launch_attn_mask_tables(int, const AttnClassHost*, hipStream_t);
-size_t attn_mask_table_bytes(int, int);
-int launch_attention_classes(int, const float*, int, const void*, float*, int, const unsigned char*, int, const AttnClassHost*,
-                             hipStream_t);
-int launch_inproj_rs(const float*, int, const void*, const float*, float*, int, int, int, void*, int, int, const KvClassHost*, hipStream_t);
-int launch_gemm_nt_bf16x6_kvc(const float*, int, const void*, int, int, const float*, const float*, int, float*, int, int, int, int,
-                              int, const float*, const float*, void*, int, int, const KvClassHost*, hipStream_t);
-int launch_in_mlp(const float*, int, int, const float*, const float*, const float*, const float*, float*, int, int,
-                  hipStream_t);
-int launch_row_copy(const float*, int, float*, int, const int*, int, int, int, hipStream_t);
-int launch_gemm256_rows(const float*, int, const void*, int, int, const float*, float*, int, const int*, int, hipStream_t);
-int launch_attention(int, const float*, int, long, const float*, const float*, int, long, float*, int, long, const int*,
-                     const unsigned char*, int, int, int, int, hipStream_t);
-int launch_head_ce(const float*, int, const void*, const float*, const int*, int, long, long, int, int, int, int, float*, int, hipStream_t);
-int launch_row_lse(const float*, long, int, int, int, const int*, int, long, long, long, int, float*, int, hipStream_t);
-int launch_loss_reduce(const float*, const float*, const unsigned char*, const float*, const float*, float*, double*, double*, int, int, int,
-                       int, int, int, int, int, hipStream_t);
-struct EmbedTables { const float *act, *rtg_g, *rtg_v, *rtg_r, *rtg_bias, *tstep, *agent, *ln_g, *ln_b; int rtg_linear, flags; };
-int launch_assemble_tokens(int, int, int, int, const float*, const float*, const float*, const int*, const int*, const int*,
-                           EmbedTables, float*, float*, int, int, unsigned char*, hipStream_t);
-int launch_assemble_rows(int, int, int, int, int, const int*, const float*, const float*, const float*, const int*, const int*,
-                         const int*, EmbedTables, float*, hipStream_t);
-int launch_assemble_rtg_rows(int, int, int, int, int, int, int, int, const int*, const int*, const int*, const float*,
-                             const int*, EmbedTables, const int*, float*, hipStream_t);
-struct MapPoolWeights { const float *Wc2, *Wc, *G, *ln_b, *U, *cb, *Mt, *mb; int force_pad; };
-int launch_map_pool(int, int, int, int, const float*, MapPoolWeights, float*, unsigned char*, hipStream_t);
-int launch_map_pool_classes(int, const int*, const int*, const long*, int, int, const float*, MapPoolWeights, float*, unsigned char*,
-                            hipStream_t);
-int launch_assemble_tokens_classes(int, const int*, const int*, const int*, const int*, const long*, const long*, const long*, int,
-                                   const float*, const float*, const float*, const int*, const int*, const int*, EmbedTables, float*,
-                                   float*, int, unsigned char*, hipStream_t);
 
 namespace {
 
@@ -367,22 +316,6 @@ Ws carve(const ctrlsim_dims& d, const Batch& bt, char* base) {
   return w;
 }
 
-// qoff: token type whose rows feed the first pass's head (0 = state tokens; 2 = action tokens, Trajeglish).  Index lists of ONE
-// class: the Areg current-step query rows per context (positions in the context's row order — regular rows: position == key —
-// and global row indices), the polyline rows of the scene-encoder source, key_all: row -> key position in the K/V images.
-__global__ void fill_index_kernel(int B, int Areg, int L, int Lreg, int rep_k0, int ti, int P, int M, int qoff, long rL, long rM,
-                                  int* pos_state, int* pos_rtg, int* idx_state, int* idx_rtg, int* idx_poly, int* key_all) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B * P) idx_poly[i] = (int)rM + (i / P) * M + (i % P);
-  if (i < Areg) { pos_state[i] = (ti * Areg + i) * 3 + qoff; pos_rtg[i] = (ti * Areg + i) * 3 + 1; }
-  if (i < B * Areg) {
-    const int b = i / Areg, a = i - b * Areg;
-    idx_state[i] = (int)rL + b * L + (ti * Areg + a) * 3 + qoff;
-    idx_rtg[i] = (int)rL + b * L + (ti * Areg + a) * 3 + 1;
-  }
-  if (i < L) key_all[i] = i < Lreg ? i : rep_k0 + (i - Lreg);
-}
-
 // y = act(x W^T + b [+ R]) through the bf16x6 MFMA kernel when the packed planes exist, else the f32-input MFMA kernel
 int gemm(const Lin& L, const float* x, int ldx, const float* R, int ldr, float* y, int ldy, int rows, int n, int k, int relu,
          hipStream_t st) {
@@ -431,6 +364,9 @@ int outproj_ln_ffn(const Lin& lo, const LNp& no, const Lin& l1, const Lin& l2, c
 
 inline bool presplit() { return ctrlsim_option(OPT_ATTN_IMPL) == 1; }
 
+// profiling rows (common.h: prof_few) of an entry point: the state its launches start in; back to full-row when it returns
+struct FewScope { explicit FewScope(bool few) { prof_few(few); } ~FewScope() { prof_few(false); } };
+
 // What the queries / keys of an attention call are, per class
 enum QKind { Q_ALL, Q_SCENE, Q_STATE, Q_RTG, Q_NEW };   // all L token rows | the M scene rows | the Areg state (first-pass) rows |
                                                          // the Areg rtg rows | the cached path's new rows
@@ -446,7 +382,7 @@ struct AttnCall {
   int Rn_mul;                    // Q_NEW: rows per context = Rn_mul * A
   bool tbl = false;              // Q_ALL, causal: the classes' mask tables (Ws::mask_tbl) were built for this pass (build_mask_tables)
 };
-int attention(const ctrlsim_dims& d, const Batch& bt, const Ws& w, const AttnCall& a, hipStream_t st) {
+int attention(const Batch& bt, const Ws& w, const AttnCall& a, hipStream_t st) {
   AttnClassHost h[MAXC];
   for (int k = 0; k < bt.n; ++k) {
     const Cls& c = bt.c[k];
@@ -499,35 +435,35 @@ int build_mask_tables(const Batch& bt, const Ws& w, int Tq, hipStream_t st) {
   return launch_attn_mask_tables(bt.n, h, st);
 }
 
-// Linear whose last 512 output columns are attention keys / values: y[:, :kcol0] as fp32 rows, K / V as split images straight from
-// the GEMM epilogue when both bf16x6 kernels are selected (the fp32 K / V columns of y are then NOT written); otherwise GEMM +
-// a split pass per class.  mem: the scene / memory rows (M per context, plain key order) instead of the token rows.
+// key geometry of a class's K/V images: the token rows (mem = false) or the scene / memory rows (M per context, plain key order)
+KvClassHost kv_class(const Cls& c, bool mem) {
+  if (mem) return KvClassHost{c.B, c.M, c.M, 0, c.nkt_mem, c.tile_mem};
+  return KvClassHost{c.B, c.L, c.Lreg, c.sh.rep_k0(c.Lreg / (3 * c.sh.Areg)), c.nkt_dec, c.tile_dec};
+}
 // The tails the row-wise epilogues leave in the last tiles of the key regions: classes' entries for the token rows (mem = false) or the
 // scene rows (mem = true), applied to nimg image sets of that geometry in ONE launch (tails of whole sub-tiles are skipped: nobody reads them)
 int zero_kv_tails(const Batch& bt, bool mem, int nimg, void* const* imgs, hipStream_t st) {
   KvTailHost tails[2 * MAXC];
   int nt = 0;
   for (int k = 0; k < bt.n; ++k) {
-    const Cls& c = bt.c[k];
-    const int Lk = mem ? c.M : c.L, Lreg = mem ? c.M : c.Lreg, nkt = mem ? c.nkt_mem : c.nkt_dec;
-    const long tile0 = mem ? c.tile_mem : c.tile_dec;
-    tails[nt++] = KvTailHost{c.B, 0, Lreg, nkt, tile0};
-    if (Lreg < Lk) tails[nt++] = KvTailHost{c.B, c.sh.rep_k0(c.Lreg / (3 * c.sh.Areg)), Lk - Lreg, nkt, tile0};
+    const KvClassHost c = kv_class(bt.c[k], mem);
+    tails[nt++] = KvTailHost{c.B, 0, c.Lreg, c.nkt, c.tile0};
+    if (c.Lreg < c.L) tails[nt++] = KvTailHost{c.B, c.rep_k0, c.L - c.Lreg, c.nkt, c.tile0};
   }
   return launch_kv_zero_tails(nt, tails, nimg, imgs, st);
 }
 
-int gemm_kv(const ctrlsim_dims& d, const Batch& bt, const Ws& w, const Lin& L, const float* x, float* y, int ldy, int n, int kcol0,
+// Linear whose last 512 output columns are attention keys / values: y[:, :kcol0] as fp32 rows, K / V as split images straight from
+// the GEMM epilogue when both bf16x6 kernels are selected (the fp32 K / V columns of y are then NOT written); otherwise GEMM +
+// a split pass per class.  mem: the scene / memory rows instead of the token rows.
+int gemm_kv(const Batch& bt, const Ws& w, const Lin& L, const float* x, float* y, int ldy, int n, int kcol0,
             void* img, bool mem, hipStream_t st, bool tails_done = false) {
   const long rows = mem ? bt.rM : bt.rL;
   bool fused = presplit() && L.w3() && ctrlsim_option(OPT_GEMM_IMPL) == 1;
   KvClassHost kc[MAXC];
   for (int k = 0; k < bt.n; ++k) {
-    const Cls& c = bt.c[k];
-    const int Lk = mem ? c.M : c.L, Lreg = mem ? c.M : c.Lreg;
-    kc[k] = KvClassHost{c.B, Lk, Lreg, mem ? 0 : c.sh.rep_k0(c.Lreg / (3 * c.sh.Areg)), mem ? c.nkt_mem : c.nkt_dec,
-                        mem ? c.tile_mem : c.tile_dec};
-    fused = fused && !(Lk & 3) && !(Lreg & 3) && Lk >= 32;
+    kc[k] = kv_class(bt.c[k], mem);
+    fused = fused && !(kc[k].L & 3) && !(kc[k].Lreg & 3) && kc[k].L >= 32;
   }
   const size_t KIMG = split_kimg();      // 16-bit elements per tile
   if (fused) {
@@ -594,11 +530,14 @@ __global__ void fill_index_cached_kernel(int B, int Actx, int Areg, int Lf, int 
   }
 }
 
+// Linear(kin -> 256) + LayerNorm + ReLU of an input MLP on dense rows of kin features
+int in_mlp(const Mlp& p, const float* x, int kin, float* y, int rows, hipStream_t st) {
+  return launch_in_mlp(x, kin, kin, p.l0.w, p.l0.b, p.ln.g, p.ln.b, y, DM, rows, st);
+}
 int mlp_tail(const Mlp& m, const float* h_in, int rows, float* hid, float* out, int n_out, hipStream_t st, int ld_in = DM) {
   // Linear(256->256) -> LN -> ReLU -> Linear(256->n_out)
   CHK(gemm_ln(m.l0, m.ln, h_in, ld_in, nullptr, 0, hid, DM, hid, rows, DM, 1, st));
-  CHK(gemm(m.l3, hid, DM, nullptr, 0, out, n_out, rows, n_out, DM, 0, st));
-  return 0;
+  return gemm(m.l3, hid, DM, nullptr, 0, out, n_out, rows, n_out, DM, 0, st);
 }
 
 // what follows a decoder layer's self-attention, shared by the full-row and compact-row paths (post-LN): out-projection + residual + norm1
@@ -613,10 +552,9 @@ int cross_and_ffn(const ctrlsim_model* m, const Batch& bt, const DecLayer& Ld, i
     CHK(gemm_ln(Ld.out, Ld.n1, att, DM, x, DM, x, DM, tmp, (int)rows, DM, 0, st));
     CHK(gemm(Ld.cq, x, DM, nullptr, 0, qc, DM, (int)rows, DM, DM, 0, st));
   }
-  CHK(attention(d, bt, w, AttnCall{0, q, qc, DM, w.memkv[layer], w.memkv[layer] + DM, 2 * DM, w.img_mem[layer], true, att, 0, 0,
+  CHK(attention(bt, w, AttnCall{0, q, qc, DM, w.memkv[layer], w.memkv[layer] + DM, 2 * DM, w.img_mem[layer], true, att, 0, 0,
                                    Rn_mul}, st));
-  CHK(outproj_ln_ffn(Ld.cout, Ld.n2, Ld.lin1, Ld.lin2, Ld.n3, Ld.fp, att, x, ffn, tmp, (int)rows, d.F, st));
-  return 0;
+  return outproj_ln_ffn(Ld.cout, Ld.n2, Ld.lin1, Ld.lin2, Ld.n3, Ld.fp, att, x, ffn, tmp, (int)rows, d.F, st);
 }
 // The engine carves the context tensors of a batch's classes out of shared buffers back to back (CtxBuffers.class_structs);
 // then the per-(context, step, slot) / per-polyline kernels can run ONCE over all classes instead of once per class — a class of
@@ -634,26 +572,31 @@ bool ctx_contiguous(const ctrlsim_dims& d, const Batch& bt, int Tn) {
   return true;
 }
 
-// map encoder + scene encoder + per-layer memory K/V (everything that only depends on the frame of the context)
-int scene_side(const ctrlsim_model* m, const Batch& bt, const Ws& w, float* dbg_seg_emb, hipStream_t st) {
+// the polylines' pooled point features (attn_pre, with the padding bytes of their scene rows) and the first layer of the road-type MLP (tfh):
+// once over all classes where their context tensors lie back to back, else per class
+int map_inputs(const ctrlsim_model* m, const Batch& bt, const Ws& w, hipStream_t st) {
   const ctrlsim_dims& d = m->d;
-  const int P = d.P, rM = (int)bt.rM, rP = (int)bt.rP;
-  // ---- map encoder (map_encoder.py:34-53): rows of `src` 0..P-1 per context
   if (bt.contig) {
     int Bk[MAXC], Mk[MAXC];
     long pad0[MAXC];
     for (int k = 0; k < bt.n; ++k) { Bk[k] = bt.c[k].B; Mk[k] = bt.c[k].M; pad0[k] = bt.c[k].rM; }
-    CHK(launch_map_pool_classes(bt.n, Bk, Mk, pad0, P, d.NP, bt.c[0].ctx->road_pts, m->mp, w.attn_pre, w.src_pad, st));
-    CHK(launch_in_mlp(bt.c[0].ctx->road_types, 8, 8, m->road_type.l0.w, m->road_type.l0.b, m->road_type.ln.g, m->road_type.ln.b,
-                      w.tfh, DM, rP, st));
-  } else {
-    for (int k = 0; k < bt.n; ++k) {
-      const Cls& c = bt.c[k];
-      CHK(launch_map_pool(c.B, P, d.NP, c.M, c.ctx->road_pts, m->mp, w.attn_pre + c.rP * DM, w.src_pad + c.rM, st));
-      CHK(launch_in_mlp(c.ctx->road_types, 8, 8, m->road_type.l0.w, m->road_type.l0.b, m->road_type.ln.g, m->road_type.ln.b,
-                        w.tfh + c.rP * DM, DM, c.B * P, st));
-    }
+    CHK(launch_map_pool_classes(bt.n, Bk, Mk, pad0, d.P, d.NP, bt.c[0].ctx->road_pts, m->mp, w.attn_pre, w.src_pad, st));
+    return in_mlp(m->road_type, bt.c[0].ctx->road_types, 8, w.tfh, (int)bt.rP, st);
   }
+  for (int k = 0; k < bt.n; ++k) {
+    const Cls& c = bt.c[k];
+    CHK(launch_map_pool(c.B, d.P, d.NP, c.M, c.ctx->road_pts, m->mp, w.attn_pre + c.rP * DM, w.src_pad + c.rM, st));
+    CHK(in_mlp(m->road_type, c.ctx->road_types, 8, w.tfh + c.rP * DM, c.B * d.P, st));
+  }
+  return 0;
+}
+
+// map encoder + scene encoder + per-layer memory K/V (everything that only depends on the frame of the context)
+int scene_side(const ctrlsim_model* m, const Batch& bt, const Ws& w, float* dbg_seg_emb, hipStream_t st) {
+  const ctrlsim_dims& d = m->d;
+  const int rM = (int)bt.rM, rP = (int)bt.rP;
+  // ---- map encoder (map_encoder.py:34-53): rows of `src` 0..P-1 per context
+  CHK(map_inputs(m, bt, w, st));
   CHK(gemm_ln(m->map_out, m->map_n1, w.attn_pre, DM, nullptr, 0, w.m1, DM, w.m1, rP, DM, 0, st));            // emb
   CHK(gemm_ln(m->map_feats.l0, m->map_feats.ln, w.m1, DM, nullptr, 0, w.m2, DM, w.m2, rP, DM, 1, st));
   CHK(gemm_ln(m->map_feats.l3, m->map_n2, w.m2, DM, w.m1, DM, w.cat, 2 * DM, w.attn_pre, rP, DM, 0, st));   // cat[:, :256]
@@ -687,13 +630,13 @@ int scene_side(const ctrlsim_model* m, const Batch& bt, const Ws& w, float* dbg_
   const bool mem_tails_done = d.ND + 1 <= 8;
   for (int i = 0; i < d.NE; ++i) {
     const EncLayer& Le = m->enc[i];
-    CHK(gemm_kv(d, bt, w, Le.qkv, w.src, w.eqkv, 3 * DM, 3 * DM, DM, w.img_enc, true, st, true));
-    CHK(attention(d, bt, w, AttnCall{0, Q_SCENE, w.eqkv, 3 * DM, w.eqkv + DM, w.eqkv + 2 * DM, 3 * DM, w.img_enc, true, w.eatt, 0, 0, 0},
+    CHK(gemm_kv(bt, w, Le.qkv, w.src, w.eqkv, 3 * DM, 3 * DM, DM, w.img_enc, true, st, true));
+    CHK(attention(bt, w, AttnCall{0, Q_SCENE, w.eqkv, 3 * DM, w.eqkv + DM, w.eqkv + 2 * DM, 3 * DM, w.img_enc, true, w.eatt, 0, 0, 0},
                   st));
     CHK(outproj_ln_ffn(Le.out, Le.n1, Le.lin1, Le.lin2, Le.n2, Le.fp, w.eatt, w.src, w.effn, w.etmp, rM, d.F, st));
   }
   // memory K/V of every decoder layer (cached for pass 2)
-  for (int i = 0; i < d.ND; ++i) CHK(gemm_kv(d, bt, w, m->dec[i].ckv, w.src, w.memkv[i], 2 * DM, 2 * DM, 0, w.img_mem[i], true, st, mem_tails_done));
+  for (int i = 0; i < d.ND; ++i) CHK(gemm_kv(bt, w, m->dec[i].ckv, w.src, w.memkv[i], 2 * DM, 2 * DM, 0, w.img_mem[i], true, st, mem_tails_done));
   return 0;
 }
 
@@ -702,6 +645,9 @@ bool classes_ok(const ctrlsim_dims& d, const Batch& bt) {
     if (bt.c[k].sh.rep && (d.variant != 0 || !presplit())) return false;
   return true;
 }
+// Index lists of the classes of a batch.  Per class: the Areg current-step query rows per context (positions in the context's row order —
+// regular rows: position == key — and global row indices), the polyline rows of the scene-encoder source, key_all: row -> key position in
+// the K/V images.  qoff: token type whose rows feed the first pass's head (0 = state tokens; 2 = action tokens, Trajeglish).
 // (round 6: the classes of a model batch in ONE launch — sixteen 7-microsecond launches in front of every forward pass were 5 664 of the
 // profiled command's 76 k dispatches)
 struct FillCls { int wg0, B, Areg, L, Lreg, rep_k0, M; long rL, rM; int ioff, rQ, rP, koff; };
@@ -721,15 +667,19 @@ __global__ void fill_index_classes_kernel(FillBatch fb, int ti, int P, int qoff,
   }
   if (i < c.L) key_all[c.koff + i] = i < c.Lreg ? i : c.rep_k0 + (i - c.Lreg);
 }
-int launch_fill_index(const Batch& bt, const Ws& w, int P, int ti, int Tq, int qoff, hipStream_t st) {
+// new_rows (K/V-cached pass at t == 0: the scene side wants the lists of the Tq = 1 layout while `bt` describes the full-window cache): a
+// class's token rows are its 3 * A new rows from row rN on, the representative's keys straight behind the regular ones (rep_k0 = 0)
+int launch_fill_index(const Batch& bt, const Ws& w, int P, int ti, int Tq, int qoff, bool new_rows, hipStream_t st) {
   FillBatch fb;
   fb.n = 0;
   int wg = 0;
   for (int k = 0; k < bt.n; ++k) {
     const Cls& c = bt.c[k];
-    const int nidx = max(max(c.B * c.sh.A, c.B * P), c.L);
+    const int L = new_rows ? 3 * c.sh.A : c.L, Lreg = new_rows ? 3 * c.sh.Areg : c.Lreg;
+    const int nidx = max(max(c.B * c.sh.A, c.B * P), L);
     if (nidx <= 0) continue;
-    fb.c[fb.n++] = FillCls{wg, c.B, c.sh.Areg, c.L, c.Lreg, c.sh.rep_k0(Tq), c.M, c.rL, c.rM, (int)c.ioff, (int)c.rQ, (int)c.rP, (int)c.koff};
+    fb.c[fb.n++] = FillCls{wg, c.B, c.sh.Areg, L, Lreg, new_rows ? 0 : c.sh.rep_k0(Tq), c.M, new_rows ? c.rN : c.rL, c.rM,
+                           (int)c.ioff, (int)c.rQ, (int)c.rP, (int)c.koff};
     wg += (nidx + 255) / 256;
   }
   if (fb.n == 0) return CTRLSIM_OK;
@@ -737,26 +687,58 @@ int launch_fill_index(const Batch& bt, const Ws& w, int P, int ti, int Tq, int q
                      w.idx_poly, w.key_all);
   return ctrlsim_launch_status();
 }
-// first embedding layers: in_mlp per class (the context tensors of the classes are separate arrays), then the folded Linear once
+// first embedding layers: in_mlp once over all classes (context tensors back to back) or per class (separate arrays), then the folded Linear once
 int embed_inputs(const ctrlsim_model* m, const Batch& bt, const Ws& w, int Tn, bool goals, hipStream_t st) {
   if (bt.contig) {
-    CHK(launch_in_mlp(bt.c[0].ctx->st12, 12, 12, m->embed_state.l0.w, m->embed_state.l0.b, m->embed_state.ln.g, m->embed_state.ln.b,
-                      w.hS, DM, (int)bt.rS, st));
-    if (goals)
-      CHK(launch_in_mlp(bt.c[0].ctx->goal5, 5, 5, m->embed_goal.l0.w, m->embed_goal.l0.b, m->embed_goal.ln.g, m->embed_goal.ln.b,
-                        w.hG, DM, (int)bt.rA, st));
+    CHK(in_mlp(m->embed_state, bt.c[0].ctx->st12, 12, w.hS, (int)bt.rS, st));
+    if (goals) CHK(in_mlp(m->embed_goal, bt.c[0].ctx->goal5, 5, w.hG, (int)bt.rA, st));
   } else
   for (int k = 0; k < bt.n; ++k) {
     const Cls& c = bt.c[k];
-    CHK(launch_in_mlp(c.ctx->st12, 12, 12, m->embed_state.l0.w, m->embed_state.l0.b, m->embed_state.ln.g, m->embed_state.ln.b,
-                      w.hS + c.rS * DM, DM, c.B * Tn * c.sh.A, st));
-    if (goals)
-      CHK(launch_in_mlp(c.ctx->goal5, 5, 5, m->embed_goal.l0.w, m->embed_goal.l0.b, m->embed_goal.ln.g, m->embed_goal.ln.b,
-                        w.hG + c.rA * DM, DM, c.B * c.sh.A, st));
+    CHK(in_mlp(m->embed_state, c.ctx->st12, 12, w.hS + c.rS * DM, c.B * Tn * c.sh.A, st));
+    if (goals) CHK(in_mlp(m->embed_goal, c.ctx->goal5, 5, w.hG + c.rA * DM, c.B * c.sh.A, st));
   }
   CHK(gemm(m->fold_state, w.hS, DM, nullptr, 0, w.S2, DM, (int)bt.rS, DM, DM, 0, st));
   if (goals) CHK(gemm(m->fold_goal, w.hG, DM, nullptr, 0, w.Gp, DM, (int)bt.rA, DM, DM, 0, st));
   return 0;
+}
+// token rows of Tq window steps (encoder.py:95-153) and the initial-state rows of `src`: once over all classes where their context tensors
+// lie back to back, else per class.  new_rows: into the new-row buffer of the K/V-cached pass (Tq = 1: the token order of assemble_tokens
+// is then the pos_new order — regular (a, k), then the representative) instead of X
+int assemble_tokens(const ctrlsim_model* m, const Batch& bt, const Ws& w, int Tq, bool new_rows, hipStream_t st) {
+  const int P = m->d.P;
+  if (bt.contig && !new_rows) {
+    int Bk[MAXC], Ak[MAXC], Ar[MAXC], Mk[MAXC];
+    long xrow[MAXC], srow[MAXC], grow[MAXC];
+    for (int k = 0; k < bt.n; ++k) {
+      const Cls& c = bt.c[k];
+      Bk[k] = c.B; Ak[k] = c.sh.A; Ar[k] = c.sh.Areg; Mk[k] = c.M; xrow[k] = c.rL; srow[k] = c.rM; grow[k] = c.rA;
+    }
+    const ctrlsim_ctx* c0 = bt.c[0].ctx;
+    return launch_assemble_tokens_classes(bt.n, Bk, Ak, Ar, Mk, xrow, srow, grow, Tq, w.S2, w.Gp, c0->exist, c0->act_tok, c0->rtg_bin,
+                                          c0->tstep, m->tb, w.X, w.src, P, w.src_pad, st);
+  }
+  for (int k = 0; k < bt.n; ++k) {
+    const Cls& c = bt.c[k];
+    CHK(launch_assemble_tokens(c.B, Tq, c.sh.A, c.sh.Areg, w.S2 + c.rS * DM, w.Gp + c.rA * DM, c.ctx->exist, c.ctx->act_tok, c.ctx->rtg_bin,
+                               c.ctx->tstep, m->tb, new_rows ? w.xn + c.rN * DM : w.X + c.rL * DM, w.src + c.rM * DM, c.M, P,
+                               w.src_pad + c.rM, st));
+  }
+  return 0;
+}
+// K / V of a few-row pass's rows (qkv: compact rows in class order, leading dimension 3 * DM; q = Q_RTG or Q_NEW as in AttnCall) into layer i's
+// cache: the tile images (what the split-operand attention reads), or — f32-input MFMA family, which attends over the fp32 rows themselves —
+// the fp32 rows of the full-row projection (nothing reads those on the split-operand path: queries come from qkv, keys / values from the images)
+int kv_rows_to_cache(const Batch& bt, const Ws& w, int i, const float* qkv, QKind q, int Rn_mul, hipStream_t st) {
+  const bool nw = q == Q_NEW;
+  if (!presplit()) return launch_row_copy(qkv, 3 * DM, w.qkv[i], 3 * DM, nw ? w.idx_new : w.idx_rtg, (int)(nw ? bt.rN : bt.rQ), 3 * DM, 1, st);
+  KvRowsHost kr[MAXC];
+  for (int k = 0; k < bt.n; ++k) {
+    const Cls& c = bt.c[k];
+    kr[k] = nw ? KvRowsHost{c.B, Rn_mul * c.sh.A, c.nkt_dec, c.rN, c.tile_dec, w.key_new + 4 * c.ioff}
+               : KvRowsHost{c.B, c.sh.Areg, c.nkt_dec, c.rQ, c.tile_dec, w.pos_rtg + c.ioff};
+  }
+  return launch_kv_split_rows_classes(qkv + DM, qkv + 2 * DM, 3 * DM, bt.n, kr, w.img_dec[i], st);
 }
 
 }  // namespace
@@ -820,9 +802,16 @@ int head_ce(const Mlp& h, const void* ce_blk, const float* ce_bias, const float*
   }
   return 0;
 }
-int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, const ctrlsim_ctx* ctx, int Tq, void* workspace,
-                 float* logits, float* dbg_seg_emb, hipStream_t st, const AllOut* all = nullptr, hipStream_t st_tail = nullptr,
-                 bool split_tail = false, const LossReq* loss = nullptr) {
+// What a full forward computes — exactly one of: logits (the rollout head on the Areg queried rows per context), all (every head on every
+// token), loss (the same heads reduced to sums and counts)
+struct FullReq {
+  float* logits = nullptr; const AllOut* all = nullptr; const LossReq* loss = nullptr;
+  bool split_tail = false; hipStream_t st_tail = nullptr;   // rollout: the few-row tail on st_tail, event-ordered behind the full-row part
+  float* dbg_seg_emb = nullptr;                             // debug output of the scene side: the polylines' compact rows [sum B*P, 256]
+};
+int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, const ctrlsim_ctx* ctx, int Tq, void* workspace, hipStream_t st,
+                 const FullReq& rq) {
+  const AllOut* all = rq.all; const LossReq* loss = rq.loss; const bool every_token = all || loss;
   const ctrlsim_dims& d = m->d;
   // d.variant: token layout / heads (tok_variant: 4 = CtRL-Sim tokens) and, one to one, the attention mask mode 1 + d.variant
   const int variant = tok_variant(d.variant), amode = 1 + d.variant, qoff = variant == 2 ? 2 : 0;
@@ -830,65 +819,48 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
   Batch bt;
   CHK(make_batch(d, n, Bk, Ak, ctx, Tq, Tq, 4, bt));
   if (!classes_ok(d, bt)) return CTRLSIM_EINVAL;
-  struct FewScope { ~FewScope() { prof_few(false); } } few_scope;    // profiling rows: full-row part, then the few-row tail
-  prof_few(false);
+  FewScope few_scope(false);           // profiling rows: full-row part, then the few-row tail
   bt.contig = bt.n > 1 && ctx_contiguous(d, bt, Tq);
   const Ws w = carve(d, bt, static_cast<char*>(workspace));
-  const int P = d.P, ti = Tq - 1, rL = (int)bt.rL, rQ = (int)bt.rQ;
-  CHK(launch_fill_index(bt, w, P, ti, Tq, qoff, st));
+  const int ti = Tq - 1, rL = (int)bt.rL, rQ = (int)bt.rQ;
+  CHK(launch_fill_index(bt, w, d.P, ti, Tq, qoff, false, st));
   // ---- token embeddings (encoder.py:95-153)
   CHK(embed_inputs(m, bt, w, Tq, true, st));
-  if (bt.contig) {
-    int Bk[MAXC], Ak[MAXC], Ar[MAXC], Mk[MAXC];
-    long xrow[MAXC], srow[MAXC], grow[MAXC];
-    for (int k = 0; k < bt.n; ++k) {
-      const Cls& c = bt.c[k];
-      Bk[k] = c.B; Ak[k] = c.sh.A; Ar[k] = c.sh.Areg; Mk[k] = c.M; xrow[k] = c.rL; srow[k] = c.rM; grow[k] = c.rA;
-    }
-    CHK(launch_assemble_tokens_classes(bt.n, Bk, Ak, Ar, Mk, xrow, srow, grow, Tq, w.S2, w.Gp, bt.c[0].ctx->exist,
-                                       bt.c[0].ctx->act_tok, bt.c[0].ctx->rtg_bin, bt.c[0].ctx->tstep, m->tb, w.X, w.src, P,
-                                       w.src_pad, st));
-  } else {
-    for (int k = 0; k < bt.n; ++k) {
-      const Cls& c = bt.c[k];
-      CHK(launch_assemble_tokens(c.B, Tq, c.sh.A, c.sh.Areg, w.S2 + c.rS * DM, w.Gp + c.rA * DM, c.ctx->exist, c.ctx->act_tok,
-                                 c.ctx->rtg_bin, c.ctx->tstep, m->tb, w.X + c.rL * DM, w.src + c.rM * DM, c.M, P, w.src_pad + c.rM, st));
-    }
-  }
-  CHK(scene_side(m, bt, w, dbg_seg_emb, st));
+  CHK(assemble_tokens(m, bt, w, Tq, false, st));
+  CHK(scene_side(m, bt, w, rq.dbg_seg_emb, st));
   const bool use_tbl = d.variant == 0 && presplit() && ctrlsim_option(OPT_ATTN_TBL) != 0;   // (own-return mask: in-kernel masks, like the baselines)
   if (use_tbl) CHK(build_mask_tables(bt, w, Tq, st));
   // ---- decoder (decoder.py:52): layers 0..ND-2 on all tokens
   for (int i = 0; i < d.ND; ++i) {
     const DecLayer& Ld = m->dec[i];
-    const bool last_few = !(i < d.ND - 1 || all);
+    const bool last_few = !(i < d.ND - 1 || every_token);
     const bool kv_only = last_few && ctrlsim_option(OPT_LAST_KV) != 0;
     // the last layer of a rollout pass reads the queries of the A queried tokens only: keys and values of every token (two of the
     // in_proj's three column groups), queries from the gathered rows below — a twelfth of the pass's in_proj work less
-    if (kv_only) CHK(gemm_kv(d, bt, w, Ld.skv, w.X, w.qkv[i] + DM, 3 * DM, 2 * DM, 0, w.img_dec[i], false, st));
-    else CHK(gemm_kv(d, bt, w, Ld.qkv, w.X, w.qkv[i], 3 * DM, 3 * DM, DM, w.img_dec[i], false, st));
+    if (kv_only) CHK(gemm_kv(bt, w, Ld.skv, w.X, w.qkv[i] + DM, 3 * DM, 2 * DM, 0, w.img_dec[i], false, st));
+    else CHK(gemm_kv(bt, w, Ld.qkv, w.X, w.qkv[i], 3 * DM, 3 * DM, DM, w.img_dec[i], false, st));
     if (!last_few) {
-      CHK(attention(d, bt, w, AttnCall{amode, Q_ALL, w.qkv[i], 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false,
+      CHK(attention(bt, w, AttnCall{amode, Q_ALL, w.qkv[i], 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false,
                                        w.att, Tq, Tq, 0, use_tbl}, st));
       CHK(cross_and_ffn(m, bt, Ld, i, w, w.X, w.tmp, w.att, w.qc, w.ffn, bt.rL, Q_ALL, 0, st));
     } else {
       // last layer: only the queried tokens of the current timestep (state tokens; Trajeglish: action tokens) of the regular slots.
       // From here on every kernel touches Areg rows per context; a caller with a second stream gets this tail there, ordered
       // behind the full-row part by an event, so that the next batch's full-row kernels need not wait for it.
-      if (split_tail && st_tail != st) {
-        if (hipEventRecord(m->ev_tail, st) != hipSuccess || hipStreamWaitEvent(st_tail, m->ev_tail, 0) != hipSuccess) return CTRLSIM_ELAUNCH;
-        st = st_tail;
+      if (rq.split_tail && rq.st_tail != st) {
+        if (hipEventRecord(m->ev_tail, st) != hipSuccess || hipStreamWaitEvent(rq.st_tail, m->ev_tail, 0) != hipSuccess) return CTRLSIM_ELAUNCH;
+        st = rq.st_tail;
       }
       prof_few(true);
       CHK(launch_row_copy(w.X, DM, w.xc, DM, w.idx_state, rQ, DM, 0, st));
       if (kv_only) CHK(gemm(Ld.sq, w.xc, DM, nullptr, 0, w.qkvc, 3 * DM, rQ, DM, DM, 0, st));        // queries of the queried rows
       else CHK(launch_row_copy(w.qkv[i], 3 * DM, w.qkvc, 3 * DM, w.idx_state, rQ, 3 * DM, 0, st));
-      CHK(attention(d, bt, w, AttnCall{amode, Q_STATE, w.qkvc, 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false,
+      CHK(attention(bt, w, AttnCall{amode, Q_STATE, w.qkvc, 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false,
                                        w.attc, Tq, Tq, 0}, st));
       CHK(cross_and_ffn(m, bt, Ld, i, w, w.xc, w.tmpc, w.attc, w.qcc, w.ffnc, bt.rQ, Q_STATE, 0, st));
     }
   }
-  if (all) {
+  if (every_token) {
     // every head on every token of its type (decoder.py:55-77): token type k of (b, tt, a) is row ((b*Tq + tt)*A + a)*3 + k, so a
     // type is a strided view of X (leading dimension 3*DM).  Action head: the rtg token (CtRL-Sim), the state token (IL, and DT,
     // whose token order is rtg, state, action), the action token (Trajeglish); rtg head: state tokens; future states: action tokens.
@@ -910,22 +882,24 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
     return CTRLSIM_OK;
   }
   // ---- predict_rtg head on the state tokens (decoder.py:74-77) / predict_action for the baselines (decoder.py:58-64)
-  if (variant) return mlp_tail(m->head_action, w.xc, rQ, w.headh, logits, d.V, st);
-  return mlp_tail(m->head_rtg, w.xc, rQ, w.headh, logits, d.R * d.C, st);
+  if (variant) return mlp_tail(m->head_action, w.xc, rQ, w.headh, rq.logits, d.V, st);
+  return mlp_tail(m->head_rtg, w.xc, rQ, w.headh, rq.logits, d.R * d.C, st);
 }
 }  // namespace
 
 extern "C" int ctrlsim_dt_forward_pass1_c(const ctrlsim_model* m, int n, const int* B, const int* A, const ctrlsim_ctx* ctx, int Tq,
                                           void* workspace, float* rtg_logits, float* dbg_seg_emb, hipStream_t st) {
   if (!m || !ctx || !workspace || !rtg_logits || Tq < 1 || Tq > m->d.T || tok_variant(m->d.variant) != 0) return CTRLSIM_EINVAL;
-  return forward_full(m, n, B, A, ctx, Tq, workspace, rtg_logits, dbg_seg_emb, st);
+  FullReq rq; rq.logits = rtg_logits; rq.dbg_seg_emb = dbg_seg_emb;
+  return forward_full(m, n, B, A, ctx, Tq, workspace, st, rq);
 }
 // The same with the few-row tail (last decoder layer on the queried rows + the head) enqueued on `tail_stream`, behind the
 // full-row part on `stream` (event-ordered inside the call).  rtg_logits are complete in tail_stream order.
 extern "C" int ctrlsim_dt_forward_pass1_c2(const ctrlsim_model* m, int n, const int* B, const int* A, const ctrlsim_ctx* ctx, int Tq,
                                            void* workspace, float* rtg_logits, hipStream_t st, hipStream_t tail_stream) {
   if (!m || !ctx || !workspace || !rtg_logits || Tq < 1 || Tq > m->d.T || tok_variant(m->d.variant) != 0) return CTRLSIM_EINVAL;
-  return forward_full(m, n, B, A, ctx, Tq, workspace, rtg_logits, nullptr, st, nullptr, tail_stream, true);
+  FullReq rq; rq.logits = rtg_logits; rq.split_tail = true; rq.st_tail = tail_stream;
+  return forward_full(m, n, B, A, ctx, Tq, workspace, st, rq);
 }
 extern "C" int ctrlsim_dt_forward_pass1_a(const ctrlsim_model* m, int B, int Tq, int Actx, const ctrlsim_ctx* c, void* workspace,
                                           float* rtg_logits, float* dbg_seg_emb, hipStream_t st) {
@@ -939,7 +913,8 @@ extern "C" int ctrlsim_dt_forward_actions(const ctrlsim_model* m, int B, int Tq,
                                           float* act_logits, hipStream_t st) {
   if (!m || !c || !workspace || !act_logits || B < 1 || Tq < 1 || Tq > m->d.T || tok_variant(m->d.variant) == 0) return CTRLSIM_EINVAL;
   const int A = m->d.A;
-  return forward_full(m, 1, &B, &A, c, Tq, workspace, act_logits, nullptr, st);
+  FullReq rq; rq.logits = act_logits;
+  return forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq);
 }
 
 // The reference's return contract of CtRLSim.forward (models/ctrl_sim.py:41-45, decoder.py:52-77): teacher-forced, every head on
@@ -951,7 +926,8 @@ extern "C" int ctrlsim_forward_all(const ctrlsim_model* m, int B, int Tq, const 
   if ((rtg_preds && tok_variant(m->d.variant) != 0) || (state_preds && !m->has_fut)) return CTRLSIM_EINVAL;
   const int A = m->d.A;
   const AllOut all{action_preds, rtg_preds, state_preds};
-  return forward_full(m, 1, &B, &A, c, Tq, workspace, nullptr, nullptr, st, &all);
+  FullReq rq; rq.all = &all;
+  return forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq);
 }
 
 // Open-loop evaluation: CtRLSim.compute_loss of the teacher-forced forward (models/ctrl_sim.py:48-189,217-228) as sums and counts; no logits
@@ -973,8 +949,8 @@ extern "C" int ctrlsim_forward_loss(const ctrlsim_model* m, int B, int Tq, const
   char* ws = static_cast<char*>(workspace);
   const LossReq lq{moving, *cfg, sums, per_ctx, row_nll, reinterpret_cast<float*>(ws + l.LT), reinterpret_cast<float*>(ws + l.fut),
                    reinterpret_cast<float*>(ws + l.chunk), reinterpret_cast<double*>(ws + l.per_ctx), l.chunk_rows};
-  const AllOut all{nullptr, nullptr, nullptr};
-  return forward_full(m, 1, &B, &A, c, Tq, workspace, nullptr, nullptr, st, &all, nullptr, false, &lq);
+  FullReq rq; rq.loss = &lq;
+  return forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq);
 }
 // The same sums and counts from logits in memory — compute_loss(data, preds) on the tensors of ctrlsim_forward_all (token-row order
 // [B,Tq,A,.]; rtg_preds / state_preds NULL for a model without the head).  scratch: B * Tq * A * 8 floats + B * 10 doubles.
@@ -1026,7 +1002,7 @@ extern "C" int ctrlsim_dt_forward_pass2_c(const ctrlsim_model* m, int n, const i
   // tensors hold only the last Tn = min(Tq, 2) window rows
   const int Tw = cached ? d.T : Tq;
   const int ctx_rows = cached ? (Tq < 2 ? Tq : 2) : Tq, ti = ctx_rows - 1;
-  struct FewScope { FewScope() { prof_few(true); } ~FewScope() { prof_few(false); } } few_scope;   // profiling rows: few-row launches
+  FewScope few_scope(true);            // profiling rows: few-row launches
   Batch bt, lay;
   CHK(make_batch(d, n, Bk, Ak, ctx, Tw, ctx_rows, 4, bt));
   CHK(make_batch(d, n, Bk, Ak, ctx, Tw, cached ? 2 : ctx_rows, 4, lay));   // cached: the layout of ctrlsim_dt_forward_pass1_cached_c
@@ -1043,23 +1019,12 @@ extern "C" int ctrlsim_dt_forward_pass2_c(const ctrlsim_model* m, int n, const i
   for (int i = 0; i < d.ND; ++i) {
     const DecLayer& Ld = m->dec[i];
     CHK(gemm(Ld.qkv, w.xc2, DM, nullptr, 0, w.qkvc, 3 * DM, rQ, 3 * DM, DM, 0, st));
-    // refresh the rtg rows' K / V: in the tile images (what the split-operand attention reads), or — f32-input MFMA family, which
-    // attends over the fp32 rows themselves — in the fp32 rows of the pass-1 projection
-    if (!presplit()) CHK(launch_row_copy(w.qkvc, 3 * DM, w.qkv[i], 3 * DM, w.idx_rtg, rQ, 3 * DM, 1, st));
-    if (presplit()) {
-      KvRowsHost kr[MAXC];
-      for (int k = 0; k < bt.n; ++k) {
-        const Cls& c = bt.c[k];
-        kr[k] = KvRowsHost{c.B, c.sh.Areg, c.nkt_dec, c.rQ, c.tile_dec, w.pos_rtg + c.ioff};
-      }
-      CHK(launch_kv_split_rows_classes(w.qkvc + DM, w.qkvc + 2 * DM, 3 * DM, bt.n, kr, w.img_dec[i], st));
-    }
-    CHK(attention(d, bt, w, AttnCall{1 + d.variant, Q_RTG, w.qkvc, 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false, w.attc,
+    CHK(kv_rows_to_cache(bt, w, i, w.qkvc, Q_RTG, 0, st));      // refresh the rtg rows' K / V
+    CHK(attention(bt, w, AttnCall{1 + d.variant, Q_RTG, w.qkvc, 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false, w.attc,
                                      Tq, Tw, 0}, st));   // keys: steps <= current
     CHK(cross_and_ffn(m, bt, Ld, i, w, w.xc2, w.tmpc, w.attc, w.qcc, w.ffnc, bt.rQ, Q_RTG, 0, st));
   }
-  CHK(mlp_tail(m->head_action, w.xc2, rQ, w.headh, act_logits, d.V, st));
-  return CTRLSIM_OK;
+  return mlp_tail(m->head_action, w.xc2, rQ, w.headh, act_logits, d.V, st);
 }
 extern "C" int ctrlsim_dt_forward_pass2_a(const ctrlsim_model* m, int B, int Tq, int Actx, int t, int N, int Tmax,
                                           const ctrlsim_ctx* c, const int* ctx_scn, const int* hist_rtg, void* workspace,
@@ -1084,8 +1049,8 @@ extern "C" int ctrlsim_dt_forward_pass1_cached_c(const ctrlsim_model* m, int n, 
                                                  int t, void* workspace, float* rtg_logits, hipStream_t st) {
   if (!m || !ctx || !workspace || !rtg_logits || t < 0 || t >= m->d.T || m->d.variant != 0) return CTRLSIM_EINVAL;
   const ctrlsim_dims& d = m->d;
-  const int P = d.P, mul = t > 0 ? 4 : 3, tt_first = t > 0 ? t - 1 : 0, Tn = t + 1 - tt_first;
-  struct FewScope { FewScope() { prof_few(true); } ~FewScope() { prof_few(false); } } few_scope;   // profiling rows: few-row launches
+  const int mul = t > 0 ? 4 : 3, tt_first = t > 0 ? t - 1 : 0, Tn = t + 1 - tt_first;
+  FewScope few_scope(true);            // profiling rows: few-row launches
   Batch bt;
   CHK(make_batch(d, n, Bk, Ak, ctx, d.T, Tn, mul, bt));
   if (!classes_ok(d, bt)) return CTRLSIM_EINVAL;
@@ -1106,18 +1071,8 @@ extern "C" int ctrlsim_dt_forward_pass1_cached_c(const ctrlsim_model* m, int n, 
   CHK(embed_inputs(m, bt, w, Tn, t == 0, st));
   if (t == 0) {
     // index lists of the Tq = 1 layout for the scene side (idx_poly); pos_rtg / idx_rtg are rewritten for the cache layout below
-    for (int k = 0; k < bt.n; ++k) {
-      const Cls& c = bt.c[k];
-      const int nidx = max(max(c.B * c.sh.A, c.B * P), 3 * c.sh.A);
-      hipLaunchKernelGGL(fill_index_kernel, dim3((nidx + 255) / 256), dim3(256), 0, st, c.B, c.sh.Areg, 3 * c.sh.A, 3 * c.sh.Areg, 0, 0, P,
-                         c.M, 0, c.rN, c.rM, w.pos_state + c.ioff, w.pos_rtg + c.ioff, w.idx_state + c.rQ, w.idx_rtg + c.rQ,
-                         w.idx_poly + c.rP, w.key_all + c.koff);
-      // token order of assemble_tokens at Tq = 1 is the pos_new order (regular (a, k), then the representative); it also writes
-      // the initial-state rows of `src`
-      CHK(launch_assemble_tokens(c.B, 1, c.sh.A, c.sh.Areg, w.S2 + c.rS * DM, w.Gp + c.rA * DM, c.ctx->exist, c.ctx->act_tok,
-                                 c.ctx->rtg_bin, c.ctx->tstep, m->tb, w.xn + c.rN * DM, w.src + c.rM * DM, c.M, P, w.src_pad + c.rM,
-                                 st));
-    }
+    CHK(launch_fill_index(bt, w, d.P, 0, 1, 0, true, st));
+    CHK(assemble_tokens(m, bt, w, 1, true, st));
     CHK(scene_side(m, bt, w, nullptr, st));
     fill_cached();
   } else {
@@ -1130,27 +1085,15 @@ extern "C" int ctrlsim_dt_forward_pass1_cached_c(const ctrlsim_model* m, int n, 
   for (int i = 0; i < d.ND; ++i) {
     const DecLayer& Ld = m->dec[i];
     CHK(gemm(Ld.qkv, w.xn, DM, nullptr, 0, w.qkvn, 3 * DM, rN, 3 * DM, DM, 0, st));
-    // K / V of the new rows into the cache: the tile images (split-operand attention) or the fp32 rows (f32-input MFMA family; nothing
-    // reads the fp32 cache rows on the split-operand path: queries come from qkvn, keys and values from the images)
-    if (!presplit()) CHK(launch_row_copy(w.qkvn, 3 * DM, w.qkv[i], 3 * DM, w.idx_new, rN, 3 * DM, 1, st));
-    if (presplit()) {
-      if (t == 0) {   // image tiles are read whole: stale bits beyond the written rows must at least be finite
-        if (hipMemsetAsync(w.img_dec[i], 0, w.img_dec_bytes, st) != hipSuccess) return CTRLSIM_ELAUNCH;
-      }
-      KvRowsHost kr[MAXC];
-      for (int k = 0; k < bt.n; ++k) {
-        const Cls& c = bt.c[k];
-        kr[k] = KvRowsHost{c.B, mul * c.sh.A, c.nkt_dec, c.rN, c.tile_dec, w.key_new + 4 * c.ioff};
-      }
-      CHK(launch_kv_split_rows_classes(w.qkvn + DM, w.qkvn + 2 * DM, 3 * DM, bt.n, kr, w.img_dec[i], st));
-    }
-    CHK(attention(d, bt, w, AttnCall{1, Q_NEW, w.qkvn, 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false, w.attn_n,
+    // image tiles are read whole: stale bits beyond the written rows must at least be finite
+    if (presplit() && t == 0 && hipMemsetAsync(w.img_dec[i], 0, w.img_dec_bytes, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+    CHK(kv_rows_to_cache(bt, w, i, w.qkvn, Q_NEW, mul, st));    // K / V of the new rows
+    CHK(attention(bt, w, AttnCall{1, Q_NEW, w.qkvn, 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false, w.attn_n,
                                      t + 1, d.T, mul}, st));
     CHK(cross_and_ffn(m, bt, Ld, i, w, w.xn, w.tmpn, w.attn_n, w.qcn, w.ffnn, bt.rN, Q_NEW, mul, st));
   }
   CHK(launch_row_copy(w.xn, DM, w.xc, DM, w.idx_state_in_new, rQ, DM, 0, st));
-  CHK(mlp_tail(m->head_rtg, w.xc, rQ, w.headh, rtg_logits, d.R * d.C, st));
-  return CTRLSIM_OK;
+  return mlp_tail(m->head_rtg, w.xc, rQ, w.headh, rtg_logits, d.R * d.C, st);
 }
 extern "C" int ctrlsim_dt_forward_pass1_cached_a(const ctrlsim_model* m, int B, int t, int Actx, const ctrlsim_ctx* c,
                                                  void* workspace, float* rtg_logits, hipStream_t st) {

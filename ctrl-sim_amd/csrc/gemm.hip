@@ -13,7 +13,7 @@
 // labelling inside a chunk is free as long as A and B use the same one.
 // Block ids are remapped so that all N-tiles of an M-tile run on one XCD (block b -> XCD b%8): the activation
 // slab is then fetched into a single XCD's L2.
-#include "common.h"
+#include "launchers.h"
 
 #define BM 128
 #define BN 128

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 namespace SPLIT_NS {
+#include "split_launchers.inc"      // this file's launchers are declared there
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -437,10 +438,6 @@ __global__ __launch_bounds__(256, MR == 1 ? 4 : ((WR == 2 && WC == 2) ? GEMM_OCC
   }
 }
 
-int launch_gemm_nt_bf16x6_kvc(const float* A, int lda, const void* W3, int n_total, int n0, const float* bias,
-                              const float* R, int ldr, float* C, int ldc, int M, int N, int K, int relu,
-                              const float* ln_gamma, const float* ln_beta, void* kv_img, int kv_col0, int kv_n,
-                              const KvClassHost* kv_cls, hipStream_t st);
 int launch_gemm_nt_bf16x6(const float* A, int lda, const void* W3, int n_total, int n0, const float* bias,
                           const float* R, int ldr, float* C, int ldc, int M, int N, int K, int relu,
                           const float* ln_gamma, const float* ln_beta, hipStream_t st) {

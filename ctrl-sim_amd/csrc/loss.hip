@@ -14,6 +14,7 @@
 // This file is compiled once per operand split (build.py: SPLIT_SRCS); the kernels that do not depend on the split, (b) and (c), are
 // compiled in the two-plane build only and live outside the scheme namespace.
 #include "split.h"
+#include "launchers.h"
 
 // one (lse, target logit) pair per row and softmax: LT[row][4][2]; softmax 0 = actions, 1..3 = return components goal / veh / road
 #define LT_STRIDE 8

@@ -16,27 +16,13 @@
 // One workgroup per polyline: phase 1 thread-per-point (LN statistics + 8 scores, weights are wave-uniform scalar
 // loads), phase 2 thread-per-channel (softmax-weighted pooling), phase 3 thread-per-output (256x256 folded matrix,
 // stored transposed so the wave reads it coalesced from L2).
-#include "common.h"
-#include "classes.h"
+#include "launchers.h"      // MapPoolWeights
 #include <type_traits>
 
 #define MAXNP 256
 #ifndef MAP_PK
 #define MAP_PK 1          // 1: the packed-fp32 kernel (round 6), 0: the scalar kernel (A/B)
 #endif
-
-struct MapPoolWeights {
-  const float* Wc2;     // [128,4,2] the same with the channels of a pair interleaved per component (packed kernel: scalar register pairs)
-  const float* Wc;      // [256,4]  g_c * (W1[c,:] - column mean, b1[c] - mean(b1)): LN(W1 p + b1)_c = Wc[c] . (x,y,e,1) * rstd + ln_b[c]
-  const float* G;       // [10]     upper triangle of sum_c wt_c wt_c^T / 256 (wt = Wc without the gain): var = (x,y,e,1)^T G (x,y,e,1)
-  const float* ln_b;    // [256]
-  const float* U;       // [256,8]
-  const float* cb;      // [8]
-  const float* Mt;      // [256(c),256(j)]
-  const float* mb;      // [256]
-  int force_pad;        // 1: cfg.model.use_map = False (ctrlsim_dims.flags bit 1) — every polyline row is key-padded: the scene encoder and the
-                        // decoder's memory then hold the vehicles' initial-state rows only, as modules/encoder.py:168-170 builds them
-};
 
 // G polylines per workgroup (2 when a polyline has <= 128 points).  Only VISIBLE points are evaluated: a padded point has softmax
 // weight exp(-inf) = 0 and adds an exact zero to every sum, so the points of the workgroup's polylines are first compacted (order

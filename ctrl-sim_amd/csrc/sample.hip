@@ -11,7 +11,7 @@
 // ctrlsim_amd/weights.py: key = H(seed, scenario, t, agent, head), u = (top24(splitmix64(key + i*C)) + 0.5) / 2^24,
 // q = (float)(-log u).
 // One wavefront per (scenario, vehicle); lanes stride over the vocabulary.
-#include "common.h"
+#include "launchers.h"
 
 __device__ __forceinline__ uint64_t noise_key(uint64_t seed, uint64_t scenario, uint64_t t, uint64_t agent,
                                               uint64_t head) {

@@ -19,7 +19,7 @@
 // One workgroup per scenario; lane i < N owns vehicle i (N <= 64: one wavefront of vehicles), all 256 threads share
 // the N x N and N x E collision tests.  State is SoA-per-scenario [S, N, ...] so a wave's loads are contiguous.
 #include <cstdlib>
-#include "common.h"
+#include "launchers.h"
 // -DSIM_JITTER (tools only): random per-wave stalls around every workgroup barrier of the step — a missing barrier / a data race
 // between the waves of a scenario's workgroup then shows as a run-to-run difference even with nothing else on the device
 #ifdef SIM_JITTER
