@@ -112,6 +112,14 @@ int launch_sim_step(int S, int N, int E, const int* act_tok, const double* act_f
                     const unsigned char* exists, float* phys, float* hist_states, unsigned char* coll, double* applied, int t, int Tmax1, float dt,
                     int kinematic, float* contact_state, const float* expert, hipStream_t st);
 
+// ---- replay.hip
+int launch_replay_latch(int S, int N, int t, int T1, const double* log, const float* phys, double* exist_hist, float* hist_states,
+                        float* speed_hist, hipStream_t st);
+int launch_replay_actions(int S, int N, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
+                          const unsigned char* controlled, const double* exist_hist, const float* hist_states, const float* phys,
+                          const int* act_now, const double* disc6, double* act_f64, unsigned char* exists, int* hist_tok,
+                          hipStream_t st);
+
 // ---- sample.hip
 int launch_sample_rtg(const float* rtg_logits, int A, int R, const int* own_ctx, const int* own_slot, const int* ctx_row0,
                       const unsigned char* tilted, const double* tilt3, const double* tilt_scn, const float* noise, uint64_t seed,

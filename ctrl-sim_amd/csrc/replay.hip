@@ -1,0 +1,126 @@
+// Device-side log replay (gfx950): who drives a vehicle at step t — the policy or its log — decided and carried out per vehicle on the
+// device, so that a partially controlled logged scene rolls inside RolloutEngine.run() without a host round trip per step.  One thread
+// per vehicle, float64, two kernels per step:
+//
+//   replay_latch_kernel     existence of step t = the log's flag, latched at 0 once it was 0
+//                           evaluators/policy_evaluator.py:118-121 (update_vehicle_data_dict: `if t > 0 and existence[-1] == 0: ex = 0`),
+//                           with the speed read-back of the same function (veh.getSpeed()) as an optional per-step record
+//   replay_actions_kernel   the (acceleration, steering) pair of step t, the simulator's `exists` flag and the action-history token:
+//                           evaluators/policy_evaluator.py:534-540  vehicles_to_evaluate from t >= history_steps - 1: policy.act, else
+//                                                                   apply_gt_action
+//                           policies/autoregressive_policy.py:256-274  act: the sampled token undiscretised; a vehicle that does not exist
+//                                                                   any more is parked; a vehicle no context answers for gets (0, 0)
+//                           datasets/rl_waymo/dataset.py:322-338    undiscretize_actions / discretize_actions
+//                           evaluators/evaluator.py:160-193         apply_gt_action: valid iff the log holds this step and the next one and
+//                                                                   the vehicle has not been latched out; else (0, 0) and parked
+//                           nocturne/bicycle_model.py:51-109        BicycleModel.backward: the inverse bicycle model against the next
+//                                                                   logged state (with utils/geometry.py:3-12 angle_sub)
+// Arithmetic follows the NumPy expressions of ctrlsim_amd/kinematics.py and ctrlsim_amd/discretize.py operation by operation (no FMA
+// contraction; `%` as NumPy defines it for floats: fmod, then the divisor's sign), so that everything but the arctangent — a library
+// function on both sides — gives the host's bits (ctrlsim_amd/replay.py is the host form the tests compare with).
+#include "launchers.h"
+#include "../../include/ctrlsim.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+struct ReplayDisc {          // cfgs/dataset/waymo/base.yaml:13-16,41-42
+  double min_accel, max_accel, min_steer, max_steer;
+  int n_accel, n_steer;
+};
+
+__global__ __launch_bounds__(256) void replay_latch_kernel(int n, int t, int T1, const double* __restrict__ log,
+                                                           const float* __restrict__ phys, double* __restrict__ exist_hist,
+                                                           float* __restrict__ hist_states, float* __restrict__ speed_hist) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double e = log[((size_t)i * (T1 + 1) + t) * 6 + 4];
+  if (t > 0) e = e * (exist_hist[(size_t)i * T1 + t - 1] != 0.0 ? 1.0 : 0.0);
+  exist_hist[(size_t)i * T1 + t] = e;
+  hist_states[((size_t)i * T1 + t) * 8 + 7] = (float)e;
+  if (speed_hist) speed_hist[(size_t)i * T1 + t] = phys[(size_t)i * 20 + 16];
+}
+
+__global__ __launch_bounds__(256) void replay_actions_kernel(int n, int t, int T1, int Tmax, int history_steps, double dt,
+                                                             const double* __restrict__ log,
+                                                             const unsigned char* __restrict__ controlled,
+                                                             const double* __restrict__ exist_hist,
+                                                             const float* __restrict__ hist_states, const float* __restrict__ phys,
+                                                             const int* __restrict__ act_now, ReplayDisc dz,
+                                                             double* __restrict__ act_f64, unsigned char* __restrict__ exists,
+                                                             int* __restrict__ hist_tok) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double ex = exist_hist[(size_t)i * T1 + t];
+  const bool by_policy = controlled[i] != 0 && t >= history_steps - 1;
+  double accel = 0.0, steer = 0.0;
+  bool alive;
+  if (by_policy) {
+    alive = ex != 0.0;
+    const int tok = act_now[i];
+    if (alive && tok >= 0) {                               // undiscretize_actions: the expressions of csrc/sim.hip's token path
+      accel = (double)(tok / dz.n_steer) / (double)(dz.n_accel - 1);
+      steer = (double)(tok % dz.n_steer) / (double)(dz.n_steer - 1);
+      accel = accel * (dz.max_accel - dz.min_accel) + dz.min_accel;
+      steer = steer * (dz.max_steer - dz.min_steer) + dz.min_steer;
+    }
+  } else {
+    const double* cur = log + ((size_t)i * (T1 + 1) + t) * 6;
+    const double* nx = cur + 6;
+    alive = cur[4] != 0.0 && nx[4] != 0.0 && !(t > 0 && ex == 0.0);
+    if (alive) {
+      const float* row = hist_states + ((size_t)i * T1 + t) * 8;
+      const double p_th = (double)row[4], p_v = (double)phys[(size_t)i * 20 + 16];
+      const double n_th = nx[2], n_v = nx[3], n_len = nx[5];
+      const double two_pi = 2.0 * 3.141592653589793;
+      accel = (n_v - p_v) / dt;
+      double d = fmod(n_th - p_th, two_pi);                 // angle_sub(current = prev, target = next)
+      if (d != 0.0) { if (d < 0.0) d += two_pi; } else d = 0.0;
+      if (d > 3.141592653589793) d = -(two_pi - d);
+      const double w = d / dt;
+      const double c = 2.0 * n_len * w / (n_v + p_v + 1e-10);
+      steer = atan(2.0 * c / sqrt(4.0 - c * c));
+      if (steer != steer) steer = 0.0;
+      steer = fmin(fmax(steer, -0.7), 0.7);
+    }
+  }
+  act_f64[(size_t)i * 2 + 0] = accel;
+  act_f64[(size_t)i * 2 + 1] = steer;
+  exists[i] = alive ? 1 : 0;
+  // discretize_actions: clip, scale, round half to even
+  const double a0 = (fmin(fmax(accel, dz.min_accel), dz.max_accel) - dz.min_accel) / (dz.max_accel - dz.min_accel);
+  const double a1 = (fmin(fmax(steer, dz.min_steer), dz.max_steer) - dz.min_steer) / (dz.max_steer - dz.min_steer);
+  const double tokf = rint(a0 * (double)(dz.n_accel - 1)) * (double)dz.n_steer + rint(a1 * (double)(dz.n_steer - 1));
+  hist_tok[(size_t)i * Tmax + t] = (int)tokf;
+}
+
+}  // namespace
+
+int launch_replay_latch(int S, int N, int t, int T1, const double* log, const float* phys, double* exist_hist, float* hist_states,
+                        float* speed_hist, hipStream_t st) {
+  if (S <= 0) return CTRLSIM_OK;
+  if (N < 1 || t < 0 || t >= T1 || !log || !exist_hist || !hist_states || (speed_hist && !phys)) return CTRLSIM_EINVAL;
+  const long n = (long)S * N;
+  if (n > 0x7fffffffL - 256) return CTRLSIM_EINVAL;
+  hipLaunchKernelGGL(replay_latch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, t, T1, log, phys, exist_hist,
+                     hist_states, speed_hist);
+  return ctrlsim_launch_status();
+}
+
+int launch_replay_actions(int S, int N, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
+                          const unsigned char* controlled, const double* exist_hist, const float* hist_states, const float* phys,
+                          const int* act_now, const double* disc6, double* act_f64, unsigned char* exists, int* hist_tok,
+                          hipStream_t st) {
+  if (S <= 0) return CTRLSIM_OK;
+  if (N < 1 || t < 0 || t >= Tmax || t + 1 >= T1 || !log || !controlled || !exist_hist || !hist_states || !phys || !act_now || !disc6 ||
+      !act_f64 || !exists || !hist_tok)
+    return CTRLSIM_EINVAL;
+  const long n = (long)S * N;
+  if (n > 0x7fffffffL - 256) return CTRLSIM_EINVAL;
+  ReplayDisc dz{disc6[0], disc6[1], disc6[2], disc6[3], (int)disc6[4], (int)disc6[5]};
+  if (dz.n_accel < 2 || dz.n_steer < 2) return CTRLSIM_EINVAL;
+  hipLaunchKernelGGL(replay_actions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, t, T1, Tmax, history_steps, dt,
+                     log, controlled, exist_hist, hist_states, phys, act_now, dz, act_f64, exists, hist_tok);
+  return ctrlsim_launch_status();
+}

@@ -298,6 +298,7 @@ class RolloutEngine:
         self._ws_cap = L0.ws.numel()
         self._main = torch.cuda.current_stream(self.device)
         self.S = 0
+        self.log = None                         # set_log: logs of the loaded scenarios (partially controlled scenes)
 
     def _bind(self):
         _lib.check(self.lib.ctrlsim_bind(int(self.scheme), self.guard.data_ptr()), "bind")
@@ -408,7 +409,37 @@ class RolloutEngine:
         self.groups_per_step = np.zeros((self.steps, S), np.int32)
         self.guard.zero_()
         self._unchecked = []
+        self.log = None                         # a new batch starts without a log (set_log)
         self.reset()
+
+    def set_log(self, log, controlled, history_steps=1):
+        """Attach the logs of the loaded scenarios: from now on run() / run_jobs() / step() roll them as PARTIALLY CONTROLLED scenes
+        (csrc/replay.hip; evaluators/policy_evaluator.py:534-540) — `controlled` [S,N] vehicles take their sampled token from step
+        history_steps - 1 on, every other vehicle (and the controlled ones before that step) replays its log through the inverse bicycle
+        model, and existence follows the log, latched at 0.  log [S,N,steps+2,6] float64 = x, y, heading, speed, exist, length per step,
+        zero rows past the end of a vehicle's log.  reset() keeps the log; set_log(None, None) detaches it (load_scenarios does too).
+        Call it on freshly loaded / reset scenarios: the rollout starts at step 0."""
+        if log is None:
+            if self.log is not None:
+                self.exists.fill_(1)            # the replay kernels' parked flags go with the log
+            self.log = None
+            return self
+        dev, S, N, T1 = self.device, self.S, self.N, self.steps + 1
+        as_dev = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, dt).contiguous()
+        log = as_dev(log, torch.float64)
+        ctrl = as_dev(np.asarray(controlled).astype(np.uint8) if not torch.is_tensor(controlled) else controlled, torch.uint8)
+        assert tuple(log.shape) == (S, N, T1 + 1, 6) and tuple(ctrl.shape) == (S, N), "log [S,N,steps+2,6], controlled [S,N]"
+        assert not self.dims.VARIANT or not self.device_ledger, "the Decision-Transformer reward ledger keeps the step-by-step route"
+        self.log, self.controlled, self.history_steps = log, ctrl, int(history_steps)
+        z = lambda *sh, dt: torch.zeros(*sh, dtype=dt, device=dev)
+        self.exist_hist = z(S, N, T1, dt=torch.float64)
+        self.speed_hist = z(S, N, T1, dt=torch.float32)
+        self.act_f64 = z(S, N, 2, dt=torch.float64)
+        self.applied_steps = z(self.steps, S, N, 2, dt=torch.float64)       # step-major: row t is the [S,N,2] array the simulator writes
+        self.own_ctx_steps = z(self.steps, S, N, dt=torch.int32)            # own_ctx of every step (>= 0: a context answers for the vehicle)
+        self.sampled_steps = z(self.steps, S, N, dt=torch.int32)            # act_now of every step: the sampled tokens, < 0 = nobody answers
+        self.exists.fill_(1)
+        return self
 
     def reset(self, s0=0, s1=None):
         """Back to step 0 for scenarios [s0, s1) (default: all)."""
@@ -422,6 +453,15 @@ class RolloutEngine:
         self.hist_rtg[sl].copy_(self._zero_rtg_row.expand_as(self.hist_rtg[sl]))
         self.persist[sl].zero_()
         self.applied[sl].zero_()
+        if self.log is not None:
+            # the replay kernels left the last step's parked flags in `exists`; a rollout starts with every vehicle in the world, and
+            # the per-step records start empty
+            self.exists[sl].fill_(1)
+            self.exist_hist[sl].zero_()
+            self.speed_hist[sl].zero_()
+            self.applied_steps[:, sl].zero_()
+            self.own_ctx_steps[:, sl].zero_()
+            self.sampled_steps[:, sl].zero_()
         p = _lib.ptr
         _lib.check(self.lib.ctrlsim_sim_init(s1 - s0, self.N, self.E, p(self.init_pose[sl]), p(self.size[sl]), p(self.edges[sl]),
                                              p(self.exists[sl]), p(self.phys[sl]), p(self.hist_states[sl]), p(self.coll[sl]),
@@ -475,8 +515,9 @@ class RolloutEngine:
         return plan, n, Bs, As, cs
 
     # ------------------------------------------------------------------ kernels of one step, on explicit streams
-    def sim_step(self, t, act_f64=None, s0=0, s1=None, stream=None):
-        """Simulator step of scenarios [s0, s1) (default: all)."""
+    def sim_step(self, t, act_f64=None, s0=0, s1=None, stream=None, applied=None):
+        """Simulator step of scenarios [s0, s1) (default: all).  applied: [S,N,2] float64 tensor that receives the continuous actions
+        of the step (None: not recorded)."""
         lib, p = self.lib, _lib.ptr
         if stream is None:
             self._bind()                        # direct calls (plugin surface); run() binds once for its whole schedule
@@ -486,7 +527,8 @@ class RolloutEngine:
         _lib.check(lib.ctrlsim_sim_step(s1 - s0, self.N, self.E, p(self.act_now[sl]) if act_f64 is None else None,
                                         p(act_f64[sl]) if act_f64 is not None else None, self.disc6, p(self.size[sl]),
                                         p(self.edges[sl]), p(self.exists[sl]), p(self.phys[sl]), p(self.hist_states[sl]),
-                                        p(self.coll[sl]), None, t, self.steps + 1, self.dt, self.kinematic,
+                                        p(self.coll[sl]), p(applied[sl]) if applied is not None else None, t, self.steps + 1, self.dt,
+                                        self.kinematic,
                                         p(self.contact_state[sl]) if self.contact_state is not None else None, st), "sim_step")
 
     def _group_build(self, t, s0=0, s1=None, stream=None):
@@ -538,13 +580,39 @@ class RolloutEngine:
             self.ref_focal[sl].copy_(self.grp_focal[sl])
             self.ref_ids[sl].copy_(self.grp_ids[sl])
 
+    def _replay_latch(self, t, s0, s1, st):
+        """Log attached: existence of row t for [s0, s1) (ctrlsim_replay_latch), behind the simulator step that wrote the row."""
+        p, sl = _lib.ptr, slice(s0, s1)
+        _lib.check(self.lib.ctrlsim_replay_latch(s1 - s0, self.N, t, self.steps + 1, p(self.log[sl]), p(self.phys[sl]),
+                                                 p(self.exist_hist[sl]), p(self.hist_states[sl]), p(self.speed_hist[sl]), st),
+                   "replay_latch")
+
+    def _replay_actions(self, t, s0, s1, st):
+        """Log attached: who drives at step t, the replay actions, `exists` and the action-history tokens of [s0, s1)
+        (ctrlsim_replay_actions), behind the action sampling of the step."""
+        p, sl = _lib.ptr, slice(s0, s1)
+        _lib.check(self.lib.ctrlsim_replay_actions(s1 - s0, self.N, t, self.steps + 1, self.steps, self.history_steps, self.dt,
+                                                   p(self.log[sl]), p(self.controlled[sl]), p(self.exist_hist[sl]),
+                                                   p(self.hist_states[sl]), p(self.phys[sl]), p(self.act_now[sl]), self.disc6,
+                                                   p(self.act_f64[sl]), p(self.exists[sl]), p(self.hist_tok[sl]), st), "replay_actions")
+
     def _enqueue_sim(self, L, t, s0, s1):
         """Simulator step of [s0, s1) on the lane's side stream, behind the sampled actions of the main stream."""
         side = self._side(L)
         if L.side is not None:
             L.ev_fwd.record(self._main)
             side.wait_event(L.ev_fwd)
-        self.sim_step(t, s0=s0, s1=s1, stream=side.cuda_stream)
+        if self.log is not None:
+            # the same stream and the same event as the simulator step: behind the sampling of step t (and its context index lists),
+            # in front of the step; the existence of the row the step writes follows it, in front of the lane's next grouping
+            with torch.cuda.stream(side):
+                self.own_ctx_steps[t, s0:s1].copy_(self.own_ctx[s0:s1])
+                self.sampled_steps[t, s0:s1].copy_(self.act_now[s0:s1])
+            self._replay_actions(t, s0, s1, side.cuda_stream)
+            self.sim_step(t, self.act_f64, s0=s0, s1=s1, stream=side.cuda_stream, applied=self.applied_steps[t])
+            self._replay_latch(t + 1, s0, s1, side.cuda_stream)
+        else:
+            self.sim_step(t, s0=s0, s1=s1, stream=side.cuda_stream)
         if L.side is not None:
             L.ev_sim.record(side)
             L.sim_in_flight = True
@@ -713,6 +781,8 @@ class RolloutEngine:
         back: the scheduler (run) then queues another lane's step before this one blocks on its read-back."""
         T = self.dims.T
         t0 = 0
+        if self.log is not None and steps > 0:
+            self._replay_latch(0, lo, hi, self._side(L).cuda_stream)     # behind the reset (run: side waits for main; run_jobs: same stream)
         # pipelined jobs: the host never BLOCKS on a lane's read-back — a lane whose group counts are not back yet (its cached steps crawl
         # underneath the other lanes' full-row kernels) yields, so that the lanes in full-recompute steps keep the main stream fed
         poll = lane_idx is not None
@@ -915,8 +985,22 @@ class RolloutEngine:
     def step(self, t, noise_rtg=None, noise_act=None):
         """One closed-loop step: policy (grouping, contexts, two-pass model, sampling) then the simulator step.
         noise_rtg [S,N,3,R] / noise_act [S,N,V] float32 tensors (explicit Exp(1) noise) or None (in-kernel)."""
+        if self.log is None:
+            self.policy_step(t, noise_rtg, noise_act)
+            self.sim_step(t)
+            return
+        st = _lib.stream_ptr()
+        self._bind()
+        if t == 0:
+            self._replay_latch(0, 0, self.S, st)
         self.policy_step(t, noise_rtg, noise_act)
-        self.sim_step(t)
+        if self.lanes[0].side is not None:      # the second pass and the sampling ran on lane 0's side stream (_policy_chunks)
+            self._main.wait_stream(self.lanes[0].side)
+        self.own_ctx_steps[t].copy_(self.own_ctx)
+        self.sampled_steps[t].copy_(self.act_now)
+        self._replay_actions(t, 0, self.S, st)
+        self.sim_step(t, self.act_f64, applied=self.applied_steps[t])
+        self._replay_latch(t + 1, 0, self.S, st)
 
     def policy_step(self, t, noise_rtg=None, noise_act=None):
         """AutoregressivePolicy.predict for every scenario: writes hist_rtg[..., t, :], hist_tok[..., t], act_now."""
@@ -993,6 +1077,11 @@ class RolloutEngine:
 
     def results(self):
         self.check_finite()
-        return dict(tokens=self.hist_tok.cpu().numpy(), rtg_bins=self.hist_rtg.cpu().numpy(),
-                    states=self.hist_states.cpu().numpy(), coll=self.coll.cpu().numpy(),
-                    n_groups=self.groups_per_step.copy())
+        out = dict(tokens=self.hist_tok.cpu().numpy(), rtg_bins=self.hist_rtg.cpu().numpy(),
+                   states=self.hist_states.cpu().numpy(), coll=self.coll.cpu().numpy(),
+                   n_groups=self.groups_per_step.copy())
+        if self.log is not None:                # applied [S,N,steps,2] (accel, steer) and existence [S,N,steps+1] of the logged rollout
+            out["applied"] = self.applied_steps.permute(1, 2, 0, 3).contiguous().cpu().numpy()
+            out["existence"] = self.exist_hist.cpu().numpy()
+            out["sampled"] = self.sampled_steps.permute(1, 2, 0).contiguous().cpu().numpy()     # [S,N,steps] sampled tokens (act_now)
+        return out

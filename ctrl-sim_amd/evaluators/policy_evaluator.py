@@ -280,7 +280,10 @@ class PolicyEvaluator:
         What this route does NOT do: it never drives the `policy` OBJECT — no `policy.reset()` / `update_state()` / `predict()` calls, so
         the policy's own buffers (`policy.states`, `policy.actions`, `policy.rtgs`, ...) keep whatever an earlier per-scenario session
         left in them; read the rollouts from `last_vehicle_data_dict` / the metric dict, or set `cfg.eval.batched = False` for the
-        reference's per-scenario loop.  One RolloutEngine (workspace of `cfg.eval.batch_contexts` contexts) serves all chunks."""
+        reference's per-scenario loop.  One RolloutEngine (workspace of `cfg.eval.batch_contexts` contexts) serves all chunks.
+
+        `cfg.eval.device_replay = True` (default False) rolls every batch as ONE RolloutEngine.run() with the log attached: the per-step
+        NumPy work above runs on the device (_roll_batch_on_device, csrc/replay.hip) and the host reads the rollout back once."""
         from .. import discretize as dz
         from ..engine import RolloutEngine
         self.reset()
@@ -345,6 +348,8 @@ class PolicyEvaluator:
                                                      temperature=pol.action_temperature, nucleus=pol.nucleus_sampling,
                                                      top_p=pol.nucleus_threshold, model=pol.model.hip, lanes=1)
         eng.load_scenarios(scns, steps=T)
+        if bool(self.cfg.eval.get("device_replay", False)):
+            return self._roll_batch_on_device(eng, items, goal_dicts, gt, ctrl, N, dz, w, T, hsteps)
         dev = eng.device
         exist = np.zeros((S, N, T1))
         accel = np.zeros((S, N, T1))
@@ -405,8 +410,51 @@ class PolicyEvaluator:
         states = eng.hist_states.cpu().numpy()
         coll = eng.coll.cpu().numpy()
         speeds[:, :, T] = eng.phys[:, :, 16].cpu().numpy()
+        self._feed_batch(items, goal_dicts, states, coll, speeds, exist, accel, steer, gt, eng.hist_rtg[S - 1].cpu().numpy(), own_last, dz, w, T, N)
+
+    def _roll_batch_on_device(self, eng, items, goal_dicts, gt, ctrl, N, dz, w, T, hsteps):
+        """cfg.eval.device_replay: the batch as ONE RolloutEngine.run() — the log, the controlled vehicles and history_steps are attached to
+        the engine (engine.set_log) and the per-step decisions of the loop in _roll_batch (existence latch, policy or log, the inverse
+        bicycle model, the action-history tokens) run on the device between the engine's own launches (csrc/replay.hip), K/V-cached steps
+        included.  One read-back after the run, one check_finite() (which repeats the run with the range-safe operand split if the fast
+        one overflowed); statistics and `last_vehicle_data_dict` are fed exactly as by the step-by-step route."""
+        import time
+        S, T1 = len(items), T + 1
+        t_a = time.perf_counter()
+        eng.set_log(gt, ctrl, hsteps)
+        eng.run()
+        t_b = time.perf_counter()
+        try:
+            eng.check_finite()
+        except FloatingPointError as e:
+            raise FloatingPointError(f"{e} — batch of scenes {[int(getattr(it[0], 'index', -1)) for it in items]}") from None
+        t_c = time.perf_counter()
+        states = eng.hist_states.cpu().numpy()
+        coll = eng.coll.cpu().numpy()
+        speeds = eng.speed_hist.cpu().numpy()
+        applied = eng.applied_steps.cpu().numpy()                      # [T, S, N, 2]
+        exist = eng.exist_hist.cpu().numpy()
+        rtg_last = eng.hist_rtg[S - 1].cpu().numpy()
+        own_last = eng.own_ctx_steps[:, S - 1].cpu().numpy()           # [T, N]
+        accel = np.zeros((S, N, T1))
+        steer = np.zeros((S, N, T1))
+        accel[:, :, :T] = applied[..., 0].transpose(1, 2, 0)
+        steer[:, :, :T] = applied[..., 1].transpose(1, 2, 0)
+        t_d = time.perf_counter()
+        self.device_replay_timing = {"enqueue": t_b - t_a, "wait_and_check": t_c - t_b, "read_back": t_d - t_c}
+        # what this route read back, batch by batch: the arrays the statistics below are built from
+        rb = dict(states=states, coll=coll, speeds=speeds, accel=accel, steer=steer, exist=exist, gt=gt, controlled=ctrl.copy(),
+                  goal_dicts=goal_dicts, to_eval=[list(it[2]) for it in items], rtg_last=rtg_last, own_last=own_last)
+        if not hasattr(self, "device_replay_readback") or self.batched_scenes == 0:
+            self.device_replay_readback = []
+        self.device_replay_readback.append(rb)
+        self._feed_batch(items, goal_dicts, states, coll, speeds, exist, accel, steer, gt, rtg_last, own_last, dz, w, T, N)
+
+    def _feed_batch(self, items, goal_dicts, states, coll, speeds, exist, accel, steer, gt, rtg_last, own_last, dz, w, T, N):
+        """A rolled batch -> `last_vehicle_data_dict` (its last scene) and the running statistics (update_running_statistics on arrays)."""
+        S, T1 = len(items), T + 1
         self.last_vehicle_data_dict = self._vehicle_data_dict_of(S - 1, items[S - 1][0], goal_dicts[S - 1], states, coll, speeds, exist, accel, steer, gt,
-                                                                 eng.hist_rtg[S - 1].cpu().numpy(), own_last, dz, w, T)
+                                                                 rtg_last, own_last, dz, w, T)
         for k, (scn, gtd, to_eval) in enumerate(items):
             stt = np.zeros((N, T1, 8))
             stt[..., :5] = states[k, :, :, :5]

@@ -1,0 +1,75 @@
+"""Host form (NumPy float64) of the device-side log replay of csrc/replay.hip — what the tests compare the kernels with.
+
+A logged scene hands some vehicles to the policy (`controlled`, from step history_steps - 1) and replays every other vehicle's
+log through the inverse bicycle model (evaluators/policy_evaluator.py:534-540, evaluators/evaluator.py:160-193).  Two phases
+per step t, the same two the engine queues around its launches (include/ctrlsim.h: ctrlsim_replay_latch / _actions):
+
+  latch    existence of step t = the log's flag, 0 for good once it was 0     (policy_evaluator.py:118-121)
+  actions  (accel, steer), the simulator's `exists` flag and the action-history token of step t
+
+Arrays: log [..., T1 + 1, 6] = x, y, heading, speed, exist, length (zero rows past the end of a vehicle's log),
+controlled [...] bool, exist_t / exist_prev [...] float64.  Built from kinematics.bicycle_backward and discretize.*, the
+functions the step-by-step evaluator route calls.
+"""
+import numpy as np
+
+from . import discretize as dz
+from .kinematics import bicycle_backward
+
+
+def latch(log, t, exist_prev=None):
+    """Existence of step t: log[..., t, 4] at t = 0, log[..., t, 4] * (exist_prev != 0) afterwards."""
+    log = np.asarray(log, np.float64)
+    if t == 0:
+        return log[..., 0, 4].copy()
+    return log[..., t, 4] * (np.asarray(exist_prev, np.float64) != 0)
+
+
+def latch_all(log, T1):
+    """exist_hist [..., T1]: the latch run over rows 0 .. T1 - 1."""
+    log = np.asarray(log, np.float64)
+    out = np.zeros(log.shape[:-2] + (T1,))
+    for t in range(T1):
+        out[..., t] = latch(log, t, out[..., t - 1] if t else None)
+    return out
+
+
+def actions(log, controlled, exist_t, t, history_steps, heading, speed, act_now, dt, w):
+    """Step t for every vehicle -> (act [..., 2] float64, alive [...] bool, token [...] int32).
+    heading / speed: the vehicles' current heading (history row t) and speed, any float type (widened to float64 as the kernel does);
+    act_now: the sampled tokens, < 0 = no context answers for the vehicle; w = cfg.dataset.waymo."""
+    log = np.asarray(log, np.float64)
+    ctrl = np.asarray(controlled).astype(bool)
+    ex = np.asarray(exist_t, np.float64)
+    toks = np.asarray(act_now)
+    a = np.zeros(ctrl.shape)
+    st = np.zeros(ctrl.shape)
+    alive = np.ones(ctrl.shape, bool)
+    by_policy = ctrl & (t >= history_steps - 1)
+    # policy.act (autoregressive_policy.py:256-274)
+    und = dz.undiscretize_actions(np.maximum(toks, 0), w)
+    live = by_policy & (ex != 0)
+    a[live] = np.where(toks[live] >= 0, und[live][:, 0], 0.0)
+    st[live] = np.where(toks[live] >= 0, und[live][:, 1], 0.0)
+    alive[by_policy & (ex == 0)] = False
+    # apply_gt_action (evaluators/evaluator.py:160-193)
+    rep = ~by_policy
+    ok = rep & (log[..., t, 4] != 0) & (log[..., t + 1, 4] != 0) & ~((t > 0) & (ex == 0))
+    if ok.any():
+        nxt = np.concatenate([log[..., t + 1, :4][ok], log[..., t + 1, 5][ok][:, None]], 1)
+        zero = np.zeros(int(ok.sum()))
+        prev = np.stack([zero, zero, np.asarray(heading)[ok].astype(np.float64), np.asarray(speed)[ok].astype(np.float64)], 1)
+        a[ok], st[ok] = bicycle_backward(nxt, prev, dt)      # (the model reads heading and speed of the current state only)
+    alive[rep & ~ok] = False
+    act = np.stack([a, st], -1)
+    return act, alive, dz.discretize_actions(act, w).astype(np.int32)
+
+
+def token_margin(act, w):
+    """Distance of the scaled (accel, steer) of discretize_actions from the nearest half-integer, [..., 2]: where it is tiny, a last-bit
+    difference of the pair may round to the neighbouring bin."""
+    a = np.asarray(act, np.float64)
+    a0 = (np.clip(a[..., 0], w.min_accel, w.max_accel) - w.min_accel) / (w.max_accel - w.min_accel) * (w.accel_discretization - 1)
+    a1 = (np.clip(a[..., 1], w.min_steer, w.max_steer) - w.min_steer) / (w.max_steer - w.min_steer) * (w.steer_discretization - 1)
+    v = np.stack([a0, a1], -1)
+    return np.abs(v - np.floor(v) - 0.5)

@@ -106,6 +106,35 @@ int ctrlsim_sim_step_expert(int S, int N, int E, const int* act_tok, const doubl
                             uint8_t* coll, double* applied, int t, int Tmax1, float dt, float* contact_state,
                             const float* expert, hipStream_t stream);
 
+/* ---- log replay of partially controlled scenes -----------------------------------------------------------------
+ * Replaces the per-step host work of a logged evaluation (evaluators/policy_evaluator.py:514-557): which vehicles the policy
+ * drives (vehicles_to_evaluate from t >= history_steps - 1, :534-540) and the log-replay action of every other vehicle.
+ * log [S,N,T1+1,6] f64 = logged x, y, heading, speed, exist, length per step, zero rows past the end of a vehicle's log (one row
+ * more than the rollout has states: step t looks at row t + 1); controlled [S,N] u8 = vehicles handed to the policy;
+ * exist_hist [S,N,T1] f64 = existence per step, latched.
+ * ctrlsim_replay_latch — the existence bookkeeping of update_vehicle_data_dict (evaluators/policy_evaluator.py:118-121):
+ * exist_hist[..,t] = log[..,t,4] (t = 0) or log[..,t,4] * (exist_hist[..,t-1] != 0), also written to hist_states[..,t,7]; call it
+ * after the simulator wrote row t (ctrlsim_sim_init for t = 0) and before ctrlsim_group_build of step t, and once for row
+ * T1 - 1 after the last step.  speed_hist (nullable, [S,N,T1] f32) [..,t] <- phys[..,16], the speed veh.getSpeed() returns at
+ * step t (the same function's state read-back; phys may be NULL without it).
+ * ctrlsim_replay_actions — after the action sampling of step t, before ctrlsim_sim_step.  A controlled vehicle from
+ * t >= history_steps - 1 takes its sampled token act_now (AutoregressivePolicy.act, policies/autoregressive_policy.py:256-274;
+ * undiscretize_actions, datasets/rl_waymo/dataset.py:322-338): (0, 0) for a token < 0 (no context answers for it), (0, 0) and
+ * exists = 0 (parked by the simulator) once exist_hist[..,t] is 0.  Every other vehicle replays its log
+ * (Evaluator.apply_gt_action, evaluators/evaluator.py:160-193): valid iff log rows t and t + 1 exist and the vehicle is not
+ * latched out (t > 0 and exist_hist[..,t] == 0); then BicycleModel.backward (nocturne/bicycle_model.py:51-109, angle_sub of
+ * utils/geometry.py:3-12) from the heading of hist_states row t and the speed phys[..,16] to x, y, heading, speed, length of log
+ * row t + 1, steer clipped to +-0.7 and NaN -> 0; else (0, 0) and exists = 0.  Outputs: act_f64 [S,N,2] (what ctrlsim_sim_step
+ * takes), exists [S,N], hist_tok[S,N,Tmax][..,t] = discretize_actions of the pair (dataset.py:365-380; np.round = round half to
+ * even; the identity on a sampled token).  disc6 (host) as for ctrlsim_sim_step.  float64, the host expressions operation by
+ * operation. */
+int ctrlsim_replay_latch(int S, int N, int t, int T1, const double* log, const float* phys, double* exist_hist, float* hist_states,
+                         float* speed_hist, hipStream_t stream);
+int ctrlsim_replay_actions(int S, int N, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
+                           const uint8_t* controlled, const double* exist_hist, const float* hist_states, const float* phys,
+                           const int* act_now, const double* disc6, double* act_f64, uint8_t* exists, int* hist_tok,
+                           hipStream_t stream);
+
 /* ---- focal grouping + context tensors ------------------------------------------------------------------------
  * Replaces AutoregressivePolicy.get_data (policies/autoregressive_policy.py:51-165) with
  * RLWaymoDataset.select_relevant_agents / normalize_scene (datasets/rl_waymo/dataset.py:278-319,390-428). */

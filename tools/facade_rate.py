@@ -1,7 +1,13 @@
 """Throughput of the PLUGIN route (BASELINE configs[0]'s analogue): PolicyEvaluator -> AutoregressivePolicy.predict / act -> Simulation.step,
 one scenario at a time through the reference-shaped surface (per step: the history mirrored to the device, one policy step, a
 device -> host read of the sampled actions, one simulator step, a read of the new state row).  Plumbing, not the product's fast path
-(RolloutEngine, bench.py) — this gives it a number.   usage: python tools/facade_rate.py [scenarios=3] [agents=8] [steps=20] [batched]"""
+(RolloutEngine, bench.py) — this gives it a number.
+usage: python tools/facade_rate.py [scenarios=3] [agents=8] [steps=20] [loop | batched | device] [repeats=1] [history_steps=1]
+  loop     the per-scenario loop (default)
+  batched  every scene of the evaluation in one RolloutEngine batch, stepped from the host (one policy_step / NumPy / sim_step round per step)
+  device   the same batch as ONE RolloutEngine.run() with the log attached (cfg.eval.device_replay: csrc/replay.hip decides policy-or-log,
+           computes the replay actions and latches existence on the device)
+Every repeat is a complete evaluate_policy() and prints its own rate (profiles/device_replay_rate.md records them)."""
 import sys
 import time
 
@@ -15,7 +21,11 @@ from ctrlsim_amd.evaluators import PolicyEvaluator
 S = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 20
-cfg = spec.make_cfg(nocturne__steps=T, nocturne__history_steps=1)
+MODE = sys.argv[4] if len(sys.argv) > 4 else "loop"
+assert MODE in ("loop", "batched", "device"), MODE
+REPEATS = int(sys.argv[5]) if len(sys.argv) > 5 else 1
+HS = int(sys.argv[6]) if len(sys.argv) > 6 else 1
+cfg = spec.make_cfg(nocturne__steps=T, nocturne__history_steps=HS)
 cfg.eval["synthetic"] = dict(num_scenarios=S + 1, n_agents=N, n_polylines=200, seed=7, extent=60.0)
 cfg.eval.num_files_to_evaluate = (S + 1) * cfg.eval.partitions
 model = CtRLSim(cfg, seed=0, device="cuda:0")
@@ -27,19 +37,26 @@ policy = AutoregressivePolicy(cfg=cfg, model_path="", model=model, use_rtg=pol.u
                               tilt_dict={"tilt": True, "goal_tilt": 0, "veh_veh_tilt": 0, "veh_edge_tilt": 0}, name=pol.model,
                               action_temperature=pol.action_temperature, nucleus_sampling=pol.nucleus_sampling,
                               nucleus_threshold=pol.nucleus_threshold)
-BATCHED = len(sys.argv) > 4 and sys.argv[4] == "batched"      # round 5: every scene of the evaluation in one RolloutEngine batch (the default of evaluate_policy)
+BATCHED = MODE != "loop"                  # round 5: every scene of the evaluation in one RolloutEngine batch (the default of evaluate_policy)
 cfg.eval["batched"] = BATCHED
-cfg1 = spec.make_cfg(nocturne__steps=T, nocturne__history_steps=1)
+cfg.eval["device_replay"] = MODE == "device"
+cfg1 = spec.make_cfg(nocturne__steps=T, nocturne__history_steps=HS)
 cfg1.eval["batched"] = BATCHED
+cfg1.eval["device_replay"] = MODE == "device"
 cfg1.eval["synthetic"] = dict(num_scenarios=1, n_agents=N, n_polylines=200, seed=7, extent=60.0)
 cfg1.eval.num_files_to_evaluate = cfg1.eval.partitions
 PolicyEvaluator(cfg1, policy).evaluate_policy()              # warm-up: first launches, allocations
-t0 = time.perf_counter()
-EV = PolicyEvaluator(cfg, policy)
-m, _ = EV.evaluate_policy()
-el = time.perf_counter() - t0
 n_scn = S + 1
-print(f"plugin route ({'batched: one RolloutEngine batch' if BATCHED else 'per-scenario loop'}): {n_scn} scenarios x {N} vehicles x {T} steps, full model, in {el:.2f} s = {n_scn * N * T / el:.0f} agent-steps/s "
-      f"({el / (n_scn * T) * 1e3:.1f} ms per scenario-step)")
-if BATCHED:
-    print("  batched route, seconds by phase of the step loop:", {k: round(v, 3) for k, v in getattr(EV, "batched_timing", {}).items()})
+route = {"loop": "per-scenario loop", "batched": "batched: one RolloutEngine batch, host-driven steps",
+         "device": "device replay: one RolloutEngine.run() with the log attached"}[MODE]
+for rep in range(REPEATS):
+    t0 = time.perf_counter()
+    EV = PolicyEvaluator(cfg, policy)
+    m, _ = EV.evaluate_policy()
+    el = time.perf_counter() - t0
+    print(f"plugin route ({route}): {n_scn} scenarios x {N} vehicles x {T} steps, history_steps {HS}, full model, in {el:.3f} s = "
+          f"{n_scn * N * T / el:.0f} agent-steps/s ({el / (n_scn * T) * 1e3:.2f} ms per scenario-step)")
+    if MODE == "batched":
+        print("  batched route, seconds by phase of the step loop:", {k: round(v, 3) for k, v in getattr(EV, "batched_timing", {}).items()})
+    if MODE == "device":
+        print("  device-replay route, seconds by phase:", {k: round(v, 3) for k, v in getattr(EV, "device_replay_timing", {}).items()})
