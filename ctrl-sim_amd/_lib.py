@@ -83,6 +83,8 @@ SIGNATURES = {
     "ctrlsim_sim_set_position": (I, [I, I, P, P, P]),
     "ctrlsim_replay_latch": (I, [I, I, I, I, P, P, P, P, P, P]),
     "ctrlsim_replay_actions": (I, [I, I, I, I, I, I, D, P, P, P, P, P, P, P, P, P, P, P]),
+    "ctrlsim_replay_latch_views": (I, [I, I, I, I, I, P, P, P, P, P, P, P]),
+    "ctrlsim_replay_actions_views": (I, [I, I, I, I, I, I, I, D, P, P, P, P, P, P, P, P, P, P, P, P]),
     "ctrlsim_group_build": (I, [I, I, I, I, I, I, D, P, P, I, P, P, P, P, P, P, P, P, P]),
     "ctrlsim_groups_changed": (I, [I, I, P, P, P, P, P, P, P, P]),
     "ctrlsim_group_size_hist": (I, [I, I, P, P, I, P, P, P]),

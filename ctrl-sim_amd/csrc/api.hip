@@ -287,6 +287,17 @@ int ctrlsim_replay_actions(int S, int N, int t, int T1, int Tmax, int history_st
   return launch_replay_actions(S, N, t, T1, Tmax, history_steps, dt, log, controlled, exist_hist, hist_states, phys, act_now, disc6,
                                act_f64, exists, hist_tok, st);
 }
+int ctrlsim_replay_latch_views(int S, int N, int R, int t, int T1, const double* log, const float* phys, double* exist_hist,
+                               float* hist_states, float* speed_hist, float* view_states, hipStream_t st) {
+  return launch_replay_latch_views(S, N, R, t, T1, log, phys, exist_hist, hist_states, speed_hist, view_states, st);
+}
+int ctrlsim_replay_actions_views(int S, int N, int R, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
+                                 const int* role, const double* exist_hist, const float* hist_states, const float* phys,
+                                 const int* act_now, const double* disc6, double* act_f64, uint8_t* exists, int* hist_tok,
+                                 int* view_tok, hipStream_t st) {
+  return launch_replay_actions_views(S, N, R, t, T1, Tmax, history_steps, dt, log, role, exist_hist, hist_states, phys, act_now, disc6,
+                                     act_f64, exists, hist_tok, view_tok, st);
+}
 int ctrlsim_group_build(int S, int N, int A, int T, int t, int Tmax1, double dist_thresh, const float* hist_states,
                         const int* eval_order, int has_roads, uint64_t* persist, int* n_groups, int* grp_focal,
                         uint64_t* grp_ids, uint64_t* grp_members, int* own_g, int* mem_g, uint8_t* tilted, hipStream_t st) {

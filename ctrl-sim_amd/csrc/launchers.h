@@ -119,6 +119,12 @@ int launch_replay_actions(int S, int N, int t, int T1, int Tmax, int history_ste
                           const unsigned char* controlled, const double* exist_hist, const float* hist_states, const float* phys,
                           const int* act_now, const double* disc6, double* act_f64, unsigned char* exists, int* hist_tok,
                           hipStream_t st);
+int launch_replay_latch_views(int S, int N, int R, int t, int T1, const double* log, const float* phys, double* exist_hist,
+                              float* hist_states, float* speed_hist, float* view_states, hipStream_t st);
+int launch_replay_actions_views(int S, int N, int R, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
+                                const int* role, const double* exist_hist, const float* hist_states, const float* phys,
+                                const int* act_now, const double* disc6, double* act_f64, unsigned char* exists, int* hist_tok,
+                                int* view_tok, hipStream_t st);
 
 // ---- sample.hip
 int launch_sample_rtg(const float* rtg_logits, int A, int R, const int* own_ctx, const int* own_slot, const int* ctx_row0,

@@ -188,7 +188,21 @@ class _Lane:
         self.pending = (0, 0, False)                             # scenario range (+ compare flag) of the read-back in flight
 
 
+class _OwnView:
+    """The policy side of an engine whose scenes have ONE role (set_roles with R = 1): the scene is its own view — every tensor is the
+    engine's — except for the role's processing order and tilt rows, which live here and never touch the engine's own."""
+
+    def __init__(self, eng, eval_order, tilt_scn):
+        self._eng, self.eval_order, self.tilt_scn = eng, eval_order, tilt_scn
+
+    def __getattr__(self, name):
+        return getattr(self._eng, name)
+
+
 class RolloutEngine:
+    MAX_ROLES = 4                               # set_roles; include/ctrlsim.h: CTRLSIM_MAX_ROLES
+    _SCENE_INPUTS = ("scenario_id", "goals", "types", "roads", "rtypes")    # per-scene inputs of the policy kernels: one copy per role view
+
     def __init__(self, cfg, weights: dict, device="cuda:0", max_ctx=256, seed=0, tilt=(0.0, 0.0, 0.0),
                  temperature=None, nucleus=None, top_p=None, kinematic=False, model=None, use_cache=True, contacts=True,
                  lanes=1, compact=True, split="auto", sizes=None, options=None):
@@ -299,6 +313,10 @@ class RolloutEngine:
         self._main = torch.cuda.current_stream(self.device)
         self.S = 0
         self.log = None                         # set_log: logs of the loaded scenarios (partially controlled scenes)
+        # set_roles: policy roles per vehicle.  _pv is the POLICY SIDE the grouping, context, forward and sampling launches take their
+        # tensors from (`v = self._pv` in those methods): the engine itself — one row per scenario — or, with roles, the scenes' policy
+        # views (R rows per scene).  The simulator side (bodies, contacts, collisions, the log) is always the engine's own [S, ...]
+        self.role, self.R, self._pv = None, 1, self
 
     def _bind(self):
         _lib.check(self.lib.ctrlsim_bind(int(self.scheme), self.guard.data_ptr()), "bind")
@@ -386,31 +404,33 @@ class RolloutEngine:
             self.dt_ledger = z(S, N, 10, dt=torch.float64)
             self.dt_rtg_raw = z(S, N, Tmax, 3, dt=torch.float64)
             self.dt_init_rtg = None                          # [S,N,3] float64 tensor, or None = (10, 90, 90) (max_return)
-        self.act_now = z(S, N, dt=torch.int32)
         self.applied = z(S, N, Tmax, 2, dt=torch.float64)
-        self.persist = z(S, N, dt=torch.int64)
-        self.n_groups = z(S, dt=torch.int32)
-        nb = len(self.sizes)
-        self.size_hist = z(S, nb, dt=torch.int32)
-        self.ctx_of_group = z(S, N, dt=torch.int32)
+        for k, a in self._policy_side(S).items():
+            setattr(self, k, a)
         for L in self.lanes:
-            L.host_hist = torch.zeros(S, nb, dtype=torch.int32).pin_memory()
-        self.grp_focal = z(S, N, dt=torch.int32)
-        self.grp_ids = z(S, N, dt=torch.int64)
-        self.grp_members = z(S, N, dt=torch.int64)
-        # snapshot of the focal groups a chunk's K/V cache was built for (ctrlsim_groups_changed)
-        self.ref_n, self.ref_focal, self.ref_ids = z(S, dt=torch.int32), z(S, N, dt=torch.int32), z(S, N, dt=torch.int64)
-        self.own_g, self.mem_g = z(S, N, dt=torch.int32), z(S, N, dt=torch.int32)
-        self.tilted = z(S, N, dt=torch.uint8)
-        self.own_ctx, self.own_slot = z(S, N, dt=torch.int32), z(S, N, dt=torch.int32)
-        self.mem_ctx, self.mem_slot = z(S, N, dt=torch.int32), z(S, N, dt=torch.int32)
+            L.host_hist = torch.zeros(S, len(self.sizes), dtype=torch.int32).pin_memory()
         self.ctx_base = z(S, dt=torch.int32)
         self._zero_rtg_row = torch.tensor(self.zero_rtg, dtype=torch.int32, device=dev)
-        self.groups_per_step = np.zeros((self.steps, S), np.int32)
         self.guard.zero_()
         self._unchecked = []
         self.log = None                         # a new batch starts without a log (set_log)
+        self.role, self.R, self._pv = None, 1, self     # ... and without roles (set_roles), whose views held their own order and tilt rows
         self.reset()
+
+    def _policy_side(self, rows):
+        """The working tensors of the policy side for `rows` rows — the loaded scenarios (load_scenarios) or their role views
+        (set_roles): a tensor added here exists on both.  Inputs (_SCENE_INPUTS, eval_order, tilt_scn) and the state / action / RTG
+        histories are not working tensors: the caller provides them."""
+        N, dev = self.N, self.device
+        z = lambda *sh, dt=torch.int32: torch.zeros(*sh, dtype=dt, device=dev)
+        i64 = torch.int64
+        return dict(act_now=z(rows, N), persist=z(rows, N, dt=i64), n_groups=z(rows), size_hist=z(rows, len(self.sizes)),
+                    ctx_of_group=z(rows, N), grp_focal=z(rows, N), grp_ids=z(rows, N, dt=i64), grp_members=z(rows, N, dt=i64),
+                    # snapshot of the focal groups a chunk's K/V cache was built for (ctrlsim_groups_changed)
+                    ref_n=z(rows), ref_focal=z(rows, N), ref_ids=z(rows, N, dt=i64),
+                    own_g=z(rows, N), mem_g=z(rows, N), tilted=z(rows, N, dt=torch.uint8),
+                    own_ctx=z(rows, N), own_slot=z(rows, N), mem_ctx=z(rows, N), mem_slot=z(rows, N),
+                    groups_per_step=np.zeros((self.steps, rows), np.int32))
 
     def set_log(self, log, controlled, history_steps=1):
         """Attach the logs of the loaded scenarios: from now on run() / run_jobs() / step() roll them as PARTIALLY CONTROLLED scenes
@@ -418,7 +438,9 @@ class RolloutEngine:
         history_steps - 1 on, every other vehicle (and the controlled ones before that step) replays its log through the inverse bicycle
         model, and existence follows the log, latched at 0.  log [S,N,steps+2,6] float64 = x, y, heading, speed, exist, length per step,
         zero rows past the end of a vehicle's log.  reset() keeps the log; set_log(None, None) detaches it (load_scenarios does too).
-        Call it on freshly loaded / reset scenarios: the rollout starts at step 0."""
+        Call it on freshly loaded / reset scenarios: the rollout starts at step 0.  Several policies in one scene: set_roles, on top of
+        the log (attaching or detaching a log detaches the roles)."""
+        self.set_roles(None)                   # roles belong to the log they were set on
         if log is None:
             if self.log is not None:
                 self.exists.fill_(1)            # the replay kernels' parked flags go with the log
@@ -431,6 +453,7 @@ class RolloutEngine:
         assert tuple(log.shape) == (S, N, T1 + 1, 6) and tuple(ctrl.shape) == (S, N), "log [S,N,steps+2,6], controlled [S,N]"
         assert not self.dims.VARIANT or not self.device_ledger, "the Decision-Transformer reward ledger keeps the step-by-step route"
         self.log, self.controlled, self.history_steps = log, ctrl, int(history_steps)
+        self._log_controlled = ctrl
         z = lambda *sh, dt: torch.zeros(*sh, dtype=dt, device=dev)
         self.exist_hist = z(S, N, T1, dt=torch.float64)
         self.speed_hist = z(S, N, T1, dt=torch.float32)
@@ -439,6 +462,84 @@ class RolloutEngine:
         self.own_ctx_steps = z(self.steps, S, N, dt=torch.int32)            # own_ctx of every step (>= 0: a context answers for the vehicle)
         self.sampled_steps = z(self.steps, S, N, dt=torch.int32)            # act_now of every step: the sampled tokens, < 0 = nobody answers
         self.exists.fill_(1)
+        return self
+
+    def set_roles(self, role, tilts=None):
+        """Policy ROLES per vehicle on top of the attached log (evaluators/planner_adversary_evaluator.py:458-546: a planner drives the
+        ego, an adversary another vehicle, each with its own tilt, focal groups, persisted context membership and RTG history, over a
+        common state and applied-action history).  role [S,N] integer: -1 = the vehicle replays its log, r in 0 .. R-1 = policy role r
+        drives it from step history_steps - 1 on (`controlled` becomes role >= 0); tilts [R,3] = (goal, veh_veh, veh_edge) of every role,
+        R <= 4.  run() / run_jobs() / step() then roll every scene with R policy VIEWS: rows s * R + r of the policy-side tensors
+        (eval_order = the role's vehicles by decreasing logged length, persist, the group arrays, hist_rtg, act_now, tilt, and copies of
+        the scene's goals, map, state and action history, kept equal to the scene's by csrc/replay.hip's _views kernels) — ordinary
+        scenarios for the grouping, context, forward and sampling kernels, with the scene's id in the noise key.  The simulator side
+        (phys, contacts, collisions, the log, hist_states / hist_tok of the scene) stays [S, ...].  With R = 1 the scene is its own view.
+        Not for the Decision-Transformer variant (its RTG rows are the scene's, fed by the reward ledger).
+        reset() keeps the roles; set_roles(None), set_log and load_scenarios detach them.  Call it on freshly loaded / reset scenarios."""
+        dev = self.device
+        if role is None:
+            if self.role is None:
+                return self
+            if self.R > 1:                      # the per-step records go back to one row per scenario
+                self.own_ctx_steps = torch.zeros(self.steps, self.S, self.N, dtype=torch.int32, device=dev)
+                self.sampled_steps = torch.zeros(self.steps, self.S, self.N, dtype=torch.int32, device=dev)
+            self.controlled = self._log_controlled
+            self.role, self.R, self._pv = None, 1, self
+            self.exists.fill_(1)
+            return self
+        if self.log is None:
+            raise RuntimeError("set_roles needs the scenes' log: call set_log(log, controlled, history_steps) first — a vehicle without a "
+                               "role replays its log, and the roles take over at step history_steps - 1")
+        if self.dims.VARIANT == 3:
+            # (device ledger or host-fed: the Decision Transformer's RTG rows are written per scene, not per policy view)
+            raise RuntimeError("set_roles: the Decision-Transformer reward ledger keeps the step-by-step route (as set_log) — its RTG rows, "
+                               "fed by the device ledger or by the host, belong to the scene and would not reach the roles' views")
+        self.set_roles(None)
+        S, N = self.S, self.N
+        role_h = (role.cpu().numpy() if torch.is_tensor(role) else np.asarray(role)).astype(np.int64)
+        tilts = np.ascontiguousarray(np.asarray(tilts, np.float64))
+        if tilts.ndim != 2 or tilts.shape[1] != 3 or tilts.shape[0] < 1:
+            raise ValueError("set_roles: tilts must be [R,3] = (goal, veh_veh, veh_edge) per role")
+        R = tilts.shape[0]
+        if R > self.MAX_ROLES:
+            raise ValueError(f"set_roles: {R} roles — at most {self.MAX_ROLES} policy roles per scene are supported")
+        if role_h.shape != (S, N):
+            raise ValueError(f"set_roles: role must be [S,N] = {(S, N)}, got {role_h.shape}")
+        if role_h.size and (role_h.max() >= R or role_h.min() < -1):
+            raise ValueError(f"set_roles: role index {int(role_h.max() if role_h.max() >= R else role_h.min())} outside -1 .. {R - 1} "
+                             f"(tilts holds {R} roles)")
+        # a view's processing order: its role's vehicles by decreasing logged length (AutoregressivePolicy._open_session)
+        lengths = self.log[..., 4].sum(-1).cpu().numpy().astype(np.int64)
+        eo = -np.ones((S, R, N), np.int32)
+        for s_ in range(S):
+            for r in range(R):
+                mine = np.nonzero(role_h[s_] == r)[0]
+                if len(mine):
+                    eo[s_, r, :len(mine)] = mine[np.argsort(lengths[s_, mine])[::-1]]
+        self.role = torch.from_numpy(role_h.astype(np.int32)).to(dev)
+        self.controlled = (self.role >= 0).to(torch.uint8)
+        self.R = R
+        tilt_rows = torch.from_numpy(np.tile(tilts, (S, 1))).to(dev)           # row s * R + r = role r's triple
+        eo_d = torch.from_numpy(eo.reshape(S * R, N)).to(dev)
+        if R == 1:                              # both sides are the same tensors; only the order and the tilt are the role's
+            self._pv = _OwnView(self, eo_d, tilt_rows)
+            return self
+        from types import SimpleNamespace
+        Tmax, V = self.steps, S * R
+        z = lambda *sh, dt=torch.float32: torch.zeros(*sh, dtype=dt, device=dev)
+        per_view = lambda a: a.repeat_interleave(R, dim=0).contiguous()
+        i32 = torch.int32
+        # (a plain namespace: a policy-side name it lacks is an AttributeError in the first launch, not the scene's tensor)
+        v = self._pv = SimpleNamespace(S=V, eval_order=eo_d, tilt_scn=tilt_rows, hist_states=z(V, N, Tmax + 1, 8),
+                                       hist_tok=z(V, N, Tmax, dt=i32), hist_rtg=z(V, N, Tmax, 3, dt=i32),
+                                       **{k: per_view(getattr(self, k)) for k in self._SCENE_INPUTS}, **self._policy_side(V))
+        v.hist_tok.fill_(ZERO_ACTION_TOKEN)
+        v.hist_rtg.copy_(self._zero_rtg_row.expand_as(v.hist_rtg))
+        self.own_ctx_steps = z(self.steps, V, N, dt=i32)        # per view and step
+        self.sampled_steps = z(self.steps, V, N, dt=i32)
+        for L in self.lanes:
+            if L.host_hist.shape[0] < V:
+                L.host_hist = torch.zeros(V, len(self.sizes), dtype=torch.int32).pin_memory()
         return self
 
     def reset(self, s0=0, s1=None):
@@ -460,8 +561,17 @@ class RolloutEngine:
             self.exist_hist[sl].zero_()
             self.speed_hist[sl].zero_()
             self.applied_steps[:, sl].zero_()
-            self.own_ctx_steps[:, sl].zero_()
-            self.sampled_steps[:, sl].zero_()
+            vl = slice(s0 * self.R, s1 * self.R)
+            self.own_ctx_steps[:, vl].zero_()
+            self.sampled_steps[:, vl].zero_()
+            if self.R > 1:
+                # the role views of these scenes: empty histories (the latch of step 0 brings the scene's first row), no persisted
+                # context membership
+                v = self._pv
+                v.hist_states[vl].zero_()
+                v.hist_tok[vl].fill_(ZERO_ACTION_TOKEN)
+                v.hist_rtg[vl].copy_(self._zero_rtg_row.expand_as(v.hist_rtg[vl]))
+                v.persist[vl].zero_()
         p = _lib.ptr
         _lib.check(self.lib.ctrlsim_sim_init(s1 - s0, self.N, self.E, p(self.init_pose[sl]), p(self.size[sl]), p(self.edges[sl]),
                                              p(self.exists[sl]), p(self.phys[sl]), p(self.hist_states[sl]), p(self.coll[sl]),
@@ -469,12 +579,19 @@ class RolloutEngine:
                                              st), "sim_init")
 
     # ------------------------------------------------------------------ chunk plan
-    def _chunks(self, hist, base=0):
+    def _chunks(self, hist, base=0, rows_per=1):
         """Cut scenarios base .. base+len(hist) into model batches.  hist [n, classes] = focal groups per scenario and size
         class.  A batch must fit the lane's workspace (compact contexts are cheaper: bytes per context by class) and its
         context buffers (ctx_cap contexts); batches are balanced (a short last batch costs a whole set of launches).
-        -> [(s0, s1, counts_per_class)]."""
+        -> [(s0, s1, counts_per_class)].  rows_per: policy rows behind one row of hist (the role views of a scene, planned as one)."""
         hist = np.asarray(hist, np.int64).reshape(-1, len(self.sizes))
+        R = self.R
+        if R > 1 and rows_per == 1:
+            # role views: hist and base are VIEW rows.  A scene's views stay in one batch (its simulator step follows the sampling of
+            # all of them), so the plan is made over scenes — the sums of their views — and handed back in view rows
+            assert base % R == 0 and len(hist) % R == 0
+            plan = self._chunks(hist.reshape(-1, R, hist.shape[1]).sum(1), base // R, rows_per=R)
+            return [(a * R, b * R, counts) for a, b, counts in plan]
         cost = hist @ np.asarray(self._bpc)                       # workspace bytes per scenario
         nctx = hist.sum(1)
         cap_b = self._ws_cap - self._ws_fixed - (1 << 20)
@@ -486,7 +603,7 @@ class RolloutEngine:
         lim_c = min(cap_c, nctx.sum() / n + (nctx.max() if len(nctx) else 0))
         chunks, s0, acc_b, acc_c = [], 0, 0.0, 0
         for s in range(len(hist)):
-            if acc_b + cost[s] > lim_b or acc_c + nctx[s] > lim_c or s - s0 >= 4095:
+            if acc_b + cost[s] > lim_b or acc_c + nctx[s] > lim_c or s - s0 >= 4095 // rows_per:
                 chunks.append((base + s0, base + s, hist[s0:s].sum(0)))
                 s0, acc_b, acc_c = s, 0.0, 0
             acc_b += cost[s]
@@ -532,15 +649,16 @@ class RolloutEngine:
                                         p(self.contact_state[sl]) if self.contact_state is not None else None, st), "sim_step")
 
     def _group_build(self, t, s0=0, s1=None, stream=None):
+        v = self._pv
         lib, p, d = self.lib, _lib.ptr, self.dims
         st = _lib.stream_ptr() if stream is None else stream
-        s1 = self.S if s1 is None else s1
+        s1 = v.S if s1 is None else s1
         sl = slice(s0, s1)
         _lib.check(lib.ctrlsim_group_build(s1 - s0, self.N, d.A, d.T, t, self.steps + 1, float(self.w.agent_dist_threshold),
-                                           p(self.hist_states[sl]), p(self.eval_order[sl]), 1 if self.P_all > 0 else 0,
-                                           p(self.persist[sl]), p(self.n_groups[sl]), p(self.grp_focal[sl]),
-                                           p(self.grp_ids[sl]), p(self.grp_members[sl]), p(self.own_g[sl]), p(self.mem_g[sl]),
-                                           p(self.tilted[sl]), st), "group_build")
+                                           p(v.hist_states[sl]), p(v.eval_order[sl]), 1 if self.P_all > 0 else 0,
+                                           p(v.persist[sl]), p(v.n_groups[sl]), p(v.grp_focal[sl]),
+                                           p(v.grp_ids[sl]), p(v.grp_members[sl]), p(v.own_g[sl]), p(v.mem_g[sl]),
+                                           p(v.tilted[sl]), st), "group_build")
 
     def _side(self, L):
         return L.side if L.side is not None else self._main
@@ -548,6 +666,7 @@ class RolloutEngine:
     def _enqueue_groups(self, L, t, s0, s1, compare=False):
         """Side stream of lane L: focal groups of step t for scenarios [s0, s1), (compare) the changed-vs-snapshot flag, the
         asynchronous read-back of the group counts per size class (+ flag), then L.ev_ready."""
+        v = self._pv
         side = self._side(L)
         sl = slice(s0, s1)
         self._group_build(t, s0, s1, side.cuda_stream)
@@ -555,14 +674,14 @@ class RolloutEngine:
             if compare:
                 L.flag.zero_()
                 p = _lib.ptr
-                _lib.check(self.lib.ctrlsim_groups_changed(s1 - s0, self.N, p(self.n_groups[sl]), p(self.grp_focal[sl]),
-                                                           p(self.grp_ids[sl]), p(self.ref_n[sl]), p(self.ref_focal[sl]),
-                                                           p(self.ref_ids[sl]), p(L.flag), side.cuda_stream), "groups_changed")
+                _lib.check(self.lib.ctrlsim_groups_changed(s1 - s0, self.N, p(v.n_groups[sl]), p(v.grp_focal[sl]),
+                                                           p(v.grp_ids[sl]), p(v.ref_n[sl]), p(v.ref_focal[sl]),
+                                                           p(v.ref_ids[sl]), p(L.flag), side.cuda_stream), "groups_changed")
                 L.host_flag.copy_(L.flag, non_blocking=True)
-            _lib.check(self.lib.ctrlsim_group_size_hist(s1 - s0, self.N, _lib.ptr(self.n_groups[sl]), _lib.ptr(self.grp_ids[sl]),
-                                                        len(self.sizes), self._sizes_c, _lib.ptr(self.size_hist[sl]),
+            _lib.check(self.lib.ctrlsim_group_size_hist(s1 - s0, self.N, _lib.ptr(v.n_groups[sl]), _lib.ptr(v.grp_ids[sl]),
+                                                        len(self.sizes), self._sizes_c, _lib.ptr(v.size_hist[sl]),
                                                         side.cuda_stream), "group_size_hist")
-            L.host_hist[:s1 - s0].copy_(self.size_hist[sl], non_blocking=True)
+            L.host_hist[:s1 - s0].copy_(v.size_hist[sl], non_blocking=True)
             L.ev_ready.record(side)
         L.pending = (s0, s1, compare)
 
@@ -574,15 +693,22 @@ class RolloutEngine:
         return L.host_hist.numpy()[:s1 - s0].copy(), bool(compare and int(L.host_flag[0]) != 0)
 
     def _snapshot_groups(self, L, s0, s1):
+        v = self._pv
         side, sl = self._side(L), slice(s0, s1)
         with torch.cuda.stream(side):
-            self.ref_n[sl].copy_(self.n_groups[sl])
-            self.ref_focal[sl].copy_(self.grp_focal[sl])
-            self.ref_ids[sl].copy_(self.grp_ids[sl])
+            v.ref_n[sl].copy_(v.n_groups[sl])
+            v.ref_focal[sl].copy_(v.grp_focal[sl])
+            v.ref_ids[sl].copy_(v.grp_ids[sl])
 
     def _replay_latch(self, t, s0, s1, st):
         """Log attached: existence of row t for [s0, s1) (ctrlsim_replay_latch), behind the simulator step that wrote the row."""
         p, sl = _lib.ptr, slice(s0, s1)
+        if self.role is not None:               # roles: the row also goes into the scene's views (ctrlsim_replay_latch_views)
+            R, v = self.R, self._pv
+            _lib.check(self.lib.ctrlsim_replay_latch_views(s1 - s0, self.N, R, t, self.steps + 1, p(self.log[sl]), p(self.phys[sl]),
+                                                           p(self.exist_hist[sl]), p(self.hist_states[sl]), p(self.speed_hist[sl]),
+                                                           p(v.hist_states[s0 * R:s1 * R]), st), "replay_latch_views")
+            return
         _lib.check(self.lib.ctrlsim_replay_latch(s1 - s0, self.N, t, self.steps + 1, p(self.log[sl]), p(self.phys[sl]),
                                                  p(self.exist_hist[sl]), p(self.hist_states[sl]), p(self.speed_hist[sl]), st),
                    "replay_latch")
@@ -591,6 +717,15 @@ class RolloutEngine:
         """Log attached: who drives at step t, the replay actions, `exists` and the action-history tokens of [s0, s1)
         (ctrlsim_replay_actions), behind the action sampling of the step."""
         p, sl = _lib.ptr, slice(s0, s1)
+        if self.role is not None:               # roles: every vehicle takes the token of its own role's view (ctrlsim_replay_actions_views)
+            R, v = self.R, self._pv
+            vl = slice(s0 * R, s1 * R)
+            _lib.check(self.lib.ctrlsim_replay_actions_views(s1 - s0, self.N, R, t, self.steps + 1, self.steps, self.history_steps,
+                                                             self.dt, p(self.log[sl]), p(self.role[sl]), p(self.exist_hist[sl]),
+                                                             p(self.hist_states[sl]), p(self.phys[sl]), p(v.act_now[vl]), self.disc6,
+                                                             p(self.act_f64[sl]), p(self.exists[sl]), p(self.hist_tok[sl]),
+                                                             p(v.hist_tok[vl]), st), "replay_actions_views")
+            return
         _lib.check(self.lib.ctrlsim_replay_actions(s1 - s0, self.N, t, self.steps + 1, self.steps, self.history_steps, self.dt,
                                                    p(self.log[sl]), p(self.controlled[sl]), p(self.exist_hist[sl]),
                                                    p(self.hist_states[sl]), p(self.phys[sl]), p(self.act_now[sl]), self.disc6,
@@ -605,9 +740,10 @@ class RolloutEngine:
         if self.log is not None:
             # the same stream and the same event as the simulator step: behind the sampling of step t (and its context index lists),
             # in front of the step; the existence of the row the step writes follows it, in front of the lane's next grouping
+            vl = slice(s0 * self.R, s1 * self.R)                 # (roles: the records hold one row per view)
             with torch.cuda.stream(side):
-                self.own_ctx_steps[t, s0:s1].copy_(self.own_ctx[s0:s1])
-                self.sampled_steps[t, s0:s1].copy_(self.act_now[s0:s1])
+                self.own_ctx_steps[t, vl].copy_(self._pv.own_ctx[vl])
+                self.sampled_steps[t, vl].copy_(self._pv.act_now[vl])
             self._replay_actions(t, s0, s1, side.cuda_stream)
             self.sim_step(t, self.act_f64, s0=s0, s1=s1, stream=side.cuda_stream, applied=self.applied_steps[t])
             self._replay_latch(t + 1, s0, s1, side.cuda_stream)
@@ -633,13 +769,15 @@ class RolloutEngine:
 
     # ------------------------------------------------------------------ policy of one model batch
     def _ctx_index(self, L, s0, s1, st):
+        v = self._pv
         lib, p = self.lib, _lib.ptr
-        _lib.check(lib.ctrlsim_ctx_index_classes(s0, s1, self.N, self.dims.A, p(self.n_groups), p(self.grp_ids), p(self.own_g),
-                                                 p(self.mem_g), len(self.sizes), self._sizes_c, p(L.ctx_scn), p(L.ctx_grp),
-                                                 p(L.ctx_row0), p(self.ctx_of_group), p(self.own_ctx), p(self.own_slot),
-                                                 p(self.mem_ctx), p(self.mem_slot), st), "ctx_index_classes")
+        _lib.check(lib.ctrlsim_ctx_index_classes(s0, s1, self.N, self.dims.A, p(v.n_groups), p(v.grp_ids), p(v.own_g),
+                                                 p(v.mem_g), len(self.sizes), self._sizes_c, p(L.ctx_scn), p(L.ctx_grp),
+                                                 p(L.ctx_row0), p(v.ctx_of_group), p(v.own_ctx), p(v.own_slot),
+                                                 p(v.mem_ctx), p(v.mem_slot), st), "ctx_index_classes")
 
     def _build_contexts(self, L, plan, t, Tq, tt_first, st):
+        v = self._pv
         lib, p, d = self.lib, _lib.ptr, self.dims
         Tmax = self.steps
         if not plan:
@@ -649,29 +787,32 @@ class RolloutEngine:
         Bs = (C.c_int * n)(*[q[0] for q in plan]); As = (C.c_int * n)(*[q[1] for q in plan])
         cs = (_lib.Ctx * n)(*[q[3] for q in plan])
         _lib.check(lib.ctrlsim_build_context_c(n, Bs, As, cs, self.N, d.T, t, Tq, tt_first, Tmax + 1, Tmax, self.P_all, d.P, d.NP,
-                                               p(L.ctx_scn), p(L.ctx_grp), p(self.grp_focal), p(self.grp_ids),
-                                               p(self.hist_states), p(self.hist_tok), p(self.hist_rtg), p(self.goals),
-                                               p(self.types), p(self.roads), p(self.rtypes), self._zero4, st), "build_context")
+                                               p(L.ctx_scn), p(L.ctx_grp), p(v.grp_focal), p(v.grp_ids),
+                                               p(v.hist_states), p(v.hist_tok), p(v.hist_rtg), p(v.goals),
+                                               p(v.types), p(v.roads), p(v.rtypes), self._zero4, st), "build_context")
 
     def _sample_rtg(self, L, t, s0, s1, st, noise_rtg=None):
+        v = self._pv
         lib, p, d, sl = self.lib, _lib.ptr, self.dims, slice(s0, s1)
-        _lib.check(lib.ctrlsim_sample_rtg_rows(p(L.rtg_logits), p(L.ctx_row0), d.R, p(self.own_ctx[sl]), p(self.own_slot[sl]),
-                                               p(self.tilted[sl]), self.tilt,
-                                               p(self.tilt_scn[sl]) if self.tilt_scn is not None else None,
+        _lib.check(lib.ctrlsim_sample_rtg_rows(p(L.rtg_logits), p(L.ctx_row0), d.R, p(v.own_ctx[sl]), p(v.own_slot[sl]),
+                                               p(v.tilted[sl]), self.tilt,
+                                               p(v.tilt_scn[sl]) if v.tilt_scn is not None else None,
                                                p(noise_rtg[sl]) if noise_rtg is not None else None, self.seed,
-                                               p(self.scenario_id[sl]), t, p(self.hist_rtg[sl]), s1 - s0, self.N, self.steps, st),
+                                               p(v.scenario_id[sl]), t, p(v.hist_rtg[sl]), s1 - s0, self.N, self.steps, st),
                    "sample_rtg")
 
     def _sample_action(self, L, t, s0, s1, st, noise_act=None):
+        v = self._pv
         lib, p, d, sl = self.lib, _lib.ptr, self.dims, slice(s0, s1)
-        _lib.check(lib.ctrlsim_sample_action_rows(p(L.act_logits), p(L.ctx_row0), d.V, p(self.mem_ctx[sl]), p(self.mem_slot[sl]),
+        _lib.check(lib.ctrlsim_sample_action_rows(p(L.act_logits), p(L.ctx_row0), d.V, p(v.mem_ctx[sl]), p(v.mem_slot[sl]),
                                                   self.temperature, self.top_p,
                                                   p(noise_act[sl]) if noise_act is not None else None, self.seed,
-                                                  p(self.scenario_id[sl]), t, p(self.hist_tok[sl]), p(self.act_now[sl]),
+                                                  p(v.scenario_id[sl]), t, p(v.hist_tok[sl]), p(v.act_now[sl]),
                                                   s1 - s0, self.N, self.steps, ZERO_ACTION_TOKEN, st), "sample_action")
 
     def _chunk_step_cached(self, L, s0, s1, counts, t):
         """Cached phase (t < T): policy step of one model batch against the decoder K/V cache it keeps in the lane's workspace."""
+        v = self._pv
         lib, p, st, d = self.lib, _lib.ptr, self._main.cuda_stream, self.dims
         N, Tmax = self.N, self.steps
         Tq, tt_first = t + 1, max(t - 1, 0)
@@ -690,7 +831,7 @@ class RolloutEngine:
         self._sample_rtg(L, t, s0, s1, st)
         if n:
             _lib.check(lib.ctrlsim_dt_forward_pass2_c(self.model.handle, n, Bs, As, cs, Tq, t, N, Tmax, p(L.ctx_scn),
-                                                      p(self.hist_rtg), p(L.ws), p(L.act_logits), 1, st), "pass2_cached")
+                                                      p(v.hist_rtg), p(L.ws), p(L.act_logits), 1, st), "pass2_cached")
         self._sample_action(L, t, s0, s1, st)
 
     def _dt_cfg(self):
@@ -722,6 +863,7 @@ class RolloutEngine:
     def _policy_chunks(self, L, t, hist, lo, hi, noise_rtg=None, noise_act=None):
         """Full-recompute policy for scenarios [lo, hi) (hist = their group counts per size class), cut into model batches, on
         the main stream with lane L's buffers."""
+        v = self._pv
         lib, p, st, d = self.lib, _lib.ptr, self._main.cuda_stream, self.dims
         N, Tmax = self.N, self.steps
         Tq = min(t, d.T - 1) + 1
@@ -770,7 +912,7 @@ class RolloutEngine:
                 self._sample_rtg(L, t, s0, s1, st2, noise_rtg)
                 if n:
                     _lib.check(lib.ctrlsim_dt_forward_pass2_c(self.model.handle, n, Bs, As, cs, Tq, t, N, Tmax, p(L.ctx_scn),
-                                                              p(self.hist_rtg), p(L.ws), p(L.act_logits), 0, st2), "pass2")
+                                                              p(v.hist_rtg), p(L.ws), p(L.act_logits), 0, st2), "pass2")
             self._sample_action(L, t, s0, s1, st2, noise_act)
             if on_side:
                 L.ev_p2.record(L.side)
@@ -781,6 +923,8 @@ class RolloutEngine:
         back: the scheduler (run) then queues another lane's step before this one blocks on its read-back."""
         T = self.dims.T
         t0 = 0
+        R, gps = self.R, self._pv.groups_per_step
+        vlo, vhi = lo * R, hi * R                # the policy side works on view rows (roles: R views per scene; else the scenes themselves)
         if self.log is not None and steps > 0:
             self._replay_latch(0, lo, hi, self._side(L).cuda_stream)     # behind the reset (run: side waits for main; run_jobs: same stream)
         # pipelined jobs: the host never BLOCKS on a lane's read-back — a lane whose group counts are not back yet (its cached steps crawl
@@ -791,15 +935,15 @@ class RolloutEngine:
             # are constant and its decoder K/V can be cached across steps (csrc/forward.hip).  A chunk whose context set does
             # change (a vehicle stops existing) falls back to the full recompute.
             nT = min(T, steps)
-            self._enqueue_groups(L, 0, lo, hi)
+            self._enqueue_groups(L, 0, vlo, vhi)
             yield
             while poll and not L.ev_ready.query():
                 yield
             hist, _ = self._await_groups(L)
-            self.groups_per_step[0, lo:hi] = hist.sum(1)
-            for (s0, s1, counts) in self._chunks(hist, lo):
+            gps[0, vlo:vhi] = hist.sum(1)
+            for (s0, s1, counts) in self._chunks(hist, vlo):    # view rows, cut between scenes
                 cached_ok = sum(counts) > 0
-                h = hist[s0 - lo:s1 - lo]
+                h = hist[s0 - vlo:s1 - vlo]
                 if nT > 1:
                     self._snapshot_groups(L, s0, s1)
                 for t in range(nT):
@@ -810,14 +954,14 @@ class RolloutEngine:
                         while poll and not L.ev_ready.query():
                             yield
                         h, changed = self._await_groups(L)
-                        self.groups_per_step[t, s0:s1] = h.sum(1)
+                        gps[t, s0:s1] = h.sum(1)
                         cached_ok = cached_ok and not changed
                     self._main_waits(L)
                     if cached_ok:
                         self._chunk_step_cached(L, s0, s1, counts, t)
                     else:
                         self._policy_chunks(L, t, h, s0, s1)
-                    self._enqueue_sim(L, t, s0, s1)
+                    self._enqueue_sim(L, t, s0 // R, s1 // R)
                     if t + 1 < nT:
                         self._enqueue_groups(L, t + 1, s0, s1, compare=True)
             t0 = nT
@@ -837,14 +981,14 @@ class RolloutEngine:
         for t in range(t0, steps):
             if lane_idx is not None:
                 self._lane_t[lane_idx] = t
-            self._enqueue_groups(L, t, lo, hi)
+            self._enqueue_groups(L, t, vlo, vhi)
             yield
             while poll and not L.ev_ready.query():
                 yield
             hist, _ = self._await_groups(L)
-            self.groups_per_step[t, lo:hi] = hist.sum(1)
+            gps[t, vlo:vhi] = hist.sum(1)
             self._main_waits(L)
-            self._policy_chunks(L, t, hist, lo, hi)
+            self._policy_chunks(L, t, hist, vlo, vhi)
             self._enqueue_sim(L, t, lo, hi)
 
     def run(self, steps=None, noise_fn=None, s0=0, s1=None):
@@ -984,7 +1128,8 @@ class RolloutEngine:
     # ------------------------------------------------------------------ synchronous single-stream steps (plugin surface)
     def step(self, t, noise_rtg=None, noise_act=None):
         """One closed-loop step: policy (grouping, contexts, two-pass model, sampling) then the simulator step.
-        noise_rtg [S,N,3,R] / noise_act [S,N,V] float32 tensors (explicit Exp(1) noise) or None (in-kernel)."""
+        noise_rtg [S,N,3,R] / noise_act [S,N,V] float32 tensors (explicit Exp(1) noise) or None (in-kernel).  With roles (set_roles) the
+        noise is per VIEW row: [S*R,N,3,R] / [S*R,N,V], row s * R + r for role r of scene s."""
         if self.log is None:
             self.policy_step(t, noise_rtg, noise_act)
             self.sim_step(t)
@@ -996,8 +1141,8 @@ class RolloutEngine:
         self.policy_step(t, noise_rtg, noise_act)
         if self.lanes[0].side is not None:      # the second pass and the sampling ran on lane 0's side stream (_policy_chunks)
             self._main.wait_stream(self.lanes[0].side)
-        self.own_ctx_steps[t].copy_(self.own_ctx)
-        self.sampled_steps[t].copy_(self.act_now)
+        self.own_ctx_steps[t].copy_(self._pv.own_ctx)
+        self.sampled_steps[t].copy_(self._pv.act_now)
         self._replay_actions(t, 0, self.S, st)
         self.sim_step(t, self.act_f64, applied=self.applied_steps[t])
         self._replay_latch(t + 1, 0, self.S, st)
@@ -1006,15 +1151,19 @@ class RolloutEngine:
         """AutoregressivePolicy.predict for every scenario: writes hist_rtg[..., t, :], hist_tok[..., t], act_now."""
         self._main = torch.cuda.current_stream(self.device)
         self._bind()
-        L = self.lanes[0]
+        L, v = self.lanes[0], self._pv
+        for name, noise in (("noise_rtg", noise_rtg), ("noise_act", noise_act)):
+            if noise is not None and self.role is not None and noise.shape[0] != v.S:
+                raise ValueError(f"{name} has {noise.shape[0]} rows: with roles the explicit noise is per view row, "
+                                 f"[S*R = {v.S}, N, ...] (row s * R + r = role r of scene s)")
         side, L.side = L.side, None                   # everything on the caller's stream
         try:
-            self._enqueue_groups(L, t, 0, self.S)
+            self._enqueue_groups(L, t, 0, v.S)
             hist, _ = self._await_groups(L)
         finally:
             L.side = side
-        self.groups_per_step[t] = hist.sum(1)
-        self._policy_chunks(L, t, hist, 0, self.S, noise_rtg, noise_act)
+        v.groups_per_step[t] = hist.sum(1)
+        self._policy_chunks(L, t, hist, 0, v.S, noise_rtg, noise_act)
 
     def metrics_pack(self, gt, goals4, eval_mask=None, out=None):
         """Evaluator statistics of the loaded scenarios' finished rollouts, accumulated on the device (ctrlsim_metrics_pack):
@@ -1084,4 +1233,24 @@ class RolloutEngine:
             out["applied"] = self.applied_steps.permute(1, 2, 0, 3).contiguous().cpu().numpy()
             out["existence"] = self.exist_hist.cpu().numpy()
             out["sampled"] = self.sampled_steps.permute(1, 2, 0).contiguous().cpu().numpy()     # [S,N,steps] sampled tokens (act_now)
+        if self.role is not None:
+            # roles: the policy side per view — rtg_bins_roles [S,R,N,steps,3], sampled_roles [S,R,N,steps] (< 0: the view has no context
+            # answering for the vehicle), own_ctx [S,R,N,steps] (0: the view sampled an RTG for it, -1: it did not), n_groups_roles [steps,S,R];
+            # `sampled` and `rtg_bins` are merged per vehicle from the role that drives it (no role: -1 / the "not yet written" row),
+            # n_groups sums the scene's views
+            S, R, N, T, v = self.S, self.R, self.N, self.steps, self._pv
+            per_view = lambda a: a.permute(1, 2, 0).contiguous().cpu().numpy().reshape(S, R, N, T)
+            out["rtg_bins_roles"] = v.hist_rtg.cpu().numpy().reshape(S, R, N, T, 3)
+            out["sampled_roles"] = per_view(self.sampled_steps)
+            out["own_ctx"] = np.where(per_view(self.own_ctx_steps) >= 0, 0, -1).astype(np.int32)   # (a context's index in its model batch
+                                                                                                 #  depends on the schedule: not reported)
+            out["n_groups_roles"] = v.groups_per_step.reshape(T, S, R).copy()
+            out["n_groups"] = out["n_groups_roles"].sum(2).astype(np.int32)
+            if R > 1:                               # (R = 1: the scene is its own view, both are already in place)
+                role = self.role.cpu().numpy()
+                pick = np.clip(role, 0, R - 1)[:, None, :, None]
+                driven = (role >= 0)[:, :, None]
+                out["sampled"] = np.where(driven, np.take_along_axis(out["sampled_roles"], pick, 1)[:, 0], -1).astype(np.int32)
+                zero = np.asarray(self.zero_rtg, np.int32)
+                out["rtg_bins"] = np.where(driven[..., None], np.take_along_axis(out["rtg_bins_roles"], pick[..., None], 1)[:, 0], zero)
         return out

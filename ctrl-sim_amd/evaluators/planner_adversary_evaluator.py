@@ -15,6 +15,7 @@ unmodified reference policies + the real FreeCar/Box2D)."""
 from __future__ import annotations
 
 import random
+from types import SimpleNamespace as _NS
 
 import numpy as np
 import torch
@@ -22,7 +23,7 @@ from scipy.spatial import distance
 
 from .. import scenarios as _scn
 from ..kinematics import bicycle_backward
-from ..simulation import Simulation
+from ..simulation import Simulation, CollisionType
 from .policy_evaluator import PolicyEvaluator
 
 PLANNER_KEYS = {"next_acceleration": "next_planner_acceleration", "next_steering": "next_planner_steering",
@@ -98,7 +99,12 @@ class PlannerAdversaryEvaluator(PolicyEvaluator):
     # ---- :458-546
     def evaluate_planner_adversary(self, adv_traj_fn=None):
         """adv_traj_fn(scn, gt_data_dict, ego, adv) -> [steps+1, 5] (x, y, vx, vy, yaw): the fixed adversarial trajectory used
-        when adversary.name == 'cat' (the reference reads it from the CAT dictionary)."""
+        when adversary.name == 'cat' (the reference reads it from the CAT dictionary).
+
+        cfg.eval_planner_adversary.device_replay = True (default False) rolls the scenes on ONE RolloutEngine with policy roles per
+        vehicle (_evaluate_on_device) where that route applies; anything else runs the loop below."""
+        if self._device_route_applies():
+            return self._evaluate_on_device(adv_traj_fn)
         self.reset()
         syn = self.synthetic
         d_model = self.planner.model.dims
@@ -160,6 +166,155 @@ class PlannerAdversaryEvaluator(PolicyEvaluator):
             self.last_vehicle_data_dict = vdd
             self.update_running_statistics(vdd)
         return self.compute_metrics()
+
+    # ---- the same evaluation on the engine: policy roles per vehicle
+    def _device_route_applies(self):
+        """cfg.eval_planner_adversary.device_replay, for two of this repo's AutoregressivePolicy objects on the SAME model object with equal
+        sampling and RTG settings (temperature, nucleus, use_rtg / predict_rtgs / discretize_rtgs, privileged / max / min return) and the policy's
+        own RTGs (no real_time_rewards) — or such a planner against a fixed trajectory (adversary.name ==
+        'cat').  Anything else keeps the stepwise loop."""
+        from ..policies.autoregressive_policy import AutoregressivePolicy
+        if not bool(self.cfg_pa.get("device_replay", False)):
+            return False
+        pl, ad = self.planner, self.adversary
+        ok = lambda q: type(q) is AutoregressivePolicy and not q.real_time_rewards and hasattr(q.model, "hip")
+        if not ok(pl):
+            return False
+        if getattr(ad, "name", None) == "cat":
+            return True
+        # one engine samples for both roles: everything but the tilts and the key names must be common to the two policies
+        common = lambda q: (float(q.action_temperature), bool(q.nucleus_sampling), float(q.nucleus_threshold) if q.nucleus_sampling else 0.0,
+                            bool(q.use_rtg), bool(q.predict_rtgs), bool(q.discretize_rtgs), bool(q.privileged_return),
+                            bool(q.max_return), bool(q.min_return))
+        return ok(ad) and ad.model is pl.model and common(ad) == common(pl)
+
+    @staticmethod
+    def _tilt_of(policy):
+        return (policy.goal_tilt, policy.veh_veh_tilt, policy.veh_edge_tilt) if policy.tilt_dict["tilt"] else (0.0, 0.0, 0.0)
+
+    def _evaluate_on_device(self, adv_traj_fn=None):
+        """evaluate_planner_adversary with the scenario loop turned inside out (as PolicyEvaluator._evaluate_policy_batched): scenes, ego
+        and adversary are chosen exactly as the loop chooses them, then all scenes of equal shape roll in one RolloutEngine batch —
+        the log attached (set_log), role 0 = the ego under the planner's tilts, role 1 = the adversary under the adversary's
+        (set_roles: one policy view per role and scene, csrc/replay.hip), everybody else and the history steps replayed from the log
+        on the device.  One run(), one check_finite(), one read-back per batch; every scene's vehicle_data_dict is then built from the
+        arrays in this class's schema and fed to the unchanged update_running_statistics.  A 'cat' adversary needs no role: its log
+        rows from history_steps on are the fixed trajectory (replay.merge_cat_log), which the replay branch follows exactly as
+        apply_adv_traj does; the statistics keep the unmodified log.  The policy OBJECTS are not driven (no reset / update_state /
+        predict calls)."""
+        from ..engine import RolloutEngine
+        from .. import replay
+        self.reset()
+        syn = self.synthetic
+        pl = self.planner
+        d_model = pl.model.dims
+        cat = self.adversary.name == "cat"
+        chosen, n_eval = [], 0
+        for k in range(int(syn["num_scenarios"])):
+            if n_eval == self.cfg_pa.num_files_to_evaluate:
+                break
+            scn = _scn.make_scenario(int(syn.get("seed", 0)), k, n_agents=int(syn["n_agents"]),
+                                     n_polylines=int(syn["n_polylines"]), n_points=d_model.NP,
+                                     extent=float(syn.get("extent", 100.0)))
+            gt_data_dict = self._ground_truth(scn)
+            ego, adv = pick_ego_adversary(scn)
+            adv_traj = adv_traj_fn(scn, gt_data_dict, ego, adv) if cat else None
+            n_eval += 1
+            chosen.append((scn, gt_data_dict, ego, adv, adv_traj))
+        groups = {}
+        for item in chosen:                                    # one engine batch = scenes of equal vehicle and polyline counts
+            groups.setdefault((item[0].N, item[0].road_points.shape[0]), []).append(item)
+        cap = int(self.cfg_pa.get("batch_scenarios", 256))
+        tilts = [self._tilt_of(pl)] + ([] if cat else [self._tilt_of(self.adversary)])
+        eng = RolloutEngine(pl.model.cfg, pl.model.weights, pl.model.device, max_ctx=int(self.cfg.eval.get("batch_contexts", 256)),
+                            seed=int(self.cfg.eval.seed), temperature=pl.action_temperature, nucleus=pl.nucleus_sampling,
+                            top_p=pl.nucleus_threshold, model=pl.model.hip, lanes=1)
+        self.device_replay_scenes = 0
+        for (N, _), items in groups.items():
+            for c0 in range(0, len(items), cap):
+                self._roll_on_device(eng, items[c0:c0 + cap], N, tilts, cat, replay)
+        return self.compute_metrics()
+
+    def _roll_on_device(self, eng, items, N, tilts, cat, replay):
+        from .. import discretize as dz
+        from ..metrics import nearest_vehicle_distance
+        w, T, hs = self.cfg_rl_waymo, self.steps, self.history_steps
+        S, T1 = len(items), T + 1
+        gt = np.zeros((S, N, T1 + 1, 6))                       # x, y, heading, speed, exist, length (+ one row: step t looks at t + 1)
+        role = -np.ones((S, N), np.int32)
+        for k, (scn, gtd, ego, adv, adv_traj) in enumerate(items):
+            for v in range(N):
+                tr = np.asarray(gtd[v]["traj"], np.float64)
+                n = min(len(tr), T1 + 1)
+                gt[k, v, :n, :5] = tr[:n, :5]
+                gt[k, v, :n, 5] = tr[:n, -1]
+            role[k, ego] = 0
+            if not cat:
+                role[k, adv] = 1
+        log = gt
+        if cat:
+            log = np.stack([replay.merge_cat_log(gt[k], it[3], it[4], hs) for k, it in enumerate(items)])
+        eng.load_scenarios([it[0] for it in items], steps=T)
+        eng.set_log(log, role >= 0, hs)
+        eng.set_roles(role, tilts)
+        eng.run()
+        try:
+            eng.check_finite()
+        except FloatingPointError as e:
+            raise FloatingPointError(f"{e} — batch of scenes {[int(it[0].index) for it in items]}") from None
+        r = eng.results()                                      # the one read-back
+        speeds = eng.speed_hist.cpu().numpy()
+        states, coll, exist, applied = r["states"], r["coll"], r["existence"], r["applied"]
+        cont = dz.undiscretize_rtgs(r["rtg_bins_roles"], w)    # [S,R,N,T,3]
+        own, sampled = r["own_ctx"], r["sampled_roles"]
+        keys = [PLANNER_KEYS] + ([] if cat else [ADVERSARY_KEYS])
+        n_comp = self.planner.cfg_model.num_reward_components
+        for k, (scn, gtd, ego, adv, adv_traj) in enumerate(items):
+            self.ego_vehicle, self.adversary_vehicle = ego, adv
+            ex_k = exist[k].astype(float)
+            nd = nearest_vehicle_distance(states[k, :, :, :2].astype(np.float64), ex_k)
+            gnd = nearest_vehicle_distance(gt[k, :, :T1, :2], ex_k)
+            vdd = {}
+            for v in range(N):
+                veh0 = _NS(getWidth=lambda v=v, scn=scn: float(scn.width[v]), getLength=lambda v=v, scn=scn: float(scn.length[v]))
+                goal = {"pos": scn.goal_pos[v].astype(np.float64), "heading": float(scn.goal_heading[v]), "speed": float(scn.goal_speed[v])}
+                d = self.initialize_vehicle_data_dict(veh0, goal)
+                norm = np.linalg.norm(np.array([states[k, v, 0, 0], states[k, v, 0, 1]]) - goal["pos"])
+                tr = gt[k, v]
+                for t in range(T1):
+                    row = states[k, v, t]                      # float32 scalars, as the Simulation facade hands them to the loop
+                    d["gt_position"].append({"x": tr[t, 0], "y": tr[t, 1]})
+                    d["gt_heading"].append(tr[t, 2])
+                    d["gt_speed"].append(tr[t, 3])
+                    d["gt_acceleration"].append((tr[t + 1, 3] - tr[t - 1, 3]) / (2 * self.dt) if 0 < t < self.steps - 1 else 0)
+                    d["position"].append({"x": row[0], "y": row[1]})
+                    d["velocity"].append({"x": row[2], "y": row[3]})
+                    d["heading"].append(row[4])
+                    d["timestep"].append(t)
+                    d["existence"].append(exist[k, v, t])
+                    veh = _NS(position=_NS(x=row[0], y=row[1]), speed=speeds[k, v, t], heading=row[4],
+                              collision_type_veh=CollisionType.VEHICLE_VEHICLE if coll[k, v, t, 0] else CollisionType.NOT_COLLIDED,
+                              collision_type_edge=CollisionType.VEHICLE_ROAD if coll[k, v, t, 1] else CollisionType.NOT_COLLIDED)
+                    d["reward"].append(self.compute_reward(veh, goal, norm, d))
+                    d["nearest_dist"].append(nd[v, t])
+                    d["gt_nearest_dist"].append(gnd[v, t])
+                    d["acceleration"].append(float(applied[k, v, t, 0]) if t < T else 0)
+                    d["steering"].append(float(applied[k, v, t, 1]) if t < T else 0)
+                    if t < T and self.planner.predict_rtgs:    # AutoregressivePolicy.predict: one RTG row per policy, vehicle and step
+                        for rr, kd in enumerate(keys):
+                            if own[k, rr, v, t] >= 0:
+                                d["next_rtg_goal"], d["next_rtg_veh"], d["next_rtg_road"] = cont[k, rr, v, t]
+                                d[kd["rtgs"]].append(np.array(cont[k, rr, v, t]))
+                            else:
+                                d[kd["rtgs"]].append(np.array([0] * n_comp))
+                vdd[v] = d
+            for rr, (kd, v) in enumerate(zip(keys, (ego, adv))):   # what the last predict() left for act()
+                tok = int(sampled[k, rr, v, T - 1])
+                a, s_ = dz.undiscretize_actions(np.array([tok]), w)[0] if tok >= 0 else (0.0, 0.0)
+                vdd[v][kd["next_acceleration"]], vdd[v][kd["next_steering"]] = a, s_
+            self.last_vehicle_data_dict = vdd
+            self.update_running_statistics(vdd)
+            self.device_replay_scenes += 1
 
     # ---- :202-365
     def update_running_statistics(self, data_dict):

@@ -65,6 +65,49 @@ def actions(log, controlled, exist_t, t, history_steps, heading, speed, act_now,
     return act, alive, dz.discretize_actions(act, w).astype(np.int32)
 
 
+# ---- policy roles (include/ctrlsim.h: ctrlsim_replay_latch_views / _actions_views): a scene [..., N] has R policy views
+# [..., R, N]; role [..., N] int = -1 (the log drives the vehicle) or the view whose policy drives it
+def latch_views(log, t, exist_prev, state_row, view_states):
+    """The latch of step t on a scene and its views.  state_row [..., N, 8] float32 = the row the simulator wrote;
+    view_states [..., R, N, T1, 8] float32 is updated in place: row t of every view <- the scene's row, existence column latched.
+    -> (exist_t [..., N] float64, the scene's row with the latched existence column)."""
+    ex = latch(log, t, exist_prev)
+    row = np.array(state_row, np.float32)
+    row[..., 7] = ex.astype(np.float32)
+    view_states[..., t, :] = row[..., None, :, :]
+    return ex, row
+
+
+def actions_views(log, role, exist_t, t, history_steps, heading, speed, act_now_views, dt, w):
+    """Step t of a scene with roles -> (act [..., N, 2], alive [..., N], token [..., N]) as actions(): role >= 0 stands for
+    `controlled`, and vehicle v of role r takes act_now_views[..., r, v] — the token its own role's view sampled (< 0, or a role the
+    views do not hold: nobody answers, (0, 0)).  The token goes into the scene's action history and every view's."""
+    role = np.asarray(role)
+    toks = np.asarray(act_now_views)
+    R = toks.shape[-2]
+    ok = (role >= 0) & (role < R)
+    own = np.take_along_axis(toks, np.clip(role, 0, R - 1)[..., None, :], axis=-2)[..., 0, :]
+    return actions(log, role >= 0, exist_t, t, history_steps, heading, speed, np.where(ok, own, -1), dt, w)
+
+
+def merge_cat_log(log, adv, traj, history_steps):
+    """The log of a scene whose adversary `adv` follows a fixed trajectory (PlannerAdversaryEvaluator.apply_adv_traj,
+    planner_adversary_evaluator.py:163-199) instead of a policy: a copy of log [N, T1 + 1, 6] in which the adversary's rows
+    >= history_steps take x, y, heading and speed = hypot(vx, vy) from traj [>= T1, 5] = x, y, vx, vy, yaw (rows beyond the trajectory
+    keep the log's).  Existence and length stay the log's, so the replay branch (role -1) decides validity and latches exactly as
+    apply_adv_traj does, and reaches for the trajectory from step history_steps - 1 on, as the loop does."""
+    out = np.array(log, np.float64)
+    traj = np.asarray(traj, np.float64)
+    n = min(out.shape[-2], len(traj))
+    hs = int(history_steps)
+    if n > hs:
+        out[adv, hs:n, 0] = traj[hs:n, 0]
+        out[adv, hs:n, 1] = traj[hs:n, 1]
+        out[adv, hs:n, 2] = traj[hs:n, 4]
+        out[adv, hs:n, 3] = np.sqrt(traj[hs:n, 2] ** 2 + traj[hs:n, 3] ** 2)
+    return out
+
+
 def token_margin(act, w):
     """Distance of the scaled (accel, steer) of discretize_actions from the nearest half-integer, [..., 2]: where it is tiny, a last-bit
     difference of the pair may round to the neighbouring bin."""

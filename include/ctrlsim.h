@@ -134,6 +134,24 @@ int ctrlsim_replay_actions(int S, int N, int t, int T1, int Tmax, int history_st
                            const uint8_t* controlled, const double* exist_hist, const float* hist_states, const float* phys,
                            const int* act_now, const double* disc6, double* act_f64, uint8_t* exists, int* hist_tok,
                            hipStream_t stream);
+/* Policy ROLES (evaluators/planner_adversary_evaluator.py:458-546: a planner drives the ego, an adversary another vehicle, each
+ * policy with its own focal groups, persisted context membership and RTG history over a common state and applied-action history).
+ * A scene s has R <= CTRLSIM_MAX_ROLES policy VIEWS, rows s * R .. s * R + R - 1 of the policy-side arrays: ordinary scenarios for
+ * ctrlsim_group_build, ctrlsim_build_context, the forward passes and the samplers.  role [S,N] i32: -1 = the vehicle replays its
+ * log, r in [0, R) = the policy of view s * R + r drives it from step history_steps - 1 on.
+ * ctrlsim_replay_latch_views = ctrlsim_replay_latch, which then copies the scene's state row t (the latched existence column
+ * included) into row t of view_states [S*R,N,T1,8].
+ * ctrlsim_replay_actions_views = ctrlsim_replay_actions with `role >= 0` for `controlled` and the sampled token read from the
+ * vehicle's own role's view, act_now [S*R,N] at (s * R + role, v) — a role >= R answers like a token < 0; the token of the applied pair
+ * also goes into column t of view_tok [S*R,N,Tmax] of every view of the scene.
+ * view_states / view_tok equal to hist_states / hist_tok (or NULL) with R = 1: the scene is its own view, nothing is copied. */
+#define CTRLSIM_MAX_ROLES 4
+int ctrlsim_replay_latch_views(int S, int N, int R, int t, int T1, const double* log, const float* phys, double* exist_hist,
+                               float* hist_states, float* speed_hist, float* view_states, hipStream_t stream);
+int ctrlsim_replay_actions_views(int S, int N, int R, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
+                                 const int* role, const double* exist_hist, const float* hist_states, const float* phys,
+                                 const int* act_now, const double* disc6, double* act_f64, uint8_t* exists, int* hist_tok,
+                                 int* view_tok, hipStream_t stream);
 
 /* ---- focal grouping + context tensors ------------------------------------------------------------------------
  * Replaces AutoregressivePolicy.get_data (policies/autoregressive_policy.py:51-165) with
