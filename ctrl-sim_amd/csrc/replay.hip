@@ -19,8 +19,9 @@
 // contraction; `%` as NumPy defines it for floats: fmod, then the divisor's sign), so that everything but the arctangent — a library
 // function on both sides — gives the host's bits (ctrlsim_amd/replay.py is the host form the tests compare with).
 //
-//   replay_latch_views_kernel / replay_actions_views_kernel   the same two steps for a scene whose vehicles are driven by up to
-//                           CTRLSIM_MAX_ROLES policy ROLES (planner, adversary, ...), each role with a policy view of the scene
+// Both kernels serve a scene whose vehicles are driven by up to CTRLSIM_MAX_ROLES policy ROLES (planner, adversary, ...), each role with
+// a policy view of the scene (the _views entry points); one policy and a `controlled` flag per vehicle (the plain entry points) is the
+// case R = 1 without view arrays.
 #include "launchers.h"
 #include "../../include/ctrlsim.h"
 
@@ -32,18 +33,6 @@ struct ReplayDisc {          // cfgs/dataset/waymo/base.yaml:13-16,41-42
   double min_accel, max_accel, min_steer, max_steer;
   int n_accel, n_steer;
 };
-
-__global__ __launch_bounds__(256) void replay_latch_kernel(int n, int t, int T1, const double* __restrict__ log,
-                                                           const float* __restrict__ phys, double* __restrict__ exist_hist,
-                                                           float* __restrict__ hist_states, float* __restrict__ speed_hist) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  double e = log[((size_t)i * (T1 + 1) + t) * 6 + 4];
-  if (t > 0) e = e * (exist_hist[(size_t)i * T1 + t - 1] != 0.0 ? 1.0 : 0.0);
-  exist_hist[(size_t)i * T1 + t] = e;
-  hist_states[((size_t)i * T1 + t) * 8 + 7] = (float)e;
-  if (speed_hist) speed_hist[(size_t)i * T1 + t] = phys[(size_t)i * 20 + 16];
-}
 
 // The pair of step t for vehicle i: the policy's token (by_policy; tok < 0 = no context answers for the vehicle) or the inverse bicycle
 // model against the next logged state.  -> alive (the simulator's `exists` flag)
@@ -92,34 +81,14 @@ __device__ __forceinline__ int replay_token(double accel, double steer, const Re
   return (int)tokf;
 }
 
-__global__ __launch_bounds__(256) void replay_actions_kernel(int n, int t, int T1, int Tmax, int history_steps, double dt,
-                                                             const double* __restrict__ log,
-                                                             const unsigned char* __restrict__ controlled,
-                                                             const double* __restrict__ exist_hist,
-                                                             const float* __restrict__ hist_states, const float* __restrict__ phys,
-                                                             const int* __restrict__ act_now, ReplayDisc dz,
-                                                             double* __restrict__ act_f64, unsigned char* __restrict__ exists,
-                                                             int* __restrict__ hist_tok) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double ex = exist_hist[(size_t)i * T1 + t];
-  const bool by_policy = controlled[i] != 0 && t >= history_steps - 1;
-  double accel, steer;
-  const bool alive = replay_pair(i, t, T1, dt, by_policy, by_policy ? act_now[i] : -1, ex, log, hist_states, phys, dz, accel, steer);
-  act_f64[(size_t)i * 2 + 0] = accel;
-  act_f64[(size_t)i * 2 + 1] = steer;
-  exists[i] = alive ? 1 : 0;
-  hist_tok[(size_t)i * Tmax + t] = replay_token(accel, steer, dz);
-}
-
 // ---- policy roles: S scenes, S * R policy views (view s * R + r = role r's picture of scene s, an ordinary engine scenario for
 // the grouping, context, forward and sampling kernels).  The simulator runs on the scene; its state row, the latched existence and
 // the applied action's token travel into every view of the scene, and a vehicle takes the token its own role's view sampled
 // (evaluators/planner_adversary_evaluator.py:497-546: two policies, one scene, a common state and applied-action history).
-__global__ __launch_bounds__(256) void replay_latch_views_kernel(int n, int N, int R, int t, int T1, const double* __restrict__ log,
-                                                                 const float* __restrict__ phys, double* __restrict__ exist_hist,
-                                                                 float* __restrict__ hist_states, float* __restrict__ speed_hist,
-                                                                 float* __restrict__ view_states) {
+__global__ __launch_bounds__(256) void replay_latch_kernel(int n, int N, int R, int t, int T1, const double* __restrict__ log,
+                                                           const float* __restrict__ phys, double* __restrict__ exist_hist,
+                                                           float* __restrict__ hist_states, float* __restrict__ speed_hist,
+                                                           float* __restrict__ view_states) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   double e = log[((size_t)i * (T1 + 1) + t) * 6 + 4];
@@ -139,20 +108,26 @@ __global__ __launch_bounds__(256) void replay_latch_views_kernel(int n, int N, i
   }
 }
 
-__global__ __launch_bounds__(256) void replay_actions_views_kernel(int n, int N, int R, int t, int T1, int Tmax, int history_steps,
-                                                                   double dt, const double* __restrict__ log,
-                                                                   const int* __restrict__ role, const double* __restrict__ exist_hist,
-                                                                   const float* __restrict__ hist_states, const float* __restrict__ phys,
-                                                                   const int* __restrict__ act_now, ReplayDisc dz,
-                                                                   double* __restrict__ act_f64, unsigned char* __restrict__ exists,
-                                                                   int* __restrict__ hist_tok, int* __restrict__ view_tok) {
+// who drives vehicle i: a policy role (>= 0) or the log (-1).  A `controlled` flag is role 0 of one policy
+__device__ __forceinline__ int replay_role(const int* __restrict__ role, int i) { return role[i]; }
+__device__ __forceinline__ int replay_role(const unsigned char* __restrict__ controlled, int i) { return controlled[i] ? 0 : -1; }
+
+template <typename Who>
+__global__ __launch_bounds__(256) void replay_actions_kernel(int n, int N, int R, int t, int T1, int Tmax, int history_steps, double dt,
+                                                             const double* __restrict__ log, const Who* __restrict__ who,
+                                                             const double* __restrict__ exist_hist,
+                                                             const float* __restrict__ hist_states, const float* __restrict__ phys,
+                                                             const int* __restrict__ act_now, ReplayDisc dz,
+                                                             double* __restrict__ act_f64, unsigned char* __restrict__ exists,
+                                                             int* __restrict__ hist_tok, int* __restrict__ view_tok) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int s = i / N, v = i - s * N;
   const double ex = exist_hist[(size_t)i * T1 + t];
-  const int r = role[i];
+  const int r = replay_role(who, i);
   const bool by_policy = r >= 0 && t >= history_steps - 1;
-  // the token of the vehicle's OWN role's view; a role index the views do not hold answers like a view without a context for it
+  // the token of the vehicle's OWN role's view (R = 1, role 0: act_now[i]); a role index the views do not hold answers like a view
+  // without a context for it
   const int tok = (by_policy && r < R) ? act_now[((size_t)s * R + r) * N + v] : -1;
   double accel, steer;
   const bool alive = replay_pair(i, t, T1, dt, by_policy, tok, ex, log, hist_states, phys, dz, accel, steer);
@@ -167,34 +142,6 @@ __global__ __launch_bounds__(256) void replay_actions_views_kernel(int n, int N,
 
 }  // namespace
 
-int launch_replay_latch(int S, int N, int t, int T1, const double* log, const float* phys, double* exist_hist, float* hist_states,
-                        float* speed_hist, hipStream_t st) {
-  if (S <= 0) return CTRLSIM_OK;
-  if (N < 1 || t < 0 || t >= T1 || !log || !exist_hist || !hist_states || (speed_hist && !phys)) return CTRLSIM_EINVAL;
-  const long n = (long)S * N;
-  if (n > 0x7fffffffL - 256) return CTRLSIM_EINVAL;
-  hipLaunchKernelGGL(replay_latch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, t, T1, log, phys, exist_hist,
-                     hist_states, speed_hist);
-  return ctrlsim_launch_status();
-}
-
-int launch_replay_actions(int S, int N, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
-                          const unsigned char* controlled, const double* exist_hist, const float* hist_states, const float* phys,
-                          const int* act_now, const double* disc6, double* act_f64, unsigned char* exists, int* hist_tok,
-                          hipStream_t st) {
-  if (S <= 0) return CTRLSIM_OK;
-  if (N < 1 || t < 0 || t >= Tmax || t + 1 >= T1 || !log || !controlled || !exist_hist || !hist_states || !phys || !act_now || !disc6 ||
-      !act_f64 || !exists || !hist_tok)
-    return CTRLSIM_EINVAL;
-  const long n = (long)S * N;
-  if (n > 0x7fffffffL - 256) return CTRLSIM_EINVAL;
-  ReplayDisc dz{disc6[0], disc6[1], disc6[2], disc6[3], (int)disc6[4], (int)disc6[5]};
-  if (dz.n_accel < 2 || dz.n_steer < 2) return CTRLSIM_EINVAL;
-  hipLaunchKernelGGL(replay_actions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, t, T1, Tmax, history_steps, dt,
-                     log, controlled, exist_hist, hist_states, phys, act_now, dz, act_f64, exists, hist_tok);
-  return ctrlsim_launch_status();
-}
-
 int launch_replay_latch_views(int S, int N, int R, int t, int T1, const double* log, const float* phys, double* exist_hist,
                               float* hist_states, float* speed_hist, float* view_states, hipStream_t st) {
   if (S <= 0) return CTRLSIM_OK;
@@ -204,26 +151,52 @@ int launch_replay_latch_views(int S, int N, int R, int t, int T1, const double* 
   if (n * R > 0x7fffffffL - 256) return CTRLSIM_EINVAL;
   if (view_states == hist_states) view_states = nullptr;     // R = 1 on the scene's own tensors: nothing to copy
   if (!view_states && R != 1) return CTRLSIM_EINVAL;
-  hipLaunchKernelGGL(replay_latch_views_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, N, R, t, T1, log, phys,
-                     exist_hist, hist_states, speed_hist, view_states);
+  hipLaunchKernelGGL(replay_latch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, N, R, t, T1, log, phys, exist_hist,
+                     hist_states, speed_hist, view_states);
   return ctrlsim_launch_status();
 }
 
-int launch_replay_actions_views(int S, int N, int R, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
-                                const int* role, const double* exist_hist, const float* hist_states, const float* phys,
-                                const int* act_now, const double* disc6, double* act_f64, unsigned char* exists, int* hist_tok,
-                                int* view_tok, hipStream_t st) {
+int launch_replay_latch(int S, int N, int t, int T1, const double* log, const float* phys, double* exist_hist, float* hist_states,
+                        float* speed_hist, hipStream_t st) {
+  return launch_replay_latch_views(S, N, 1, t, T1, log, phys, exist_hist, hist_states, speed_hist, nullptr, st);
+}
+
+namespace {
+
+// `who` = role [S,N] int32 or controlled [S,N] uint8 (replay_role)
+template <typename Who>
+int launch_actions(int S, int N, int R, int t, int T1, int Tmax, int history_steps, double dt, const double* log, const Who* who,
+                   const double* exist_hist, const float* hist_states, const float* phys, const int* act_now, const double* disc6,
+                   double* act_f64, unsigned char* exists, int* hist_tok, int* view_tok, hipStream_t st) {
   if (S <= 0) return CTRLSIM_OK;
-  if (N < 1 || R < 1 || R > CTRLSIM_MAX_ROLES || t < 0 || t >= Tmax || t + 1 >= T1 || !log || !role || !exist_hist || !hist_states ||
+  if (N < 1 || R < 1 || R > CTRLSIM_MAX_ROLES || t < 0 || t >= Tmax || t + 1 >= T1 || !log || !who || !exist_hist || !hist_states ||
       !phys || !act_now || !disc6 || !act_f64 || !exists || !hist_tok)
     return CTRLSIM_EINVAL;
   const long n = (long)S * N;
   if (n * R > 0x7fffffffL - 256) return CTRLSIM_EINVAL;
   if (view_tok == hist_tok) view_tok = nullptr;
   if (!view_tok && R != 1) return CTRLSIM_EINVAL;
-  ReplayDisc dz{disc6[0], disc6[1], disc6[2], disc6[3], (int)disc6[4], (int)disc6[5]};
+  const ReplayDisc dz{disc6[0], disc6[1], disc6[2], disc6[3], (int)disc6[4], (int)disc6[5]};
   if (dz.n_accel < 2 || dz.n_steer < 2) return CTRLSIM_EINVAL;
-  hipLaunchKernelGGL(replay_actions_views_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, N, R, t, T1, Tmax,
-                     history_steps, dt, log, role, exist_hist, hist_states, phys, act_now, dz, act_f64, exists, hist_tok, view_tok);
+  hipLaunchKernelGGL(replay_actions_kernel<Who>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)n, N, R, t, T1, Tmax,
+                     history_steps, dt, log, who, exist_hist, hist_states, phys, act_now, dz, act_f64, exists, hist_tok, view_tok);
   return ctrlsim_launch_status();
+}
+
+}  // namespace
+
+int launch_replay_actions(int S, int N, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
+                          const unsigned char* controlled, const double* exist_hist, const float* hist_states, const float* phys,
+                          const int* act_now, const double* disc6, double* act_f64, unsigned char* exists, int* hist_tok,
+                          hipStream_t st) {
+  return launch_actions(S, N, 1, t, T1, Tmax, history_steps, dt, log, controlled, exist_hist, hist_states, phys, act_now, disc6, act_f64,
+                        exists, hist_tok, nullptr, st);
+}
+
+int launch_replay_actions_views(int S, int N, int R, int t, int T1, int Tmax, int history_steps, double dt, const double* log,
+                                const int* role, const double* exist_hist, const float* hist_states, const float* phys,
+                                const int* act_now, const double* disc6, double* act_f64, unsigned char* exists, int* hist_tok,
+                                int* view_tok, hipStream_t st) {
+  return launch_actions(S, N, R, t, T1, Tmax, history_steps, dt, log, role, exist_hist, hist_states, phys, act_now, disc6, act_f64, exists,
+                        hist_tok, view_tok, st);
 }

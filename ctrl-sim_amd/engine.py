@@ -471,7 +471,7 @@ class RolloutEngine:
         drives it from step history_steps - 1 on (`controlled` becomes role >= 0); tilts [R,3] = (goal, veh_veh, veh_edge) of every role,
         R <= 4.  run() / run_jobs() / step() then roll every scene with R policy VIEWS: rows s * R + r of the policy-side tensors
         (eval_order = the role's vehicles by decreasing logged length, persist, the group arrays, hist_rtg, act_now, tilt, and copies of
-        the scene's goals, map, state and action history, kept equal to the scene's by csrc/replay.hip's _views kernels) — ordinary
+        the scene's goals, map, state and action history, kept equal to the scene's by csrc/replay.hip's _views entries) — ordinary
         scenarios for the grouping, context, forward and sampling kernels, with the scene's id in the noise key.  The simulator side
         (phys, contacts, collisions, the log, hist_states / hist_tok of the scene) stays [S, ...].  With R = 1 the scene is its own view.
         Not for the Decision-Transformer variant (its RTG rows are the scene's, fed by the reward ledger).

@@ -23,7 +23,7 @@ from scipy.spatial import distance
 
 from .. import scenarios as _scn
 from ..kinematics import bicycle_backward
-from ..simulation import Simulation, CollisionType
+from ..simulation import Simulation
 from .policy_evaluator import PolicyEvaluator
 
 PLANNER_KEYS = {"next_acceleration": "next_planner_acceleration", "next_steering": "next_planner_steering",
@@ -188,10 +188,6 @@ class PlannerAdversaryEvaluator(PolicyEvaluator):
                             bool(q.max_return), bool(q.min_return))
         return ok(ad) and ad.model is pl.model and common(ad) == common(pl)
 
-    @staticmethod
-    def _tilt_of(policy):
-        return (policy.goal_tilt, policy.veh_veh_tilt, policy.veh_edge_tilt) if policy.tilt_dict["tilt"] else (0.0, 0.0, 0.0)
-
     def _evaluate_on_device(self, adv_traj_fn=None):
         """evaluate_planner_adversary with the scenario loop turned inside out (as PolicyEvaluator._evaluate_policy_batched): scenes, ego
         and adversary are chosen exactly as the loop chooses them, then all scenes of equal shape roll in one RolloutEngine batch —
@@ -202,12 +198,9 @@ class PlannerAdversaryEvaluator(PolicyEvaluator):
         rows from history_steps on are the fixed trajectory (replay.merge_cat_log), which the replay branch follows exactly as
         apply_adv_traj does; the statistics keep the unmodified log.  The policy OBJECTS are not driven (no reset / update_state /
         predict calls)."""
-        from ..engine import RolloutEngine
-        from .. import replay
         self.reset()
         syn = self.synthetic
-        pl = self.planner
-        d_model = pl.model.dims
+        d_model = self.planner.model.dims
         cat = self.adversary.name == "cat"
         chosen, n_eval = [], 0
         for k in range(int(syn["num_scenarios"])):
@@ -221,33 +214,21 @@ class PlannerAdversaryEvaluator(PolicyEvaluator):
             adv_traj = adv_traj_fn(scn, gt_data_dict, ego, adv) if cat else None
             n_eval += 1
             chosen.append((scn, gt_data_dict, ego, adv, adv_traj))
-        groups = {}
-        for item in chosen:                                    # one engine batch = scenes of equal vehicle and polyline counts
-            groups.setdefault((item[0].N, item[0].road_points.shape[0]), []).append(item)
-        cap = int(self.cfg_pa.get("batch_scenarios", 256))
-        tilts = [self._tilt_of(pl)] + ([] if cat else [self._tilt_of(self.adversary)])
-        eng = RolloutEngine(pl.model.cfg, pl.model.weights, pl.model.device, max_ctx=int(self.cfg.eval.get("batch_contexts", 256)),
-                            seed=int(self.cfg.eval.seed), temperature=pl.action_temperature, nucleus=pl.nucleus_sampling,
-                            top_p=pl.nucleus_threshold, model=pl.model.hip, lanes=1)
+        eng = self._engine_of(self.planner, lanes=1)
         self.device_replay_scenes = 0
-        for (N, _), items in groups.items():
-            for c0 in range(0, len(items), cap):
-                self._roll_on_device(eng, items[c0:c0 + cap], N, tilts, cat, replay)
+        for items in self._batches(chosen, int(self.cfg_pa.get("batch_scenarios", 256))):
+            self._roll_on_device(eng, items, cat)
         return self.compute_metrics()
 
-    def _roll_on_device(self, eng, items, N, tilts, cat, replay):
+    def _roll_on_device(self, eng, items, cat):
         from .. import discretize as dz
+        from .. import replay
         from ..metrics import nearest_vehicle_distance
         w, T, hs = self.cfg_rl_waymo, self.steps, self.history_steps
-        S, T1 = len(items), T + 1
-        gt = np.zeros((S, N, T1 + 1, 6))                       # x, y, heading, speed, exist, length (+ one row: step t looks at t + 1)
+        S, N, T1 = len(items), items[0][0].N, T + 1
+        gt = replay.log_array([it[1] for it in items], N, T1)
         role = -np.ones((S, N), np.int32)
         for k, (scn, gtd, ego, adv, adv_traj) in enumerate(items):
-            for v in range(N):
-                tr = np.asarray(gtd[v]["traj"], np.float64)
-                n = min(len(tr), T1 + 1)
-                gt[k, v, :n, :5] = tr[:n, :5]
-                gt[k, v, :n, 5] = tr[:n, -1]
             role[k, ego] = 0
             if not cat:
                 role[k, adv] = 1
@@ -256,7 +237,7 @@ class PlannerAdversaryEvaluator(PolicyEvaluator):
             log = np.stack([replay.merge_cat_log(gt[k], it[3], it[4], hs) for k, it in enumerate(items)])
         eng.load_scenarios([it[0] for it in items], steps=T)
         eng.set_log(log, role >= 0, hs)
-        eng.set_roles(role, tilts)
+        eng.set_roles(role, [self._tilt_of(self.planner)] + ([] if cat else [self._tilt_of(self.adversary)]))
         eng.run()
         try:
             eng.check_finite()
@@ -268,46 +249,17 @@ class PlannerAdversaryEvaluator(PolicyEvaluator):
         cont = dz.undiscretize_rtgs(r["rtg_bins_roles"], w)    # [S,R,N,T,3]
         own, sampled = r["own_ctx"], r["sampled_roles"]
         keys = [PLANNER_KEYS] + ([] if cat else [ADVERSARY_KEYS])
-        n_comp = self.planner.cfg_model.num_reward_components
         for k, (scn, gtd, ego, adv, adv_traj) in enumerate(items):
             self.ego_vehicle, self.adversary_vehicle = ego, adv
             ex_k = exist[k].astype(float)
-            nd = nearest_vehicle_distance(states[k, :, :, :2].astype(np.float64), ex_k)
-            gnd = nearest_vehicle_distance(gt[k, :, :T1, :2], ex_k)
-            vdd = {}
-            for v in range(N):
-                veh0 = _NS(getWidth=lambda v=v, scn=scn: float(scn.width[v]), getLength=lambda v=v, scn=scn: float(scn.length[v]))
-                goal = {"pos": scn.goal_pos[v].astype(np.float64), "heading": float(scn.goal_heading[v]), "speed": float(scn.goal_speed[v])}
-                d = self.initialize_vehicle_data_dict(veh0, goal)
-                norm = np.linalg.norm(np.array([states[k, v, 0, 0], states[k, v, 0, 1]]) - goal["pos"])
-                tr = gt[k, v]
-                for t in range(T1):
-                    row = states[k, v, t]                      # float32 scalars, as the Simulation facade hands them to the loop
-                    d["gt_position"].append({"x": tr[t, 0], "y": tr[t, 1]})
-                    d["gt_heading"].append(tr[t, 2])
-                    d["gt_speed"].append(tr[t, 3])
-                    d["gt_acceleration"].append((tr[t + 1, 3] - tr[t - 1, 3]) / (2 * self.dt) if 0 < t < self.steps - 1 else 0)
-                    d["position"].append({"x": row[0], "y": row[1]})
-                    d["velocity"].append({"x": row[2], "y": row[3]})
-                    d["heading"].append(row[4])
-                    d["timestep"].append(t)
-                    d["existence"].append(exist[k, v, t])
-                    veh = _NS(position=_NS(x=row[0], y=row[1]), speed=speeds[k, v, t], heading=row[4],
-                              collision_type_veh=CollisionType.VEHICLE_VEHICLE if coll[k, v, t, 0] else CollisionType.NOT_COLLIDED,
-                              collision_type_edge=CollisionType.VEHICLE_ROAD if coll[k, v, t, 1] else CollisionType.NOT_COLLIDED)
-                    d["reward"].append(self.compute_reward(veh, goal, norm, d))
-                    d["nearest_dist"].append(nd[v, t])
-                    d["gt_nearest_dist"].append(gnd[v, t])
-                    d["acceleration"].append(float(applied[k, v, t, 0]) if t < T else 0)
-                    d["steering"].append(float(applied[k, v, t, 1]) if t < T else 0)
-                    if t < T and self.planner.predict_rtgs:    # AutoregressivePolicy.predict: one RTG row per policy, vehicle and step
-                        for rr, kd in enumerate(keys):
-                            if own[k, rr, v, t] >= 0:
-                                d["next_rtg_goal"], d["next_rtg_veh"], d["next_rtg_road"] = cont[k, rr, v, t]
-                                d[kd["rtgs"]].append(np.array(cont[k, rr, v, t]))
-                            else:
-                                d[kd["rtgs"]].append(np.array([0] * n_comp))
-                vdd[v] = d
+            goals = {v: {"pos": scn.goal_pos[v].astype(np.float64), "heading": float(scn.goal_heading[v]), "speed": float(scn.goal_speed[v])}
+                     for v in range(N)}
+            # (the applied actions as Python floats, as the stepwise loop appends them)
+            one = _NS(states=states[k], coll=coll[k], speeds=speeds[k], exist=exist[k], accel=applied[k, :, :, 0].tolist(),
+                      steer=applied[k, :, :, 1].tolist(), gt=gt[k], rtg=cont[k], own=own[k], keys=keys,
+                      nearest=nearest_vehicle_distance(states[k, :, :, :2].astype(np.float64), ex_k),
+                      gt_nearest=nearest_vehicle_distance(gt[k, :, :T1, :2], ex_k))
+            vdd = self._vehicle_data_dict_of(scn, goals, one)
             for rr, (kd, v) in enumerate(zip(keys, (ego, adv))):   # what the last predict() left for act()
                 tok = int(sampled[k, rr, v, T - 1])
                 a, s_ = dz.undiscretize_actions(np.array([tok]), w)[0] if tok >= 0 else (0.0, 0.0)
@@ -315,6 +267,20 @@ class PlannerAdversaryEvaluator(PolicyEvaluator):
             self.last_vehicle_data_dict = vdd
             self.update_running_statistics(vdd)
             self.device_replay_scenes += 1
+
+    def _append_step_extras(self, d, r, v, t):
+        """What update_vehicle_data_dict adds for this evaluator's statistics, and one RTG row per policy, vehicle and step
+        (r.rtg [R,N,T,3], r.own [R,N,T], r.keys = the roles' key names)."""
+        d["gt_acceleration"].append((r.gt[v, t + 1, 3] - r.gt[v, t - 1, 3]) / (2 * self.dt) if 0 < t < self.steps - 1 else 0)
+        d["nearest_dist"].append(r.nearest[v, t])
+        d["gt_nearest_dist"].append(r.gt_nearest[v, t])
+        if t < self.steps and self.planner.predict_rtgs:
+            for rr, kd in enumerate(r.keys):
+                if r.own[rr, v, t] >= 0:
+                    d["next_rtg_goal"], d["next_rtg_veh"], d["next_rtg_road"] = r.rtg[rr, v, t]
+                    d[kd["rtgs"]].append(np.array(r.rtg[rr, v, t]))
+                else:
+                    d[kd["rtgs"]].append(np.array([0] * self.planner.cfg_model.num_reward_components))
 
     # ---- :202-365
     def update_running_statistics(self, data_dict):

@@ -10,6 +10,7 @@ by the environment: scenarios come from `cfg.eval.synthetic` (no Nocturne JSON /
 from __future__ import annotations
 
 import random
+from types import SimpleNamespace as _NS
 
 import numpy as np
 import torch
@@ -273,9 +274,9 @@ class PolicyEvaluator:
         by one RolloutEngine — one grouping / context / two-pass forward / sampling sequence per step for the whole batch
         (engine.policy_step), the log-replay actions of the vehicles the policy does not control (Evaluator.apply_gt_action,
         evaluators/evaluator.py:160-193: inverse bicycle model against the next logged state) computed for the whole batch in NumPy
-        float64 — the same code, hence the same bits, as the per-scenario route — and one simulator step for the batch.  The statistics
-        are the per-scenario route's (update_running_statistics on the same arrays): the metric dict is identical to it (1e-12: the
-        accumulation order of floating-point sums), at the engine's throughput instead of a host round trip per vehicle and step.
+        float64 (ctrlsim_amd/replay.py: the expressions, hence the bits, of the per-scenario route) and one simulator step for the batch.
+        The statistics are the per-scenario route's (update_running_statistics on the same arrays): the metric dict is identical to it
+        (1e-12: the accumulation order of floating-point sums), at the engine's throughput instead of a host round trip per vehicle and step.
 
         What this route does NOT do: it never drives the `policy` OBJECT — no `policy.reset()` / `update_state()` / `predict()` calls, so
         the policy's own buffers (`policy.states`, `policy.actions`, `policy.rtgs`, ...) keep whatever an earlier per-scenario session
@@ -284,11 +285,7 @@ class PolicyEvaluator:
 
         `cfg.eval.device_replay = True` (default False) rolls every batch as ONE RolloutEngine.run() with the log attached: the per-step
         NumPy work above runs on the device (_roll_batch_on_device, csrc/replay.hip) and the host reads the rollout back once."""
-        from .. import discretize as dz
-        from ..engine import RolloutEngine
         self.reset()
-        pol, w = self.policy, self.cfg_rl_waymo
-        T, T1, hsteps = self.steps, self.steps + 1, self.history_steps
         chosen, n_done = [], 0
         for scn, gt_data_dict, moving, pre in self._scenes(self.synthetic):
             if n_done == self.cfg.eval.num_files_to_evaluate // self.cfg.eval.partitions:
@@ -298,37 +295,48 @@ class PolicyEvaluator:
                 continue
             n_done += 1
             chosen.append((scn, gt_data_dict, list(to_eval)))
-        groups = {}
-        for item in chosen:                                    # one engine batch = scenes of equal vehicle and polyline counts
-            groups.setdefault((item[0].N, item[0].road_points.shape[0]), []).append(item)
-        tilt = (pol.goal_tilt, pol.veh_veh_tilt, pol.veh_edge_tilt) if pol.tilt_dict["tilt"] else (0.0, 0.0, 0.0)
-        cap = int(self.cfg.eval.get("batch_scenarios", 256))
         self.batched_scenes = 0
         self._batch_engine = None
         try:
-            for (N, _), items in groups.items():
-                for c0 in range(0, len(items), cap):
-                    self._roll_batch(items[c0:c0 + cap], N, tilt, dz, RolloutEngine, w, T, T1, hsteps)
+            for items in self._batches(chosen, int(self.cfg.eval.get("batch_scenarios", 256))):
+                self._roll_batch(items)
         finally:
             self._batch_engine = None                          # the workspace goes back to torch's allocator with the evaluation
         return self.compute_metrics()
 
-    def _roll_batch(self, items, N, tilt, dz, RolloutEngine, w, T, T1, hsteps):
+    # ---- shared with PlannerAdversaryEvaluator's engine route
+    @staticmethod
+    def _batches(chosen, cap):
+        """One engine batch = scenes (items whose first element is the scenario) of equal vehicle and polyline counts, at most `cap`."""
+        groups = {}
+        for item in chosen:
+            groups.setdefault((item[0].N, item[0].road_points.shape[0]), []).append(item)
+        for items in groups.values():
+            for c0 in range(0, len(items), cap):
+                yield items[c0:c0 + cap]
+
+    @staticmethod
+    def _tilt_of(policy):
+        return (policy.goal_tilt, policy.veh_veh_tilt, policy.veh_edge_tilt) if policy.tilt_dict["tilt"] else (0.0, 0.0, 0.0)
+
+    def _engine_of(self, pol, **kw):
+        """A RolloutEngine on the policy's model, sampling as the policy samples."""
+        from ..engine import RolloutEngine
+        return RolloutEngine(pol.model.cfg, pol.model.weights, pol.model.device, max_ctx=int(self.cfg.eval.get("batch_contexts", 256)),
+                             seed=int(self.cfg.eval.seed), temperature=pol.action_temperature, nucleus=pol.nucleus_sampling,
+                             top_p=pol.nucleus_threshold, model=pol.model.hip, **kw)
+
+    def _prepare_batch(self, items):
+        """items = [(scenario, gt_data_dict, vehicles to evaluate)] -> the batch record the rolled arrays are added to: scns (the scenes as
+        the policy sees them), goal_dicts, gt [S,N,T1+1,6] (replay.log_array), ctrl [S,N] = vehicles_to_evaluate."""
         import copy
-        pol = self.policy
-        S = len(items)
-        gt = np.zeros((S, N, T1 + 1, 6))                       # x, y, heading, speed, exist, length (+ one row: apply_gt_action looks at t + 1)
-        scns, goal_dicts, evals = [], [], []
-        ctrl = np.zeros((S, N), bool)                          # vehicles_to_evaluate
+        from .. import replay
+        N = items[0][0].N
+        b = _NS(items=items, scns=[], goal_dicts=[], ctrl=np.zeros((len(items), N), bool),
+                gt=replay.log_array([gtd for _, gtd, _ in items], N, self.steps + 1))
         for k, (scn, gtd, to_eval) in enumerate(items):
             ids = list(range(scn.N))                           # Simulation's vehicle ids are the indices (synthetic) / follow the loader's order
-            gd = {}
-            for v in ids:
-                tr = np.asarray(gtd[v]["traj"], np.float64)
-                n = min(len(tr), T1 + 1)
-                gt[k, v, :n, :5] = tr[:n, :5]
-                gt[k, v, :n, 5] = tr[:n, -1]
-                gd[v] = self.initialize_goal_dict(scn, v, tr)
+            gd = {v: self.initialize_goal_dict(scn, v, np.asarray(gtd[v]["traj"], np.float64)) for v in ids}
             # the policy sees the goals the evaluator works with (initialize_goal_dict moves the goal of a vehicle that leaves the log)
             s2 = copy.copy(scn)
             s2.goal_pos = np.array([gd[v]["pos"] for v in ids], np.float32)
@@ -337,31 +345,35 @@ class PolicyEvaluator:
             # processing order of the vehicles to evaluate: decreasing ground-truth length (autoregressive_policy.py:88-94)
             lengths = [int(np.asarray(gtd[v]["traj"])[:, 4].sum()) for v in to_eval]
             s2.eval_order = np.array(to_eval)[np.argsort(np.array(lengths))[::-1]].astype(np.int32)
-            scns.append(s2); goal_dicts.append(gd); evals.append(to_eval)
-            ctrl[k, to_eval] = True
+            b.scns.append(s2); b.goal_dicts.append(gd)
+            b.ctrl[k, to_eval] = True
+        return b
+
+    def _roll_batch(self, items):
+        import time
+        from .. import replay
+        b = self._prepare_batch(items)
+        gt, ctrl = b.gt, b.ctrl
+        S, N = ctrl.shape
+        T, T1, hsteps, w = self.steps, self.steps + 1, self.history_steps, self.cfg_rl_waymo
         # ONE engine for every group / chunk of the evaluation (its workspace — the expensive allocation — depends on the model batch only;
         # load_scenarios re-sizes the per-scenario tensors for each batch)
         eng = getattr(self, "_batch_engine", None)
         if eng is None:
-            eng = self._batch_engine = RolloutEngine(pol.model.cfg, pol.model.weights, pol.model.device,
-                                                     max_ctx=int(self.cfg.eval.get("batch_contexts", 256)), seed=int(self.cfg.eval.seed), tilt=tilt,
-                                                     temperature=pol.action_temperature, nucleus=pol.nucleus_sampling,
-                                                     top_p=pol.nucleus_threshold, model=pol.model.hip, lanes=1)
-        eng.load_scenarios(scns, steps=T)
+            eng = self._batch_engine = self._engine_of(self.policy, tilt=self._tilt_of(self.policy), lanes=1)
+        eng.load_scenarios(b.scns, steps=T)
         if bool(self.cfg.eval.get("device_replay", False)):
-            return self._roll_batch_on_device(eng, items, goal_dicts, gt, ctrl, N, dz, w, T, hsteps)
+            return self._roll_batch_on_device(eng, b)
         dev = eng.device
-        exist = np.zeros((S, N, T1))
-        accel = np.zeros((S, N, T1))
-        steer = np.zeros((S, N, T1))
-        speeds = np.zeros((S, N, T1), np.float32)
-        own_last = np.zeros((T, N), np.int32)                  # last scene of the batch: does a context answer for the vehicle at step t
-        import time
+        b.exist = exist = np.zeros((S, N, T1))
+        b.accel, b.steer = np.zeros((S, N, T1)), np.zeros((S, N, T1))
+        b.speeds = np.zeros((S, N, T1), np.float32)
+        b.own_last = np.zeros((T, N), np.int32)                # last scene of the batch: does a context answer for the vehicle at step t
         tm = self.batched_timing = {"policy_step_enqueue": 0.0, "read_back": 0.0, "host_actions": 0.0, "upload_and_sim": 0.0}
         for t in range(T):
             t_a = time.perf_counter()
             # update_vehicle_data_dict (:99-159): existence = the log's flag, latched at 0
-            exist[:, :, t] = gt[:, :, t, 4] if t == 0 else gt[:, :, t, 4] * (exist[:, :, t - 1] != 0)
+            exist[:, :, t] = replay.latch(gt, t, exist[:, :, t - 1] if t else None)
             eng.hist_states[:, :, t, 7] = torch.from_numpy(exist[:, :, t].astype(np.float32)).to(dev)
             eng.policy_step(t)
             t_b = time.perf_counter()
@@ -378,127 +390,122 @@ class PolicyEvaluator:
             if bad:
                 raise FloatingPointError(f"{bad} guard events at step {t} of the batched evaluation (csrc/split.h: activation range; csrc/sim.hip: "
                                          f"contact table) in the batch of scenes {[int(getattr(it[0], 'index', -1)) for it in items]}")
-            speeds[:, :, t] = speed
-            own_last[t] = eng.own_ctx[S - 1].cpu().numpy()
-            a = np.zeros((S, N)); st = np.zeros((S, N)); alive = np.ones((S, N), bool)
-            by_policy = ctrl & (t >= hsteps - 1)
-            # policy.act (autoregressive_policy.py:256-274): a vehicle that does not exist any more is parked; a vehicle no context
-            # answers for (dead_agent_veh_ids) gets (0, 0)
-            und = dz.undiscretize_actions(np.maximum(toks, 0), w)
-            live = by_policy & (exist[:, :, t] != 0)
-            a[live], st[live] = np.where(toks[live] >= 0, und[live][:, 0], 0.0), np.where(toks[live] >= 0, und[live][:, 1], 0.0)
-            alive[by_policy & (exist[:, :, t] == 0)] = False
-            # apply_gt_action (evaluators/evaluator.py:160-193) for everyone else
-            rep = ~by_policy
-            ok = rep & (gt[:, :, t, 4] != 0) & (gt[:, :, t + 1, 4] != 0) & ~((t > 0) & (exist[:, :, t] == 0))
-            if ok.any():
-                nxt = np.concatenate([gt[:, :, t + 1, :4][ok], gt[:, :, t + 1, 5][ok][:, None]], 1)
-                prev = np.stack([row[..., 0][ok], row[..., 1][ok], row[..., 4][ok], speed[ok]], 1).astype(np.float64)
-                a[ok], st[ok] = bicycle_backward(nxt, prev, self.dt)
-            alive[rep & ~ok] = False
-            accel[:, :, t] = a
-            steer[:, :, t] = st
+            b.speeds[:, :, t] = speed
+            b.own_last[t] = eng.own_ctx[S - 1].cpu().numpy()
+            # policy.act for the vehicles to evaluate, apply_gt_action for everyone else, and what update_state writes back as the action
+            # history of step t: the applied action, discretised (identity for a sampled token)
+            act, alive, tok = replay.actions(gt, ctrl, exist[:, :, t], t, hsteps, heading=row[..., 4], speed=speed, act_now=toks, dt=self.dt, w=w)
+            b.accel[:, :, t], b.steer[:, :, t] = act[..., 0], act[..., 1]
             t_d = time.perf_counter()
-            act = torch.from_numpy(np.stack([a, st], -1)).to(dev)
-            # what update_state writes back as the action history of step t: the applied action, discretised (identity for a sampled token)
-            eng.hist_tok[:, :, t] = torch.from_numpy(dz.discretize_actions(np.stack([a, st], -1), w).astype(np.int32)).to(dev)
+            eng.hist_tok[:, :, t] = torch.from_numpy(tok).to(dev)
             eng.exists.copy_(torch.from_numpy(alive.astype(np.uint8)).to(dev))
-            eng.sim_step(t, act)
+            eng.sim_step(t, torch.from_numpy(act).to(dev))
             t_e = time.perf_counter()
             tm["policy_step_enqueue"] += t_b - t_a; tm["read_back"] += t_c - t_b; tm["host_actions"] += t_d - t_c; tm["upload_and_sim"] += t_e - t_d
-        exist[:, :, T] = gt[:, :, T, 4] * (exist[:, :, T - 1] != 0)
-        states = eng.hist_states.cpu().numpy()
-        coll = eng.coll.cpu().numpy()
-        speeds[:, :, T] = eng.phys[:, :, 16].cpu().numpy()
-        self._feed_batch(items, goal_dicts, states, coll, speeds, exist, accel, steer, gt, eng.hist_rtg[S - 1].cpu().numpy(), own_last, dz, w, T, N)
+        exist[:, :, T] = replay.latch(gt, T, exist[:, :, T - 1])
+        b.states = eng.hist_states.cpu().numpy()
+        b.coll = eng.coll.cpu().numpy()
+        b.speeds[:, :, T] = eng.phys[:, :, 16].cpu().numpy()
+        b.rtg_last = eng.hist_rtg[S - 1].cpu().numpy()
+        self._feed_batch(b)
 
-    def _roll_batch_on_device(self, eng, items, goal_dicts, gt, ctrl, N, dz, w, T, hsteps):
+    def _roll_batch_on_device(self, eng, b):
         """cfg.eval.device_replay: the batch as ONE RolloutEngine.run() — the log, the controlled vehicles and history_steps are attached to
         the engine (engine.set_log) and the per-step decisions of the loop in _roll_batch (existence latch, policy or log, the inverse
         bicycle model, the action-history tokens) run on the device between the engine's own launches (csrc/replay.hip), K/V-cached steps
         included.  One read-back after the run, one check_finite() (which repeats the run with the range-safe operand split if the fast
         one overflowed); statistics and `last_vehicle_data_dict` are fed exactly as by the step-by-step route."""
         import time
-        S, T1 = len(items), T + 1
+        S, N = b.ctrl.shape
+        T = self.steps
         t_a = time.perf_counter()
-        eng.set_log(gt, ctrl, hsteps)
+        eng.set_log(b.gt, b.ctrl, self.history_steps)
         eng.run()
         t_b = time.perf_counter()
         try:
             eng.check_finite()
         except FloatingPointError as e:
-            raise FloatingPointError(f"{e} — batch of scenes {[int(getattr(it[0], 'index', -1)) for it in items]}") from None
+            raise FloatingPointError(f"{e} — batch of scenes {[int(getattr(it[0], 'index', -1)) for it in b.items]}") from None
         t_c = time.perf_counter()
-        states = eng.hist_states.cpu().numpy()
-        coll = eng.coll.cpu().numpy()
-        speeds = eng.speed_hist.cpu().numpy()
+        b.states = eng.hist_states.cpu().numpy()
+        b.coll = eng.coll.cpu().numpy()
+        b.speeds = eng.speed_hist.cpu().numpy()
         applied = eng.applied_steps.cpu().numpy()                      # [T, S, N, 2]
-        exist = eng.exist_hist.cpu().numpy()
-        rtg_last = eng.hist_rtg[S - 1].cpu().numpy()
-        own_last = eng.own_ctx_steps[:, S - 1].cpu().numpy()           # [T, N]
-        accel = np.zeros((S, N, T1))
-        steer = np.zeros((S, N, T1))
-        accel[:, :, :T] = applied[..., 0].transpose(1, 2, 0)
-        steer[:, :, :T] = applied[..., 1].transpose(1, 2, 0)
+        b.exist = eng.exist_hist.cpu().numpy()
+        b.rtg_last = eng.hist_rtg[S - 1].cpu().numpy()
+        b.own_last = eng.own_ctx_steps[:, S - 1].cpu().numpy()         # [T, N]
+        b.accel, b.steer = np.zeros((S, N, T + 1)), np.zeros((S, N, T + 1))
+        b.accel[:, :, :T] = applied[..., 0].transpose(1, 2, 0)
+        b.steer[:, :, :T] = applied[..., 1].transpose(1, 2, 0)
         t_d = time.perf_counter()
         self.device_replay_timing = {"enqueue": t_b - t_a, "wait_and_check": t_c - t_b, "read_back": t_d - t_c}
         # what this route read back, batch by batch: the arrays the statistics below are built from
-        rb = dict(states=states, coll=coll, speeds=speeds, accel=accel, steer=steer, exist=exist, gt=gt, controlled=ctrl.copy(),
-                  goal_dicts=goal_dicts, to_eval=[list(it[2]) for it in items], rtg_last=rtg_last, own_last=own_last)
+        rb = dict(states=b.states, coll=b.coll, speeds=b.speeds, accel=b.accel, steer=b.steer, exist=b.exist, gt=b.gt,
+                  controlled=b.ctrl.copy(), goal_dicts=b.goal_dicts, to_eval=[list(it[2]) for it in b.items], rtg_last=b.rtg_last,
+                  own_last=b.own_last)
         if not hasattr(self, "device_replay_readback") or self.batched_scenes == 0:
             self.device_replay_readback = []
         self.device_replay_readback.append(rb)
-        self._feed_batch(items, goal_dicts, states, coll, speeds, exist, accel, steer, gt, rtg_last, own_last, dz, w, T, N)
+        self._feed_batch(b)
 
-    def _feed_batch(self, items, goal_dicts, states, coll, speeds, exist, accel, steer, gt, rtg_last, own_last, dz, w, T, N):
+    def _feed_batch(self, b):
         """A rolled batch -> `last_vehicle_data_dict` (its last scene) and the running statistics (update_running_statistics on arrays)."""
-        S, T1 = len(items), T + 1
-        self.last_vehicle_data_dict = self._vehicle_data_dict_of(S - 1, items[S - 1][0], goal_dicts[S - 1], states, coll, speeds, exist, accel, steer, gt,
-                                                                 rtg_last, own_last, dz, w, T)
-        for k, (scn, gtd, to_eval) in enumerate(items):
+        from .. import discretize as dz
+        S, N = b.ctrl.shape
+        T1 = self.steps + 1
+        k = S - 1
+        last = _NS(states=b.states[k], coll=b.coll[k], speeds=b.speeds[k], exist=b.exist[k], accel=b.accel[k], steer=b.steer[k], gt=b.gt[k],
+                   rtg=dz.undiscretize_rtgs(b.rtg_last, self.cfg_rl_waymo) if self.policy.predict_rtgs else None, own=b.own_last)
+        self.last_vehicle_data_dict = self._vehicle_data_dict_of(b.items[k][0], b.goal_dicts[k], last)
+        for k, (scn, gtd, to_eval) in enumerate(b.items):
             stt = np.zeros((N, T1, 8))
-            stt[..., :5] = states[k, :, :, :5]
-            stt[..., 7] = exist[k]
-            g = gt[k, :, :T1, :5]
+            stt[..., :5] = b.states[k, :, :, :5]
+            stt[..., 7] = b.exist[k]
+            g = b.gt[k, :, :T1, :5]
             ids = list(range(N))
-            gp = np.array([np.asarray(goal_dicts[k][v]["pos"], np.float64) for v in ids])
-            gh = np.array([float(goal_dicts[k][v]["heading"]) for v in ids])
-            gs = np.array([float(goal_dicts[k][v]["speed"]) for v in ids])
+            gp = np.array([np.asarray(b.goal_dicts[k][v]["pos"], np.float64) for v in ids])
+            gh = np.array([float(b.goal_dicts[k][v]["heading"]) for v in ids])
+            gs = np.array([float(b.goal_dicts[k][v]["speed"]) for v in ids])
             self.vehicles_to_evaluate = to_eval
-            self.acc.add_scenario(stt, coll[k].astype(np.float64), accel[k], g, gp, gh, gs, self.cfg, eval_ids=[ids.index(v) for v in to_eval])
+            self.acc.add_scenario(stt, b.coll[k].astype(np.float64), b.accel[k], g, gp, gh, gs, self.cfg, eval_ids=[ids.index(v) for v in to_eval])
             self.batched_scenes += 1
 
-    def _vehicle_data_dict_of(self, k, scn, goal_dict, states, coll, speeds, exist, accel, steer, gt, rtg_bins, own, dz, w, T):
-        """`last_vehicle_data_dict` of the batched route: scene k's rollout in the per-scenario loop's dict schema
-        (policy_evaluator.py:70-96) — what a caller inspecting the evaluator after evaluate_policy() reads."""
-        from types import SimpleNamespace as NS
+    def _vehicle_data_dict_of(self, scn, goal_dict, r):
+        """One rolled scene in the per-scenario loop's dict schema (policy_evaluator.py:70-96) — what a caller inspecting the evaluator
+        after the evaluation reads as `last_vehicle_data_dict`.  r = the scene's read-back arrays: states [N,T1,8], coll [N,T1,2],
+        speeds / exist [N,T1], accel / steer [N][>= T], gt [N,T1+1,6], and whatever _append_step_extras reads.  (compute_reward reads
+        d["reward"] only: the other lists may be appended in any order.)"""
+        T = self.steps
         vdd = {}
-        cont = dz.undiscretize_rtgs(rtg_bins, w) if self.policy.predict_rtgs else None
         for v in range(scn.N):
-            veh0 = NS(getWidth=lambda v=v: float(scn.width[v]), getLength=lambda v=v: float(scn.length[v]))
+            veh0 = _NS(getWidth=lambda v=v: float(scn.width[v]), getLength=lambda v=v: float(scn.length[v]))
             d = self.initialize_vehicle_data_dict(veh0, goal_dict[v])
-            norm = np.linalg.norm(np.array([states[k, v, 0, 0], states[k, v, 0, 1]]) - goal_dict[v]["pos"])
+            norm = np.linalg.norm(np.array([r.states[v, 0, 0], r.states[v, 0, 1]]) - goal_dict[v]["pos"])
             for t in range(T + 1):
-                r = states[k, v, t]
-                d["position"].append({"x": r[0], "y": r[1]})
-                d["velocity"].append({"x": r[2], "y": r[3]})
-                d["heading"].append(r[4])
+                row = r.states[v, t]                           # float32 scalars, as the Simulation facade hands them to the loop
+                d["position"].append({"x": row[0], "y": row[1]})
+                d["velocity"].append({"x": row[2], "y": row[3]})
+                d["heading"].append(row[4])
                 d["timestep"].append(t)
-                d["existence"].append(exist[k, v, t])
-                d["gt_position"].append({"x": gt[k, v, t, 0], "y": gt[k, v, t, 1]})
-                d["gt_heading"].append(gt[k, v, t, 2])
-                d["gt_speed"].append(gt[k, v, t, 3])
-                d["acceleration"].append(accel[k, v, t] if t < T else 0)
-                d["steering"].append(steer[k, v, t] if t < T else 0)
-                veh = NS(position=NS(x=r[0], y=r[1]), speed=speeds[k, v, t], heading=r[4],
-                         collision_type_veh=CollisionType.VEHICLE_VEHICLE if coll[k, v, t, 0] else CollisionType.NOT_COLLIDED,
-                         collision_type_edge=CollisionType.VEHICLE_ROAD if coll[k, v, t, 1] else CollisionType.NOT_COLLIDED)
+                d["existence"].append(r.exist[v, t])
+                d["gt_position"].append({"x": r.gt[v, t, 0], "y": r.gt[v, t, 1]})
+                d["gt_heading"].append(r.gt[v, t, 2])
+                d["gt_speed"].append(r.gt[v, t, 3])
+                d["acceleration"].append(r.accel[v][t] if t < T else 0)
+                d["steering"].append(r.steer[v][t] if t < T else 0)
+                veh = _NS(position=_NS(x=row[0], y=row[1]), speed=r.speeds[v, t], heading=row[4],
+                          collision_type_veh=CollisionType.VEHICLE_VEHICLE if r.coll[v, t, 0] else CollisionType.NOT_COLLIDED,
+                          collision_type_edge=CollisionType.VEHICLE_ROAD if r.coll[v, t, 1] else CollisionType.NOT_COLLIDED)
                 d["reward"].append(self.compute_reward(veh, goal_dict[v], norm, d))
-                if cont is not None and t < T:
-                    d[self.policy.key_dict["rtgs"]].append(np.array(cont[v, t]) if own[t, v] >= 0 else
-                                                           np.array([0] * self.policy.cfg_model.num_reward_components))
+                self._append_step_extras(d, r, v, t)
             vdd[v] = d
         return vdd
+
+    def _append_step_extras(self, d, r, v, t):
+        """AutoregressivePolicy.predict: the RTG the policy predicted for step t (r.rtg [N,T,3], r.own [T,N]: < 0 = no context answered)."""
+        if r.rtg is not None and t < self.steps:
+            d[self.policy.key_dict["rtgs"]].append(np.array(r.rtg[v, t]) if r.own[t, v] >= 0 else
+                                                   np.array([0] * self.policy.cfg_model.num_reward_components))
 
     def _evaluate_policy_per_scenario(self):
         self.reset()

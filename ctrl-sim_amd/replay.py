@@ -9,12 +9,25 @@ per step t, the same two the engine queues around its launches (include/ctrlsim.
 
 Arrays: log [..., T1 + 1, 6] = x, y, heading, speed, exist, length (zero rows past the end of a vehicle's log),
 controlled [...] bool, exist_t / exist_prev [...] float64.  Built from kinematics.bicycle_backward and discretize.*, the
-functions the step-by-step evaluator route calls.
+functions the per-scenario loop calls; the host-driven batched route (PolicyEvaluator._roll_batch) calls latch / actions themselves.
 """
 import numpy as np
 
 from . import discretize as dz
 from .kinematics import bicycle_backward
+
+
+def log_array(gt_data_dicts, N, T1):
+    """The logs of S scenes, gt_data_dicts[k][v]["traj"] = rows of x, y, heading, speed, exist, ..., length, as [S, N, T1 + 1, 6]
+    (T1 = steps + 1; one row more: step t looks at t + 1): a longer log is truncated, zero rows (existence 0) past the end of a shorter one."""
+    log = np.zeros((len(gt_data_dicts), N, T1 + 1, 6))
+    for k, gtd in enumerate(gt_data_dicts):
+        for v in range(N):
+            tr = np.asarray(gtd[v]["traj"], np.float64)
+            n = min(len(tr), T1 + 1)
+            log[k, v, :n, :5] = tr[:n, :5]
+            log[k, v, :n, 5] = tr[:n, -1]
+    return log
 
 
 def latch(log, t, exist_prev=None):

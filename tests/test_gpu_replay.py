@@ -1,8 +1,6 @@
 """GPU: device-side log replay — the kernels of csrc/replay.hip through the C ABI against their host form (ctrlsim_amd/replay.py),
 RolloutEngine.run() with a log attached against the host-driven stepping of PolicyEvaluator._roll_batch, scheduling invariance of a
 logged batch, and the evaluator's cfg.eval.device_replay route."""
-import copy
-
 import numpy as np
 import pytest
 import torch
@@ -11,27 +9,13 @@ pytestmark = pytest.mark.gpu
 
 from helpers import cfg_of, golden  # noqa: E402
 from gpu_utils import DEV, dev  # noqa: E402
-from ctrlsim_amd import _lib, spec, replay, discretize as dz  # noqa: E402
-from ctrlsim_amd.engine import RolloutEngine  # noqa: E402
-from ctrlsim_amd.kinematics import bicycle_backward  # noqa: E402
+from replay_utils import ULP, _ulps, _disc6, _cut_logs, engine_of as _engine, host_driven, assert_rollouts_agree  # noqa: E402
+from ctrlsim_amd import _lib, spec, replay  # noqa: E402
+from ctrlsim_amd.kinematics import bicycle_backward  # noqa: E402  (the fixture test's host check of its narrowed rows)
 from ctrlsim_amd.metrics import MetricAccumulators  # noqa: E402
 from ctrlsim_amd.models import CtRLSim  # noqa: E402
 from ctrlsim_amd.policies import AutoregressivePolicy  # noqa: E402
 from ctrlsim_amd.evaluators import PolicyEvaluator  # noqa: E402
-
-ULP = 8          # steer: device atan within OpenCL's 5 ulp of the true value, glibc's within 1; every operation before it is identical
-
-
-def _ulps(a, b):
-    """|a - b| in units of the spacing of float64 at max(|a|, |b|) (0 where both are equal, signed zeros included)."""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    sp = np.spacing(np.maximum(np.abs(a), np.abs(b)))
-    return np.where(a == b, 0.0, np.abs(a - b) / sp)
-
-
-def _disc6(w):
-    import ctypes as C
-    return (C.c_double * 6)(w.min_accel, w.max_accel, w.min_steer, w.max_steer, w.accel_discretization, w.steer_discretization)
 
 
 def _device_step(log, ctrl, exist_prev, t, T1, hsteps, heading32, speed32, toks, dt, w):
@@ -230,11 +214,10 @@ def _cfg64(device_replay=None):
 
 
 def _logged_batch(ev, limit=None, cut=None):
-    """The batch PolicyEvaluator._evaluate_policy_batched / _roll_batch build: scenes (goals moved as initialize_goal_dict does,
-    eval_order by decreasing log length), gt [S,N,T1+1,6], controlled [S,N], goal dicts, the drawn vehicles.
+    """The batch PolicyEvaluator._evaluate_policy_batched / _roll_batch build (ev._prepare_batch): scenes (goals moved as
+    initialize_goal_dict does, eval_order by decreasing log length), gt [S,N,T1+1,6], controlled [S,N], goal dicts, the drawn vehicles.
     cut(k, v, traj) -> traj: shorten / blank a vehicle's log (tests of vehicles that leave)."""
     ev.reset()
-    T1 = ev.steps + 1
     items = []
     for scn, gtd, moving, pre in ev._scenes(ev.synthetic):
         if limit is not None and len(items) == limit:
@@ -242,79 +225,20 @@ def _logged_batch(ev, limit=None, cut=None):
         to_eval = ev._choose_vehicles(scn, gtd, moving)
         if to_eval:
             items.append((scn, gtd, list(to_eval)))
-    S, N = len(items), items[0][0].N
-    gt = np.zeros((S, N, T1 + 1, 6))
-    ctrl = np.zeros((S, N), bool)
-    scns, goal_dicts = [], []
-    for k, (scn, gtd, to_eval) in enumerate(items):
-        gd = {}
-        for v in range(N):
-            tr = np.asarray(gtd[v]["traj"], np.float64)
-            if cut is not None:
-                tr = cut(k, v, tr.copy())
-                gtd[v]["traj"] = tr
-            n = min(len(tr), T1 + 1)
-            gt[k, v, :n, :5] = tr[:n, :5]
-            gt[k, v, :n, 5] = tr[:n, -1]
-            gd[v] = ev.initialize_goal_dict(scn, v, tr)
-        s2 = copy.copy(scn)
-        s2.goal_pos = np.array([gd[v]["pos"] for v in range(N)], np.float32)
-        s2.goal_heading = np.array([gd[v]["heading"] for v in range(N)], np.float32)
-        s2.goal_speed = np.array([gd[v]["speed"] for v in range(N)], np.float32)
-        lengths = [int(np.asarray(gtd[v]["traj"])[:, 4].sum()) for v in to_eval]
-        s2.eval_order = np.array(to_eval)[np.argsort(np.array(lengths))[::-1]].astype(np.int32)
-        scns.append(s2); goal_dicts.append(gd)
-        ctrl[k, to_eval] = True
-    return scns, gt, ctrl, goal_dicts, items
-
-
-def _engine(ev, **kw):
-    pol = ev.policy
-    tilt = (pol.goal_tilt, pol.veh_veh_tilt, pol.veh_edge_tilt)
-    return RolloutEngine(pol.model.cfg, pol.model.weights, pol.model.device, max_ctx=int(ev.cfg.eval.get("batch_contexts", 256)),
-                         seed=int(ev.cfg.eval.seed), tilt=tilt, temperature=pol.action_temperature, nucleus=pol.nucleus_sampling,
-                         top_p=pol.nucleus_threshold, model=pol.model.hip, **kw)
+    if cut is not None:
+        for k, (scn, gtd, to_eval) in enumerate(items):
+            for v in range(scn.N):
+                gtd[v]["traj"] = cut(k, v, np.asarray(gtd[v]["traj"], np.float64).copy())
+    b = ev._prepare_batch(items)
+    return b.scns, b.gt, b.ctrl, b.goal_dicts, items
 
 
 def _host_driven(eng, gt, ctrl, hsteps, dt, w):
-    """What PolicyEvaluator._roll_batch does per step: policy_step, read-backs, NumPy float64 actions, uploads, sim_step."""
-    S, N = ctrl.shape
-    T = eng.steps
-    T1 = T + 1
-    d = eng.device
-    exist = np.zeros((S, N, T1)); accel = np.zeros((S, N, T)); steer = np.zeros((S, N, T))
-    sampled = np.zeros((S, N, T), np.int32)
-    for t in range(T):
-        exist[:, :, t] = gt[:, :, t, 4] if t == 0 else gt[:, :, t, 4] * (exist[:, :, t - 1] != 0)
-        eng.hist_states[:, :, t, 7] = torch.from_numpy(exist[:, :, t].astype(np.float32)).to(d)
-        eng.policy_step(t)
-        row = eng.hist_states[:, :, t].cpu().numpy()
-        toks = eng.act_now.cpu().numpy()
-        speed = eng.phys[:, :, 16].cpu().numpy()
-        assert eng.nonfinite() == 0
-        sampled[:, :, t] = toks
-        a = np.zeros((S, N)); st = np.zeros((S, N)); alive = np.ones((S, N), bool)
-        by_policy = ctrl & (t >= hsteps - 1)
-        und = dz.undiscretize_actions(np.maximum(toks, 0), w)
-        live = by_policy & (exist[:, :, t] != 0)
-        a[live], st[live] = np.where(toks[live] >= 0, und[live][:, 0], 0.0), np.where(toks[live] >= 0, und[live][:, 1], 0.0)
-        alive[by_policy & (exist[:, :, t] == 0)] = False
-        rep = ~by_policy
-        ok = rep & (gt[:, :, t, 4] != 0) & (gt[:, :, t + 1, 4] != 0) & ~((t > 0) & (exist[:, :, t] == 0))
-        if ok.any():
-            nxt = np.concatenate([gt[:, :, t + 1, :4][ok], gt[:, :, t + 1, 5][ok][:, None]], 1)
-            prev = np.stack([row[..., 0][ok], row[..., 1][ok], row[..., 4][ok], speed[ok]], 1).astype(np.float64)
-            a[ok], st[ok] = bicycle_backward(nxt, prev, dt)
-        alive[rep & ~ok] = False
-        accel[:, :, t] = a; steer[:, :, t] = st
-        act = torch.from_numpy(np.stack([a, st], -1)).to(d)
-        eng.hist_tok[:, :, t] = torch.from_numpy(dz.discretize_actions(np.stack([a, st], -1), w).astype(np.int32)).to(d)
-        eng.exists.copy_(torch.from_numpy(alive.astype(np.uint8)).to(d))
-        eng.sim_step(t, act)
-    exist[:, :, T] = gt[:, :, T, 4] * (exist[:, :, T - 1] != 0)
-    eng.hist_states[:, :, T, 7] = torch.from_numpy(exist[:, :, T].astype(np.float32)).to(d)
-    return dict(tokens=eng.hist_tok.cpu().numpy(), rtg_bins=eng.hist_rtg.cpu().numpy(), states=eng.hist_states.cpu().numpy(),
-                coll=eng.coll.cpu().numpy(), existence=exist, applied=np.stack([accel, steer], -1), sampled=sampled)
+    """What PolicyEvaluator._roll_batch does per step (replay_utils.host_driven on one engine): policy_step, read-backs, NumPy float64
+    actions, uploads, sim_step."""
+    out = host_driven([eng], gt, np.where(ctrl, 0, -1), hsteps, dt, w)
+    out["sampled"], out["rtg_bins"] = out["sampled_roles"][:, 0], out["rtg_bins_roles"][:, 0]
+    return out
 
 
 def _report_token_difference(a, b, ctrl, hsteps):
@@ -334,16 +258,7 @@ def _report_token_difference(a, b, ctrl, hsteps):
 def _assert_rollouts_agree(host, devr, ctrl, hsteps, what):
     """The agreement the host-driven and the device-side replay owe each other."""
     assert np.array_equal(host["sampled"], devr["sampled"]), _report_token_difference(host, devr, ctrl, hsteps)
-    for k in ("tokens", "rtg_bins", "existence", "coll"):
-        assert np.array_equal(host[k], devr[k]), (what, k)
-    assert np.array_equal(host["states"][..., 7], devr["states"][..., 7])
-    identical = np.array_equal(host["states"], devr["states"])
-    print(f"{what}: states bit-identical: {identical}; largest difference {np.abs(host['states'] - devr['states']).max():.3g}")
-    np.testing.assert_allclose(devr["states"], host["states"], rtol=0, atol=1e-4)
-    assert np.array_equal(host["applied"][..., 0].view(np.int64), devr["applied"][..., 0].view(np.int64)), f"{what}: applied accel"
-    u = _ulps(host["applied"][..., 1], devr["applied"][..., 1])
-    print(f"{what}: largest applied-steer distance {u.max():.1f} ulp ({int((u > 0).sum())} of {u.size} differ)")
-    assert u.max() <= ULP
+    assert_rollouts_agree(host, devr, what, ("tokens", "rtg_bins", "existence", "coll"))
 
 
 def test_engine_run_with_a_log_equals_the_host_driven_stepping_on_64_scenes():
@@ -363,20 +278,6 @@ def test_engine_run_with_a_log_equals_the_host_driven_stepping_on_64_scenes():
     assert devr["applied"].shape == (64, 12, T, 2) and devr["existence"].shape == (64, 12, T + 1)
     assert (host["sampled"][ctrl][:, hs - 1:] >= 0).any() and (host["applied"][~ctrl][..., 1] != 0).any()
     _assert_rollouts_agree(host, devr, ctrl, hs, "64 scenes x 12 vehicles")
-
-
-def _cut_logs(k, v, tr):
-    """Vehicles that leave: in every scene vehicle 1's log ends after row 6 (+ k % 5), vehicle 2's after row 11, vehicle 3 is not there
-    at t = 0 (its later rows are logged: latched out), vehicle 4's flag drops at rows 8-9 and comes back (stays out)."""
-    if v == 1:
-        tr[7 + k % 5:] = 0.0
-    elif v == 2:
-        tr[12:] = 0.0
-    elif v == 3:
-        tr[0, 4] = 0.0
-    elif v == 4:
-        tr[8:10, 4] = 0.0
-    return tr
 
 
 def _small_logged(cfg_kw=None):
@@ -482,9 +383,10 @@ def test_evaluator_device_replay_route():
         if flag:
             inner = ev._roll_batch
 
-            def rolled(items, N, *a, inner=inner, ev=ev, cap=cap, cfg=cfg):
-                inner(items, N, *a)
+            def rolled(items, inner=inner, ev=ev, cap=cap, cfg=cfg):
+                inner(items)
                 rb = ev.device_replay_readback[-1]
+                N = items[0][0].N
                 T1 = cfg.nocturne.steps + 1
                 goals4 = np.array([[[*np.asarray(gd[v]["pos"], np.float64), float(gd[v]["heading"]), float(gd[v]["speed"])]
                                     for v in range(N)] for gd in rb["goal_dicts"]])

@@ -1,4 +1,4 @@
-"""GPU: policy roles per vehicle (RolloutEngine.set_roles) — the _views kernels of csrc/replay.hip against their host form, run() with
+"""GPU: policy roles per vehicle (RolloutEngine.set_roles) — the _views entries of csrc/replay.hip against their host form, run() with
 roles against R ordinary single-policy engines stepped by the host, scheduling invariance, R = 1 against set_log alone, and the
 planner-vs-adversary evaluator's cfg.eval_planner_adversary.device_replay route against its stepwise route and the reference fixture."""
 import copy
@@ -11,25 +11,13 @@ pytestmark = pytest.mark.gpu
 
 from helpers import cfg_of, golden  # noqa: E402
 from gpu_utils import DEV, dev  # noqa: E402
+from replay_utils import ULP, _ulps, _disc6, _cut_logs, host_driven, assert_rollouts_agree  # noqa: E402
 from ctrlsim_amd import _lib, replay, scenarios  # noqa: E402
 from ctrlsim_amd.engine import RolloutEngine  # noqa: E402
 from ctrlsim_amd.models import CtRLSim  # noqa: E402
 from ctrlsim_amd.policies import AutoregressivePolicy  # noqa: E402
 from ctrlsim_amd.evaluators import PlannerAdversaryEvaluator  # noqa: E402
 from ctrlsim_amd.evaluators.planner_adversary_evaluator import PLANNER_KEYS, ADVERSARY_KEYS, pick_ego_adversary  # noqa: E402
-
-ULP = 8          # steer: the device atan against glibc's (tests/test_gpu_replay.py)
-
-
-def _ulps(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    sp = np.spacing(np.maximum(np.abs(a), np.abs(b)))
-    return np.where(a == b, 0.0, np.abs(a - b) / sp)
-
-
-def _disc6(w):
-    import ctypes as C
-    return (C.c_double * 6)(w.min_accel, w.max_accel, w.min_steer, w.max_steer, w.accel_discretization, w.steer_discretization)
 
 
 # ---------------------------------------------------------------------------------------------------------------- (a) kernels
@@ -124,33 +112,14 @@ def _model(cfg):
     return CtRLSim(cfg, seed=0, device=DEV)
 
 
-def _cut_logs(k, v, tr):
-    """tests/test_gpu_replay.py's cuts: vehicle 1's log ends after row 6 (+ k % 5) — at k % 5 == 0 inside the K/V-cached steps
-    (t < 8), else after them —, vehicle 2's after row 11, vehicle 3 is not there at t = 0, vehicle 4's flag drops at rows 8-9."""
-    if v == 1:
-        tr[7 + k % 5:] = 0.0
-    elif v == 2:
-        tr[12:] = 0.0
-    elif v == 3:
-        tr[0, 4] = 0.0
-    elif v == 4:
-        tr[8:10, 4] = 0.0
-    return tr
-
-
 def _scenes(cfg, model, S, N, seed, cut=None):
     """S synthetic scenes with their stand-in logs -> (scenes, log [S,N,T1+1,6])."""
     T = cfg.nocturne.steps
     scns = [scenarios.make_scenario(seed, k, n_agents=N, n_polylines=14, n_points=model.dims.NP, extent=40.0) for k in range(S)]
-    log = np.zeros((S, N, T + 2, 6))
-    for k, scn in enumerate(scns):
-        gtd = scenarios.standin_log(scn, T, cfg.nocturne.dt)
-        for v in range(N):
-            tr = np.asarray(gtd[v]["traj"], np.float64).copy()
-            if cut is not None:
-                tr = cut(k, v, tr)
-            log[k, v, :T + 1] = tr
-    return scns, log
+    gtds = [scenarios.standin_log(scn, T, cfg.nocturne.dt) for scn in scns]
+    if cut is not None:
+        gtds = [{v: {"traj": cut(k, v, np.asarray(gtd[v]["traj"], np.float64).copy())} for v in range(N)} for k, gtd in enumerate(gtds)]
+    return scns, replay.log_array(gtds, N, T + 1)
 
 
 def _role_order(role_row, log_s, r):
@@ -168,11 +137,10 @@ def _new_engine(cfg, model, tilt=(0.0, 0.0, 0.0), **kw):
 
 
 def _oracle(cfg, model, scns, log, role, tilts, hsteps, noise=None):
-    """R ordinary single-policy engines on the same scenes, stepped by the host as tests/test_gpu_replay.py::_host_driven steps one:
-    every step, policy_step on each, the tokens merged by role, the replay actions in NumPy, one sim_step on engine 0, the new state
-    row, existence and token column copied into the others.  No code of the roles feature is used.
+    """R ordinary single-policy engines on the same scenes, stepped by the host (replay_utils.host_driven, as
+    tests/test_gpu_replay.py::_host_driven steps one).  No code of the roles feature is used.
     noise(t) -> (noise_rtg [S*R,N,3,bins], noise_act [S*R,N,V]): explicit sampling noise per view row; engine r takes rows r::R."""
-    w, T, dt = cfg.dataset.waymo, cfg.nocturne.steps, cfg.nocturne.dt
+    T = cfg.nocturne.steps
     S, N = role.shape
     R = len(tilts)
     engs = []
@@ -185,53 +153,22 @@ def _oracle(cfg, model, scns, log, role, tilts, hsteps, noise=None):
         e = _new_engine(cfg, model, tilt=tuple(tilts[r]), lanes=1)
         e.load_scenarios(mine, steps=T)
         engs.append(e)
-    d = engs[0].device
-    exist = np.zeros((S, N, T + 1)); accel = np.zeros((S, N, T)); steer = np.zeros((S, N, T))
-    sampled = np.zeros((S, R, N, T), np.int32)
-    own = np.zeros((S, R, N, T), np.int32)
     mutual = np.zeros(S, bool)
-    ctrl = role >= 0
-    for t in range(T):
-        exist[:, :, t] = replay.latch(log, t, exist[:, :, t - 1] if t else None)
-        col = torch.from_numpy(exist[:, :, t].astype(np.float32)).to(d)
-        toks = np.zeros((S, R, N), np.int32)
-        members = []
-        for r, e in enumerate(engs):
-            e.hist_states[:, :, t, 7] = col
-            if noise is None:
-                e.policy_step(t)
-            else:
-                e.policy_step(t, *(a[r::R].contiguous() for a in noise(t)))
-            toks[:, r] = e.act_now.cpu().numpy()
-            own[:, r, :, t] = e.own_ctx.cpu().numpy()
-            assert e.nonfinite() == 0
-            members.append((e.n_groups.cpu().numpy(), e.grp_focal.cpu().numpy(), e.grp_ids.cpu().numpy().astype(np.uint64)))    # context slots
-        sampled[..., t] = toks
-        if R == 2 and t >= hsteps - 1:                     # ego (role 0) and adversary (role 1) in each other's context
-            for k in range(S):
-                ego, adv = int(np.nonzero(role[k] == 0)[0][0]), int(np.nonzero(role[k] == 1)[0][0])
-                sees = []
-                for (ng, gf, gm), me, other in ((members[0], ego, adv), (members[1], adv, ego)):
-                    g = [i for i in range(ng[k]) if gf[k, i] == me]
-                    sees.append(bool(g) and bool((int(gm[k, g[0]]) >> other) & 1))
-                mutual[k] |= all(sees)
-        row = engs[0].hist_states[:, :, t].cpu().numpy()
-        speed = engs[0].phys[:, :, 16].cpu().numpy()
-        merged = np.where(ctrl, np.take_along_axis(toks, np.clip(role, 0, R - 1)[:, None, :], 1)[:, 0], -1)
-        act, alive, tok = replay.actions(log, ctrl, exist[:, :, t], t, hsteps, row[..., 4], speed, merged, dt, w)
-        accel[:, :, t], steer[:, :, t] = act[..., 0], act[..., 1]
-        tok_d = torch.from_numpy(tok.astype(np.int32)).to(d)
-        for e in engs:
-            e.hist_tok[:, :, t] = tok_d
-        engs[0].exists.copy_(torch.from_numpy(alive.astype(np.uint8)).to(d))
-        engs[0].sim_step(t, torch.from_numpy(act).to(d))
-        for e in engs[1:]:
-            e.hist_states[:, :, t + 1].copy_(engs[0].hist_states[:, :, t + 1])
-    exist[:, :, T] = replay.latch(log, T, exist[:, :, T - 1])
-    engs[0].hist_states[:, :, T, 7] = torch.from_numpy(exist[:, :, T].astype(np.float32)).to(d)
-    return dict(tokens=engs[0].hist_tok.cpu().numpy(), states=engs[0].hist_states.cpu().numpy(), coll=engs[0].coll.cpu().numpy(),
-                existence=exist, applied=np.stack([accel, steer], -1), sampled_roles=sampled, own_ctx=own,
-                rtg_bins_roles=np.stack([e.hist_rtg.cpu().numpy() for e in engs], 1), mutual=mutual)
+
+    def meet(t, engs):                                     # ego (role 0) and adversary (role 1) in each other's context
+        if R != 2 or t < hsteps - 1:
+            return
+        members = [(e.n_groups.cpu().numpy(), e.grp_focal.cpu().numpy(), e.grp_ids.cpu().numpy().astype(np.uint64)) for e in engs]   # context slots
+        for k in range(S):
+            ego, adv = int(np.nonzero(role[k] == 0)[0][0]), int(np.nonzero(role[k] == 1)[0][0])
+            sees = []
+            for (ng, gf, gm), me, other in ((members[0], ego, adv), (members[1], adv, ego)):
+                g = [i for i in range(ng[k]) if gf[k, i] == me]
+                sees.append(bool(g) and bool((int(gm[k, g[0]]) >> other) & 1))
+            mutual[k] |= all(sees)
+    out = host_driven(engs, log, role, hsteps, cfg.nocturne.dt, cfg.dataset.waymo, noise=noise, after_policy_step=meet)
+    out["mutual"] = mutual
+    return out
 
 
 def _first_difference(a, b, name):
@@ -245,17 +182,8 @@ def _first_difference(a, b, name):
 
 def _assert_roles_rollout_agrees(host, devr, what):
     assert np.array_equal(host["sampled_roles"], devr["sampled_roles"]), _first_difference(host["sampled_roles"], devr["sampled_roles"], "sampled tokens")
-    for k in ("tokens", "rtg_bins_roles", "existence", "coll"):
-        assert np.array_equal(host[k], devr[k]), (what, k)
     assert np.array_equal(host["own_ctx"] >= 0, devr["own_ctx"] >= 0)
-    assert np.array_equal(host["states"][..., 7], devr["states"][..., 7])
-    identical = np.array_equal(host["states"], devr["states"])
-    print(f"{what}: states bit-identical: {identical}; largest difference {np.abs(host['states'] - devr['states']).max():.3g}")
-    np.testing.assert_allclose(devr["states"], host["states"], rtol=0, atol=1e-4)
-    assert np.array_equal(host["applied"][..., 0].view(np.int64), devr["applied"][..., 0].view(np.int64)), f"{what}: applied accel"
-    u = _ulps(host["applied"][..., 1], devr["applied"][..., 1])
-    print(f"{what}: largest applied-steer distance {u.max():.1f} ulp ({int((u > 0).sum())} of {u.size} differ)")
-    assert u.max() <= ULP
+    assert_rollouts_agree(host, devr, what, ("tokens", "rtg_bins_roles", "existence", "coll"))
 
 
 def _roles_cfg():
