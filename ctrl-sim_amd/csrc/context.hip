@@ -203,95 +203,148 @@ __global__ __launch_bounds__(256) void group_size_hist_kernel(int S, int N, cons
 
 // ctx_index with the contexts of scenarios [s0, s1) SORTED by size class (stable in (scenario, group) order inside a class):
 // class k occupies contexts [start_k, start_k + count_k).  ctx_row0[c] = first logits row of context c when every class
-// writes (slots - 1, or A for the last class) rows per context, classes in order.  One block of 256 threads: thread i owns
-// scenarios i, i + 256, ... of the chunk in turn; per round a block-wide exclusive scan of the threads' per-class counts gives
-// every scenario its first context of each class (<= 4095 scenarios per chunk: 16 rounds).
-__global__ __launch_bounds__(256) void ctx_index_classes_kernel(int s0, int s1, int N, int A, const int* __restrict__ n_groups,
-                                                                const unsigned long long* __restrict__ grp_ids,
-                                                                const int* __restrict__ own_g, const int* __restrict__ mem_g,
-                                                                SizeClasses sc, int* __restrict__ ctx_scn,
-                                                                int* __restrict__ ctx_grp, int* __restrict__ ctx_row0,
-                                                                int* __restrict__ ctx_of_group,   // [S, N] scratch
-                                                                int* __restrict__ own_ctx, int* __restrict__ own_slot,
-                                                                int* __restrict__ mem_ctx, int* __restrict__ mem_slot) {
-  __shared__ int scan[MAXC][256];
-  __shared__ int total[MAXC], start[MAXC], row0[MAXC], carry[MAXC];
+// writes (slots - 1, or A for the last class) rows per context, classes in order.  One block of 1024 threads: thread i owns
+// scenarios i, i + 1024, i + 2048, i + 3072 of the chunk (<= 4095 scenarios per chunk) and reads their group masks ONCE: the
+// class of group g stays in nibble g of four 64-bit registers per scenario, the scenario's per-class counts in the bytes of two
+// more (a scenario has <= 64 groups).  The totals, the scan and the fill all run from those registers; per round of 1024
+// scenarios a block-wide exclusive scan of the threads' per-class counts gives every scenario its first context of each class.
+// The per-vehicle entries are a launch of their own over a grid (ctx_vehicle_index_kernel).
+#define IDX_THREADS 1024
+#define IDX_SLOTS 4
+__global__ __launch_bounds__(IDX_THREADS) void ctx_index_classes_kernel(int s0, int s1, int N, int A, const int* __restrict__ n_groups,
+                                                                        const unsigned long long* __restrict__ grp_ids, SizeClasses sc,
+                                                                        int* __restrict__ ctx_scn, int* __restrict__ ctx_grp,
+                                                                        int* __restrict__ ctx_row0,
+                                                                        int* __restrict__ ctx_of_group) {   // [S, N]
+  __shared__ int wtot[MAXC][IDX_THREADS / 64];
+  __shared__ int total[MAXC], start[MAXC], row0[MAXC], rows_of[MAXC], carry[MAXC], btot[MAXC];
   const int ns = s1 - s0, tid = threadIdx.x, nb = sc.nb;
+  const int lane = tid & 63, wv = tid >> 6;
+  // ---- the one pass over the group masks
+  int ng[IDX_SLOTS];
+  unsigned long long cls[IDX_SLOTS][4], cnt8[IDX_SLOTS][2];
+#pragma unroll
+  for (int r = 0; r < IDX_SLOTS; ++r) {
+    const int i = r * IDX_THREADS + tid;
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) cls[r][w] = 0ull;
+    cnt8[r][0] = cnt8[r][1] = 0ull;
+    if (i < ns) {
+      n = n_groups[s0 + i];
+      if (n > 64) n = 64;
+      const unsigned long long* ids = grp_ids + (size_t)(s0 + i) * N;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) {
+        if (w * 8 < n) {
+          unsigned long long m[8];
+#pragma unroll
+          for (int gg = 0; gg < 8; ++gg) m[gg] = ids[min(w * 8 + gg, n - 1)];   // eight independent loads in flight
+          unsigned long long acc = 0ull;
+#pragma unroll
+          for (int gg = 0; gg < 8; ++gg) {
+            if (w * 8 + gg < n) {
+              const int k = size_class(__popcll(m[gg]), sc.sizes, nb);
+              acc |= (unsigned long long)k << (((w & 1) * 8 + gg) * 4);
+              if (k < 8) cnt8[r][0] += 1ull << (k * 8); else cnt8[r][1] += 1ull << ((k - 8) * 8);
+            }
+          }
+          cls[r][w >> 1] |= acc;
+        }
+      }
+    }
+    ng[r] = n;
+  }
   // ---- class totals of the chunk
-  int cnt[MAXC] = {};
-  for (int i = tid; i < ns; i += 256)
-    for (int g = 0; g < n_groups[s0 + i]; ++g) ++cnt[size_class(__popcll(grp_ids[(size_t)(s0 + i) * N + g]), sc.sizes, nb)];
   if (tid < MAXC) total[tid] = 0;
   __syncthreads();
-  for (int k = 0; k < nb; ++k)
-    if (cnt[k]) atomicAdd(&total[k], cnt[k]);
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k) {
+    int c = 0;
+#pragma unroll
+    for (int r = 0; r < IDX_SLOTS; ++r) c += (int)((cnt8[r][k >> 3] >> ((k & 7) * 8)) & 0xFFull);
+    if (c) atomicAdd(&total[k], c);
+  }
   __syncthreads();
   if (tid == 0) {
     int acc = 0, racc = 0;
     for (int k = 0; k < nb; ++k) {
-      start[k] = acc; row0[k] = racc; carry[k] = 0;
+      const int rows = sc.sizes[k] < A ? sc.sizes[k] - 1 : A;
+      start[k] = acc; row0[k] = racc; rows_of[k] = rows; carry[k] = 0;
       acc += total[k];
-      racc += total[k] * (sc.sizes[k] < A ? sc.sizes[k] - 1 : A);
+      racc += total[k] * rows;
     }
   }
   __syncthreads();
-  // ---- rounds of 256 scenarios, in scenario order
-  for (int base = 0; base < ns; base += 256) {
-    const int i = base + tid;
-    int mine[MAXC] = {};
-    if (i < ns)
-      for (int g = 0; g < n_groups[s0 + i]; ++g) ++mine[size_class(__popcll(grp_ids[(size_t)(s0 + i) * N + g]), sc.sizes, nb)];
-    // inclusive scan over the 256 threads per class: inside a wave by lane shuffles (6 steps, no barrier), then the three
-    // preceding waves' totals through LDS — one barrier per round instead of sixteen (the 16-class kernel had grown to 0.2 ms)
-    const int lane = tid & 63, wv = tid >> 6;
+  // ---- rounds of 1024 scenarios, in scenario order
+#pragma unroll
+  for (int r = 0; r < IDX_SLOTS; ++r) {
+    if (r * IDX_THREADS >= ns) break;                       // uniform: every thread leaves at the same round
+    // inclusive scan over the threads per class: inside a wave by lane shuffles (6 steps, no barrier), then the preceding
+    // waves' totals through LDS — one barrier per round
     int incl[MAXC];
 #pragma unroll
     for (int k = 0; k < MAXC; ++k) {
-      int v = k < nb ? mine[k] : 0;
+      int v = (int)((cnt8[r][k >> 3] >> ((k & 7) * 8)) & 0xFFull);
 #pragma unroll
       for (int off = 1; off < 64; off <<= 1) {
         const int u = __shfl_up(v, off, 64);
         if (lane >= off) v += u;
       }
       incl[k] = v;
-      if (lane == 63) scan[k][wv] = v;                  // the wave's total
+      if (lane == 63) wtot[k][wv] = v;                      // the wave's total
     }
     __syncthreads();
+    {
+      int fill[MAXC];                                       // indexed by unrolled constants only (no run-time indexed array); at the 128
+                                                            // registers of a 1024-thread block the compiler still spills 26 of the kernel's
 #pragma unroll
-    for (int k = 0; k < MAXC; ++k) {
-      int before = 0;
-      for (int q = 0; q < wv; ++q) before += scan[k][q];
-      incl[k] += before;
-    }
-    if (tid == 255)
-      for (int k = 0; k < nb; ++k) scan[k][255] = incl[k];  // block total of the round (read below as scan[k][255])
-    if (i < ns) {
-      int fill[MAXC];
+      for (int k = 0; k < MAXC; ++k) {
+        int before = 0;
+        for (int q = 0; q < wv; ++q) before += wtot[k][q];
+        const int all = incl[k] + before;
+        if (tid == IDX_THREADS - 1) btot[k] = all;          // block total of the round
+        fill[k] = k < nb ? carry[k] + all - (int)((cnt8[r][k >> 3] >> ((k & 7) * 8)) & 0xFFull) : 0;
+      }
+      const int i = r * IDX_THREADS + tid, n = ng[r];
 #pragma unroll
-      for (int k = 0; k < MAXC; ++k) fill[k] = k < nb ? carry[k] + incl[k] - mine[k] : 0;
-      for (int g = 0; g < n_groups[s0 + i]; ++g) {
-        const int k = size_class(__popcll(grp_ids[(size_t)(s0 + i) * N + g]), sc.sizes, nb);
-        const int c = start[k] + fill[k];
-        ctx_scn[c] = s0 + i; ctx_grp[c] = g;
-        ctx_row0[c] = row0[k] + fill[k] * (sc.sizes[k] < A ? sc.sizes[k] - 1 : A);
-        ctx_of_group[(size_t)(s0 + i) * N + g] = c;
-        ++fill[k];
+      for (int w = 0; w < 4; ++w) {
+        const unsigned long long word = cls[r][w];
+        for (int g = w * 16; g < n && g < w * 16 + 16; ++g) {
+          const int k = (int)((word >> ((g & 15) * 4)) & 15ull);
+          int f = 0;
+#pragma unroll
+          for (int kk = 0; kk < MAXC; ++kk) { f = k == kk ? fill[kk] : f; fill[kk] += k == kk ? 1 : 0; }
+          const int c = start[k] + f;
+          ctx_scn[c] = s0 + i; ctx_grp[c] = g;
+          ctx_row0[c] = row0[k] + f * rows_of[k];
+          ctx_of_group[(size_t)(s0 + i) * N + g] = c;
+        }
       }
     }
     __syncthreads();
-    if (tid < nb) carry[tid] += scan[tid][255];
+    if (tid < nb) carry[tid] += btot[tid];
     __syncthreads();
   }
-  for (int k = tid; k < ns * N; k += blockDim.x) {
-    const int i = k / N, v = k - i * N;
-    const size_t sv = (size_t)(s0 + i) * N + v;
-    const int og = own_g[sv], mg = mem_g[sv];
-    const unsigned long long below = (v == 0) ? 0ull : (~0ull >> (64 - v));
-    own_ctx[sv] = og < 0 ? -1 : ctx_of_group[(size_t)(s0 + i) * N + og];
-    own_slot[sv] = og < 0 ? -1 : __popcll(grp_ids[(size_t)(s0 + i) * N + og] & below);
-    mem_ctx[sv] = mg < 0 ? -1 : ctx_of_group[(size_t)(s0 + i) * N + mg];
-    mem_slot[sv] = mg < 0 ? -1 : __popcll(grp_ids[(size_t)(s0 + i) * N + mg] & below);
-  }
+}
+
+// Per-vehicle owner / member context ids and slots of scenarios [s0, s0 + ns): one thread per (scenario, vehicle), after
+// ctx_index_classes_kernel on the same stream (reads its ctx_of_group).
+__global__ __launch_bounds__(256) void ctx_vehicle_index_kernel(int s0, int ns, int N, const unsigned long long* __restrict__ grp_ids,
+                                                                const int* __restrict__ own_g, const int* __restrict__ mem_g,
+                                                                const int* __restrict__ ctx_of_group, int* __restrict__ own_ctx,
+                                                                int* __restrict__ own_slot, int* __restrict__ mem_ctx,
+                                                                int* __restrict__ mem_slot) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= ns * N) return;
+  const int i = k / N, v = k - i * N;
+  const size_t sv = (size_t)(s0 + i) * N + v;
+  const int og = own_g[sv], mg = mem_g[sv];
+  const unsigned long long below = (v == 0) ? 0ull : (~0ull >> (64 - v));
+  own_ctx[sv] = og < 0 ? -1 : ctx_of_group[(size_t)(s0 + i) * N + og];
+  own_slot[sv] = og < 0 ? -1 : __popcll(grp_ids[(size_t)(s0 + i) * N + og] & below);
+  mem_ctx[sv] = mg < 0 ? -1 : ctx_of_group[(size_t)(s0 + i) * N + mg];
+  mem_slot[sv] = mg < 0 ? -1 : __popcll(grp_ids[(size_t)(s0 + i) * N + mg] & below);
 }
 
 // ------------------------------------------------------------------------------------------------ context tensors
@@ -300,10 +353,25 @@ __global__ __launch_bounds__(256) void ctx_index_classes_kernel(int s0, int s1, 
 // 50-150 contexts = workgroups, and a workgroup's float64 chain takes ~150 us whatever the grid.
 struct CtxBatch { int n; int c0[MAXC + 1]; int A[MAXC]; CtxOut o[MAXC]; };
 
-// One block per context.  Agent part: threads over (tt, slot).  Road part: two sweeps over P_all x NP points.
+// One block of CTX_THREADS threads per context.  Agent part: threads over (tt, slot).  Road part, when P_all > P:
+//   keys    CTX_LPP neighbouring lanes take consecutive points of one polyline (a wave reads 64 / CTX_LPP runs of contiguous bytes) and
+//           reduce their maxima by lane shuffles: key[p] = max over the NP points of the point's distance * exist (finite, >= 0: the
+//           maximum does not depend on the order it is taken in);
+//   rank    rank[p] = #{q : key[q] < key[p] or (key[q] == key[p] and q < p)} (ascending key, ties to the lower index), the P_all x P_all
+//           compares cut into H ranges of q so that every thread has some, the partial counts added in LDS (integers: any order);
+//   gather  a wave per output row, lanes over the row's NP x 3 consecutive floats.
 // Window rows [tt_first, Tq) are emitted (Tn = Tq - tt_first rows per context): the cached incremental forward only needs
 // the last one or two timesteps; tt_first = 0 gives the whole window.
-__global__ __launch_bounds__(256) void build_context_kernel(
+#ifndef CTX_THREADS
+#define CTX_THREADS 512
+#endif
+#define CTX_LPP 16      // lanes per polyline in the key sweep
+#ifndef CTX_UNR
+#define CTX_UNR 8       // points (floats in the gather) per lane requested ahead of their use
+#endif
+static_assert(CTX_THREADS % 64 == 0 && CTX_THREADS <= 1024 && 64 % CTX_LPP == 0 && CTX_UNR >= 1,
+              "whole waves (a wave per gathered row), whole shuffle groups of CTX_LPP lanes inside a wave");
+__global__ __launch_bounds__(CTX_THREADS) void build_context_kernel(
     int N, int T, int t, int Tq, int tt_first, int Tmax1, int Tmax, int P_all, int P, int NP,
     const int* __restrict__ ctx_scn, const int* __restrict__ ctx_grp, const int* __restrict__ grp_focal,
     const unsigned long long* __restrict__ grp_ids, const float* __restrict__ hist_states,
@@ -311,9 +379,10 @@ __global__ __launch_bounds__(256) void build_context_kernel(
     const float* __restrict__ types,                                                                     // [S,N,5]
     const float* __restrict__ roads, const float* __restrict__ rtypes,                                    // [S,P_all,NP,3], [S,P_all,8]
     int zero_tok, int zr0, int zr1, int zr2, CtxBatch cb) {
-  extern __shared__ double far_[];                 // [P_all] distance key, then int rank/sel arrays behind it
+  extern __shared__ double far_[];                 // [P_all] distance key, then int rank[P_all] and sel[P] behind it
   __shared__ int slot_of[64];
   __shared__ int gid_of[64];
+  __shared__ double frame[5];
   const int tid = threadIdx.x;
   int k_ = 0;
   while (k_ + 1 < cb.n && (int)blockIdx.x >= cb.c0[k_ + 1]) ++k_;      // wave-uniform: the class of this context
@@ -327,19 +396,19 @@ __global__ __launch_bounds__(256) void build_context_kernel(
   if (tid < 64) {
     const unsigned long long below = (tid == 0) ? 0ull : (~0ull >> (64 - tid));
     slot_of[tid] = ((ids >> tid) & 1ull) ? __popcll(ids & below) : -1;
+    // frame of the focal agent at window index 0 (dataset.py:392-396): evaluated once, by the first wave, for the whole block
+    const float* f0 = hist_states + (((size_t)s * N + focal) * Tmax1 + w0) * 8;
+    const double yaw0 = (double)f0[4];
+    const double sgn = (-yaw0 > 0.0) ? 1.0 : ((-yaw0 < 0.0) ? -1.0 : 0.0);
+    const double rot_ = (PI_D / 2) + sgn * fabs(yaw0);
+    const double cr_ = cos(rot_), sr_ = sin(rot_);
+    if (tid == 0) { frame[0] = rot_; frame[1] = cr_; frame[2] = sr_; frame[3] = (double)f0[0]; frame[4] = (double)f0[1]; }
   }
   __syncthreads();
   if (tid < 64 && tid < N && slot_of[tid] >= 0) gid_of[slot_of[tid]] = tid;
+  const double rot = frame[0], cr = frame[1], sr = frame[2], tx = frame[3], ty = frame[4];
   __syncthreads();
   if (tid < A) o.slot_gid[(size_t)b * A + tid] = tid < n_ids ? gid_of[tid] : -1;
-
-  // frame of the focal agent at window index 0 (dataset.py:392-396)
-  const float* f0 = hist_states + (((size_t)s * N + focal) * Tmax1 + w0) * 8;
-  const double yaw0 = (double)f0[4];
-  const double sgn = (-yaw0 > 0.0) ? 1.0 : ((-yaw0 < 0.0) ? -1.0 : 0.0);
-  const double rot = (PI_D / 2) + sgn * fabs(yaw0);
-  const double cr = cos(rot), sr = sin(rot);
-  const double tx = (double)f0[0], ty = (double)f0[1];
 
   // ---- agents
   const int Tn = Tq - tt_first;
@@ -403,46 +472,96 @@ __global__ __launch_bounds__(256) void build_context_kernel(
   }
 
   // ---- roads
-  const float* rsrc = roads + (size_t)s * P_all * NP * 3;
-  int* sel = reinterpret_cast<int*>(far_ + P_all);     // sel[r] = source polyline of output row r
+  const int rowf = NP * 3;                             // floats of one polyline
+  const float* rsrc = roads + (size_t)s * P_all * rowf;
+  int* rank = reinterpret_cast<int*>(far_ + P_all);
+  int* sel = rank + P_all;                             // sel[r] = source polyline of output row r
   if (P_all > P) {
-    for (int p = tid; p < P_all; p += blockDim.x) {
+    // keys: the trip count is the same for every thread, so that all lanes of a wave meet at the shuffles
+    const int sub = tid & (CTX_LPP - 1), grp = tid / CTX_LPP;
+    for (int p0 = 0; p0 < P_all; p0 += CTX_THREADS / CTX_LPP) {
+      const int p = p0 + grp;
       double mxd = 0.0;
-      bool first = true;
-      for (int q = 0; q < NP; ++q) {
-        const float* pt = rsrc + ((size_t)p * NP + q) * 3;
-        const double px = (double)pt[0] - tx, py = (double)pt[1] - ty;
-        const double x = cr * px + (-sr) * py, y = sr * px + cr * py;
-        const double dd = sqrt(x * x + y * y) * (double)pt[2];
-        if (first || dd > mxd) { mxd = dd; first = false; }
+      if (p < P_all) {
+        const float* pl = rsrc + (size_t)p * rowf;
+        // CTX_UNR points per lane are requested before the first is used (clamped addresses, the surplus is not evaluated): a
+        // polyline of NP <= CTX_LPP * CTX_UNR points costs one memory latency instead of one per point
+        for (int q0 = sub; q0 < NP; q0 += CTX_LPP * CTX_UNR) {
+          float v[CTX_UNR][3];
+#pragma unroll
+          for (int j = 0; j < CTX_UNR; ++j) {
+            const float* pt = pl + min(q0 + j * CTX_LPP, NP - 1) * 3;
+            v[j][0] = pt[0]; v[j][1] = pt[1]; v[j][2] = pt[2];
+          }
+#pragma unroll
+          for (int j = 0; j < CTX_UNR; ++j) {
+            if (q0 + j * CTX_LPP < NP) {
+              const double px = (double)v[j][0] - tx, py = (double)v[j][1] - ty;
+              const double x = cr * px + (-sr) * py, y = sr * px + cr * py;
+              const double dd = sqrt(x * x + y * y) * (double)v[j][2];
+              if (dd > mxd) mxd = dd;
+            }
+          }
+        }
       }
-      far_[p] = mxd;
+#pragma unroll
+      for (int off = CTX_LPP / 2; off > 0; off >>= 1) {
+        const double other = __shfl_xor(mxd, off, 64);
+        if (other > mxd) mxd = other;
+      }
+      if (sub == 0 && p < P_all) { far_[p] = mxd; rank[p] = 0; }
     }
     __syncthreads();
-    for (int p = tid; p < P_all; p += blockDim.x) {
+    // rank: item (h, p) counts the polylines q of range h that come before p
+    const int H = P_all >= CTX_THREADS ? 1 : (CTX_THREADS + P_all - 1) / P_all;
+    const int span = (P_all + H - 1) / H;
+    for (int k = tid; k < P_all * H; k += CTX_THREADS) {
+      const int h = k / P_all, p = k - h * P_all;
+      const int q0 = h * span, q1 = min(P_all, q0 + span);
       const double d = far_[p];
-      int rank = 0;
-      for (int q = 0; q < P_all; ++q) {
+      int before = 0;
+#pragma unroll 8
+      for (int q = q0; q < q1; ++q) {
         const double dq = far_[q];
-        rank += (dq < d || (dq == d && q < p)) ? 1 : 0;
+        before += (dq < d || (dq == d && q < p)) ? 1 : 0;
       }
-      if (rank < P) sel[rank] = p;
+      if (before) atomicAdd(&rank[p], before);
+    }
+    __syncthreads();
+    for (int p = tid; p < P_all; p += CTX_THREADS) {
+      const int r = rank[p];
+      if (r < P) sel[r] = p;
     }
     __syncthreads();
   }
   const int n_live = P_all > P ? P : P_all;
-  for (int k = tid; k < P * NP; k += blockDim.x) {
-    const int r = k / NP, q = k - r * NP;
-    float* po = o.road_pts + (((size_t)b * P + r) * NP + q) * 3;
+  for (int r = tid >> 6; r < P; r += CTX_THREADS / 64) {        // a wave per output row
+    float* po = o.road_pts + ((size_t)b * P + r) * rowf;
     if (r < n_live) {
       const int p = P_all > P ? sel[r] : r;
-      const float* pt = rsrc + ((size_t)p * NP + q) * 3;
-      const double px = (double)pt[0] - tx, py = (double)pt[1] - ty;
-      po[0] = (float)(cr * px + (-sr) * py);
-      po[1] = (float)(sr * px + cr * py);
-      po[2] = pt[2];
+      const float* pl = rsrc + (size_t)p * rowf;
+      for (int f0 = tid & 63; f0 < rowf; f0 += 64 * CTX_UNR) {   // the row's loads first, as in the key sweep
+        float v[CTX_UNR][3];
+#pragma unroll
+        for (int j = 0; j < CTX_UNR; ++j) {
+          const float* pt = pl + (min(f0 + j * 64, rowf - 1) / 3) * 3;
+          v[j][0] = pt[0]; v[j][1] = pt[1]; v[j][2] = pt[2];
+        }
+#pragma unroll
+        for (int j = 0; j < CTX_UNR; ++j) {
+          const int f = f0 + j * 64;
+          if (f < rowf) {
+            const int c = f - (f / 3) * 3;
+            const double px = (double)v[j][0] - tx, py = (double)v[j][1] - ty;
+            // c == 0: cr * px + (-sr) * py, c == 1: sr * px + cr * py — the same products and sum as written out
+            const double ca = c == 0 ? cr : sr, cb_ = c == 0 ? -sr : cr;
+            const float xy = (float)(ca * px + cb_ * py);
+            po[f] = c == 2 ? v[j][2] : xy;
+          }
+        }
+      }
     } else {
-      po[0] = 0.f; po[1] = 0.f; po[2] = 0.f;
+      for (int f = tid & 63; f < rowf; f += 64) po[f] = 0.f;
     }
   }
   for (int k = tid; k < P * 8; k += blockDim.x) {
@@ -498,9 +617,9 @@ int launch_build_context_classes(int n, const int* Bk, const int* Ak, const CtxO
     bytes += (double)Bk[k] * (12.0 * P_all * NP + 12.0 * P * NP + 32.0 * P + (double)(Tq - tt_first) * Ak[k] * (48.0 + 68.0));
   }
   if (cb.n == 0) return CTRLSIM_OK;
-  const size_t shm = (size_t)P_all * sizeof(double) + (size_t)(P > 0 ? P : 1) * sizeof(int);
+  const size_t shm = (size_t)P_all * (sizeof(double) + sizeof(int)) + (size_t)(P > 0 ? P : 1) * sizeof(int);
   prof_before(PROF_CTX, st);
-  hipLaunchKernelGGL(build_context_kernel, dim3(cb.c0[cb.n]), dim3(256), shm, st, N, T, t, Tq, tt_first, Tmax1, Tmax, P_all, P, NP,
+  hipLaunchKernelGGL(build_context_kernel, dim3(cb.c0[cb.n]), dim3(CTX_THREADS), shm, st, N, T, t, Tq, tt_first, Tmax1, Tmax, P_all, P, NP,
                      ctx_scn, ctx_grp, grp_focal, grp_ids, hist_states, hist_tok, hist_rtg, goals, types, roads, rtypes, zero4[0],
                      zero4[1], zero4[2], zero4[3], cb);
   prof_after(PROF_CTX, 0.0, st, bytes);
@@ -540,10 +659,13 @@ int launch_ctx_index_classes(int s0, int s1, int N, int A, const int* n_groups, 
                              hipStream_t st) {
   if (s1 <= s0) return CTRLSIM_OK;
   if (nb < 1 || nb > MAXC || !sizes || sizes[nb - 1] != A) return CTRLSIM_EINVAL;
+  if (s1 - s0 > IDX_THREADS * IDX_SLOTS - 1) return CTRLSIM_EINVAL;     // 4095: what the block's register slots hold
   SizeClasses sc;
   sc.nb = nb;
   for (int k = 0; k < MAXC; ++k) sc.sizes[k] = k < nb ? sizes[k] : 0;
-  hipLaunchKernelGGL(ctx_index_classes_kernel, dim3(1), dim3(256), 0, st, s0, s1, N, A, n_groups, grp_ids, own_g, mem_g, sc,
-                     ctx_scn, ctx_grp, ctx_row0, ctx_of_group, own_ctx, own_slot, mem_ctx, mem_slot);
+  hipLaunchKernelGGL(ctx_index_classes_kernel, dim3(1), dim3(IDX_THREADS), 0, st, s0, s1, N, A, n_groups, grp_ids, sc, ctx_scn, ctx_grp,
+                     ctx_row0, ctx_of_group);
+  hipLaunchKernelGGL(ctx_vehicle_index_kernel, dim3(((s1 - s0) * N + 255) / 256), dim3(256), 0, st, s0, s1 - s0, N, grp_ids, own_g, mem_g,
+                     ctx_of_group, own_ctx, own_slot, mem_ctx, mem_slot);
   return ctrlsim_launch_status();
 }
