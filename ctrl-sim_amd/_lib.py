@@ -30,6 +30,13 @@ class DtRewardCfg(C.Structure):
                [(k, C.c_int) for k in ("remove_shaped_goal", "remove_shaped_veh", "remove_shaped_edge", "pad_")]
 
 
+class DatasetCfg(C.Structure):
+    """ctrlsim_dataset_cfg (include/ctrlsim.h)."""
+    _fields_ = [(k, C.c_double) for k in ("pos_tol", "heading_tol", "speed_tol", "shaped_scaling", "reward_scaling", "goal_mult",
+                                          "shaped_min", "shaped_max", "veh_mult", "max_veh_dist", "edge_mult", "edge_scale")] + \
+               [(k, C.c_int) for k in ("remove_shaped_goal", "remove_shaped_veh", "remove_shaped_edge", "pad_")]
+
+
 class Ctx(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("st12", "exist", "goal5", "act_tok", "rtg_bin", "tstep", "slot_gid",
                                            "road_pts", "road_types")]
@@ -63,6 +70,10 @@ SIGNATURES = {
     "ctrlsim_prof_collect_sub": (I, [P, I, P, P, P, P]),
     "ctrlsim_metrics_size": (I, []),
     "ctrlsim_dt_ledger_step": (I, [I, I, I, I, I, I, P, P, P, P, P, C.POINTER(DtRewardCfg), P, P, P, P]),
+    "ctrlsim_dataset_edge_distance": (I, [I, I, I, I, I, I, P, P, P, P, P, P]),
+    "ctrlsim_dataset_edge_distance_f64": (I, [I, I, I, I, P, P, P, P, P, P]),
+    "ctrlsim_dataset_rewards": (I, [I, I, I, I, P, P, P, P, P, C.POINTER(DatasetCfg), P, P, P, P, P]),
+    "ctrlsim_dataset_rtgs": (I, [I, I, I, P, P, P, P, C.POINTER(DatasetCfg), P, P]),
     "ctrlsim_metrics_pack": (I, [I, I, I, I, I, D, P, P, P, P, P, P, P, P, P, P]),
     "ctrlsim_gemm_nt": (I, [P, I, P, I, P, P, I, P, I, I, I, I, I, P]),
     "ctrlsim_gemm_nt_bf16x6": (I, [P, I, P, I, I, P, P, I, P, I, I, I, I, I, P, P, P]),

@@ -344,6 +344,47 @@ int ctrlsim_dt_ledger_step(int S, int N, int E, int t, int T1, int Tmax, const f
                            const double* goals /*[S,N,5]: x, y first*/, const float* edges, const double* init_rtg,
                            const ctrlsim_dt_reward_cfg* cfg, double* ledger, double* rtg_raw, int* hist_rtg, hipStream_t stream);
 
+/* ---- offline-RL dataset generation (csrc/dataset.hip) ---------------------------------------------------------------
+ * Replaces what stands between a rolled, fully logged batch (data/generate_offline_rl_dataset.py:17-144: ctrlsim_replay_actions with
+ * nothing controlled, ctrlsim_sim_step, ctrlsim_replay_latch) and the `*_physics.pkl` dictionaries of RLWaymoDatasetCtRLSim.get_data
+ * (datasets/rl_waymo/dataset.py:111-275, dataset_ctrl_sim.py:54-97) with their returns-to-go.  The dataset holds T <= T1 steps: rows
+ * 0 .. T-1 of hist_states [S,N,T1,8] / coll [S,N,T1,2]; exist [S,N,T] f64 is the DATASET's existence (the `exists` flag of
+ * ctrlsim_replay_actions per step: logged now and at the next step, latched).  All float64, the NumPy expressions of the host forms
+ * operation by operation; N <= 64.
+ * ctrlsim_dataset_edge_distance — out [S,N,T] = compute_distance_to_road_edge (utils/data.py:152-290): the SIGNED distance of every
+ * point to the first road-edge polyline of minimum |signed distance| (host form: rewards.signed_distance_to_road_edges).  edges
+ * [S,E,4] is the simulator's segment table; poly_off [S,PE+1] i32 cuts a scene's segments into polylines in the order of its road-edge
+ * polylines: polyline p = segments poly_off[s,p] .. poly_off[s,p+1]-1, poly_off[s,0] = 0, unused entries repeat the end (a one-point
+ * polyline has no segment).  exist NULL = column 7 of hist_states.  A point that does not exist is written as 0 without being
+ * evaluated; in a scene without segments an existing point gets +inf (callers refuse such scenes: the reference raises there).
+ * ctrlsim_dataset_edge_distance_f64 — the same kernel on plain float64 tables: P query points per scene xy [S,P,2], edges [S,E,4] f64,
+ * exist [S,P] (NULL = every point exists), out [S,P]: for positions and polylines that float32 does not hold (the reference's own
+ * fixture values among them).
+ * ctrlsim_dataset_rewards — ag_rewards [S,N,T,8] = compute_reward rows (utils/sim.py:83-141; host form metrics.compute_rewards) times
+ * existence, the collision flags being those of the row's own step; veh_veh [S,N,T] = clip(nearest existing vehicle, 0, max) / max,
+ * 0 when absent or alone; veh_edge [S,N,T] = -edge_dist / edge_scale * existence from ctrlsim_dataset_edge_distance's output; rtgs as
+ * ctrlsim_dataset_rtgs.  goals4 [S,N,4] f64 = goal x, y, heading, speed (after initialize_goal_dict).
+ * ctrlsim_dataset_rtgs — rtgs [S,N,T,5] from the dictionary's arrays (host form ingest.load_preprocessed): compute_rewards' five
+ * components (goal position, heading, speed, vehicle, road edge; the remove_shaped_* switches honoured) times existence, summed from
+ * the last step backwards in np.cumsum's order. */
+typedef struct ctrlsim_dataset_cfg {
+  double pos_tol, heading_tol, speed_tol;       // cfg.nocturne.rew_cfg.position / heading / speed_target_tolerance
+  double shaped_scaling, reward_scaling;        // shaped_goal_distance_scaling, reward_scaling
+  double goal_mult, shaped_min, shaped_max;     // pos_target_achieved_rew_multiplier, pos_goal_shaped_min / _max
+  double veh_mult, max_veh_dist;                // veh_veh_collision_rew_multiplier, max_veh_veh_distance
+  double edge_mult, edge_scale;                 // veh_edge_collision_rew_multiplier, dist_to_road_edge_scaling_factor
+  int remove_shaped_goal, remove_shaped_veh, remove_shaped_edge, pad_;
+} ctrlsim_dataset_cfg;
+int ctrlsim_dataset_edge_distance(int S, int N, int T, int T1, int E, int PE, const float* hist_states, const double* exist,
+                                  const float* edges, const int* poly_off, double* out, hipStream_t stream);
+int ctrlsim_dataset_edge_distance_f64(int S, int P, int E, int PE, const double* xy, const double* exist, const double* edges,
+                                      const int* poly_off, double* out, hipStream_t stream);
+int ctrlsim_dataset_rewards(int S, int N, int T, int T1, const float* hist_states, const uint8_t* coll, const double* exist,
+                            const double* goals4, const double* edge_dist, const ctrlsim_dataset_cfg* cfg, double* ag_rewards,
+                            double* veh_veh, double* veh_edge, double* rtgs, hipStream_t stream);
+int ctrlsim_dataset_rtgs(int S, int N, int T, const double* ag_rewards, const double* veh_veh, const double* veh_edge,
+                         const double* exist, const ctrlsim_dataset_cfg* cfg, double* rtgs, hipStream_t stream);
+
 /* ---- metrics ----------------------------------------------------------------------------------------------------
  * Replaces PolicyEvaluator.update_running_statistics (evaluators/policy_evaluator.py:162-248) with compute_reward's goal latch
  * (utils/sim.py:99-104) and compute_nearest_dist_all (evaluators/evaluator.py:87-103) for S finished rollouts: out[0 ..
