@@ -37,6 +37,13 @@ class DatasetCfg(C.Structure):
                [(k, C.c_int) for k in ("remove_shaped_goal", "remove_shaped_veh", "remove_shaped_edge", "pad_")]
 
 
+class WindowCfg(C.Structure):
+    """ctrlsim_window_cfg (include/ctrlsim.h)."""
+    _fields_ = [("agent_dist_threshold", C.c_double), ("moving_threshold", C.c_double), ("rtg_lo", C.c_double * 3), ("rtg_hi", C.c_double * 3)] + \
+               [(k, C.c_double) for k in ("min_accel", "max_accel", "min_steer", "max_steer")] + \
+               [(k, C.c_int) for k in ("rtg_discretization", "accel_discretization", "steer_discretization", "continuous_rtg")]
+
+
 class Ctx(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("st12", "exist", "goal5", "act_tok", "rtg_bin", "tstep", "slot_gid",
                                            "road_pts", "road_types")]
@@ -74,6 +81,7 @@ SIGNATURES = {
     "ctrlsim_dataset_edge_distance_f64": (I, [I, I, I, I, P, P, P, P, P, P]),
     "ctrlsim_dataset_rewards": (I, [I, I, I, I, P, P, P, P, P, C.POINTER(DatasetCfg), P, P, P, P, P]),
     "ctrlsim_dataset_rtgs": (I, [I, I, I, P, P, P, P, C.POINTER(DatasetCfg), P, P]),
+    "ctrlsim_window_build": (I, [I] * 9 + [P] * 11 + [C.POINTER(WindowCfg), C.POINTER(Ctx), P, P, P]),
     "ctrlsim_metrics_pack": (I, [I, I, I, I, I, D, P, P, P, P, P, P, P, P, P, P]),
     "ctrlsim_gemm_nt": (I, [P, I, P, I, P, P, I, P, I, I, I, I, I, P]),
     "ctrlsim_gemm_nt_bf16x6": (I, [P, I, P, I, I, P, P, I, P, I, I, I, I, I, P, P, P]),

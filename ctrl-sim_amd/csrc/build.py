@@ -1,6 +1,6 @@
 """Build libctrlsim_hip.so (gfx950) in-tree with hipcc.  Usage: python build.py [--force]
 
-sim.hip, context.hip, metrics.hip, rewards.hip, replay.hip and dataset.hip are compiled with -ffp-contract=off: their float32/float64 arithmetic must equal the
+sim.hip, context.hip, metrics.hip, rewards.hip, replay.hip, dataset.hip and window.hip are compiled with -ffp-contract=off: their float32/float64 arithmetic must equal the
 reference's plain IEEE evaluation (no FMA contraction); the MFMA/GEMM files use the default contraction.
 """
 import os
@@ -29,7 +29,7 @@ NO_PK = "-Xclang -target-feature -Xclang -packed-fp32-ops"
 COMMON = "-fno-slp-vectorize"
 SRCS = {"gemm": "", "attention": "", "sim": "-ffp-contract=off", "context": "-ffp-contract=off", "embed": NO_PK,
         "map_encoder": "", "sample": "", "metrics": "-ffp-contract=off", "rewards": "-ffp-contract=off", "replay": "-ffp-contract=off",
-        "dataset": "-ffp-contract=off", "forward": "", "dispatch": "", "api": ""}
+        "dataset": "-ffp-contract=off", "window": "-ffp-contract=off", "forward": "", "dispatch": "", "api": ""}
 OUT = os.path.join(HERE, "libctrlsim_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # CTRLSIM_VARIANT=<name> (tools only): a complete second library built with CTRLSIM_EXTRA_DEFS into its own object directory,

@@ -86,6 +86,13 @@ int launch_build_context_classes(int n, const int* Bk, const int* Ak, const CtxO
                                  const unsigned long long* grp_ids, const float* hist_states, const int* hist_tok, const int* hist_rtg,
                                  const double* goals, const float* types, const float* roads, const float* rtypes, const int* zero4, hipStream_t st);
 
+// ---- window.hip: open-loop training windows cut from a device-resident dataset (the ABI entry ctrlsim_window_build lives there too)
+struct ctrlsim_window_cfg;          // include/ctrlsim.h
+int launch_window_build(int B, int S, int N, int Td, int T, int A, int Pmax, int P, int NP, const double* ag_data, const double* actions,
+                        const double* rtgs, const double* goals5, const double* types, const double* road_points,
+                        const double* road_types, const int* n_polys, const int* win_scn, const int* win_t0, const int* win_agent,
+                        const ctrlsim_window_cfg& cfg, CtxOut o, unsigned char* moving, int* status, hipStream_t st);
+
 // ---- gemm.hip, attention.hip: the f32-input MFMA family and the row-wise satellites
 int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, const float* R, int ldr, float* C, int ldc, int M, int N,
                    int K, int relu, hipStream_t st);

@@ -304,6 +304,32 @@ class LogReplayer:
                                                     p(out["ag_rewards"]), p(out["veh_veh"]), p(out["veh_edge"]), p(out["rtgs"]),
                                                     _lib.stream_ptr()), "dataset_rewards")
 
+    def device_dataset(self, out, scenes):
+        """The tensors dataset() left on the device (`out`) as a windows.DeviceDataset: what read_back() would put into the scenes'
+        dictionaries, without the read-back of the large arrays.  The states are the simulator's float32 rows, cast to the dictionary's
+        float64 on the device (the cast _scene_dict does on the host); what travels to the host are the existence flags (one byte per
+        vehicle and step) and the step-0 positions, for the tables of the two random draws.  scenes: the Scenario objects given to
+        load() (their types and polylines; the polylines are uploaded, padded to the largest count)."""
+        from .windows import DeviceDataset
+        S, N, T, dev = self.S, self.N, self.steps, self.device
+        assert len(scenes) == S
+        self.check()
+        ag_data = torch.cat([self.hist_states[:, :, :T, :7].to(torch.float64), out["exist"].unsqueeze(-1)], dim=-1).contiguous()
+        actions = self.applied_steps.permute(1, 2, 0, 3).contiguous()
+        NP = int(self.w.max_num_road_pts_per_polyline)
+        roads = [ingest.roads_to_polylines(road_data_of(s), NP)[:2] for s in scenes]
+        Pmax = max(len(p) for p, _ in roads)
+        road_points, road_types = np.zeros((S, Pmax, NP, 3)), np.zeros((S, Pmax, 8))
+        for k, (p, t) in enumerate(roads):
+            road_points[k, :len(p)] = p
+            road_types[k, :len(p)] = t
+        up = lambda a, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        exist = self.alive_steps.permute(1, 2, 0).contiguous().cpu().numpy()
+        xy0 = self.hist_states[:, :, 0, :2].to(torch.float64).cpu().numpy()
+        return DeviceDataset(self.cfg, ag_data, actions, out["rtgs"], up(_goals5(self.goals4_h)),
+                             up(np.stack([np.asarray(s.types, np.float64) for s in scenes])), up(road_points), up(road_types),
+                             up([len(p) for p, _ in roads], np.int32), exist, xy0)
+
 
 def _goals5(goals4):
     """Policy.update_state's goal row of the dictionary: x, y, speed * cos(heading), speed * sin(heading), heading."""

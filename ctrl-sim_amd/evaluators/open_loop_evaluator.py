@@ -69,3 +69,42 @@ class OpenLoopEvaluator:
         out["windows"] = len(windows)
         out["windows_per_s"] = len(mine) / dt if dt > 0 else float("nan")       # this rank's rate
         return out
+
+    def evaluate_dataset(self, ds, triples, batch_size=None):
+        """evaluate() for windows named by (scene, first step, origin agent) triples of a windows.DeviceDataset: the windows are built
+        on the device (windows.build_windows: ctrlsim_window_build) and scored where they lie, so `windows_per_s` includes the build.
+        Every triple is validated on the host first (ValueError, the messages of ingest.training_window); rank r of a world of W takes
+        triples r, r + W, ...; the ten doubles are all-reduced once and come back in the one copy, together with this rank's count of
+        windows the kernel itself refused (a non-zero count raises)."""
+        import torch.distributed as dist
+        from ..engine import CtxBuffers
+        from ..windows import launch_windows
+        tr = np.asarray(triples, np.int64).reshape(-1, 3)
+        scn, t0, agent = ds.validate(tr[:, 0], tr[:, 1], tr[:, 2])
+        on = dist.is_available() and dist.is_initialized()
+        rank, world = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a[rank::world])).to(self.device)
+        scn_d, t0_d, agent_d = up(scn), up(t0), up(agent)
+        n_mine = int(scn_d.shape[0])
+        B = batch_size or self.batch_size()
+        total = torch.zeros(5, 2, dtype=torch.float64, device=self.device)
+        refused = torch.zeros(1, dtype=torch.float64, device=self.device)
+        cb = CtxBuffers(self.model.dims, max(1, min(B, n_mine)), self.device)
+        t_start = time.perf_counter()
+        for i in range(0, n_mine, B):
+            n = min(B, n_mine - i)
+            _, moving, status = launch_windows(ds, scn_d[i:i + n], t0_d[i:i + n], agent_d[i:i + n], n, out=cb)
+            total += self.model.loss_sums_ctx(cb, moving, n, fused=self.fused)[0]
+            refused += (status != 0).sum()
+        allreduce_loss_sums(total)
+        back = torch.cat([total.reshape(-1), refused]).cpu().numpy()             # the one copy (it waits for the queue)
+        dt = time.perf_counter() - t_start
+        if back[10] != 0:
+            raise RuntimeError(f"{int(back[10])} windows were refused by ctrlsim_window_build after the host tables had accepted them")
+        sums = back[:10].reshape(5, 2)
+        out = dict(self.model.losses_from_sums(sums))
+        out["counts"] = {k: float(sums[self.model.LOSS_KEYS.index(k), 1]) for k in self.model.loss_keys()}
+        out["sums"] = sums
+        out["windows"] = len(tr)
+        out["windows_per_s"] = n_mine / dt if dt > 0 else float("nan")          # this rank's rate, window build included
+        return out

@@ -161,24 +161,38 @@ class CtRLSim:
         lib, st = _lib.lib(), _lib.stream_ptr()
         cb = ctx_from_reference_layout(d, arrs, d.T, dev)
         cb.slot_gid.copy_(torch.arange(d.A, dtype=torch.int32, device=dev).expand(B, d.A))
+        if preds is None:
+            return self.loss_sums_ctx(cb, moving, B, fused=fused, per_ctx=per_ctx, row_nll=row_nll)
         sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
         pc = torch.zeros(B, 5, 2, dtype=torch.float64, device=dev) if per_ctx else None
         rn = torch.zeros(B, d.T, d.A, 4, device=dev) if row_nll else None
         cfg = self.loss_cfg(fused)
-        if preds is None:
-            n = lib.ctrlsim_forward_loss_workspace_bytes(C.byref(self.hip.cdims), B, d.T)
-            if n < 0:
-                raise RuntimeError(f"loss workspace query failed: {n}")
-            ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
-            _lib.check(lib.ctrlsim_forward_loss(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), ws.data_ptr(),
-                                                sums.data_ptr(), _lib.ptr(pc), _lib.ptr(rn), st), "forward_loss")
-        else:
-            rows = lambda k: (preds[k].to(dev).float().permute(0, 2, 1, 3).contiguous() if preds.get(k) is not None else None)
-            act, rtg, fut = rows("action_preds"), rows("rtg_preds"), rows("state_preds")
-            scratch = torch.empty(int(lib.ctrlsim_loss_scratch_bytes(B, d.T, d.A)), dtype=torch.uint8, device=dev)
-            _lib.check(lib.ctrlsim_loss_from_preds(C.byref(self.hip.cdims), B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg),
-                                                   _lib.ptr(act), _lib.ptr(rtg), _lib.ptr(fut), scratch.data_ptr(), sums.data_ptr(),
-                                                   _lib.ptr(pc), _lib.ptr(rn), st), "loss_from_preds")
+        rows = lambda k: (preds[k].to(dev).float().permute(0, 2, 1, 3).contiguous() if preds.get(k) is not None else None)
+        act, rtg, fut = rows("action_preds"), rows("rtg_preds"), rows("state_preds")
+        scratch = torch.empty(int(lib.ctrlsim_loss_scratch_bytes(B, d.T, d.A)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.ctrlsim_loss_from_preds(C.byref(self.hip.cdims), B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg),
+                                               _lib.ptr(act), _lib.ptr(rtg), _lib.ptr(fut), scratch.data_ptr(), sums.data_ptr(),
+                                               _lib.ptr(pc), _lib.ptr(rn), st), "loss_from_preds")
+        return sums, pc, rn                 # enqueued on the current stream; reading the tensors waits for it
+
+    def loss_sums_ctx(self, cb, moving, B, fused=True, per_ctx=False, row_nll=False):
+        """loss_sums below the upload: one teacher-forced forward + loss over the first B contexts of `cb` (engine.CtxBuffers already on
+        the device: ctx_from_reference_layout, or windows.build_windows) with moving [B,A] uint8 or None -> (sums, per_ctx, row_nll)."""
+        import ctypes as C
+        import torch
+        from .. import _lib
+        d, dev = self.dims, self.device
+        lib, st = _lib.lib(), _lib.stream_ptr()
+        sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
+        pc = torch.zeros(B, 5, 2, dtype=torch.float64, device=dev) if per_ctx else None
+        rn = torch.zeros(B, d.T, d.A, 4, device=dev) if row_nll else None
+        cfg = self.loss_cfg(fused)
+        n = lib.ctrlsim_forward_loss_workspace_bytes(C.byref(self.hip.cdims), B, d.T)
+        if n < 0:
+            raise RuntimeError(f"loss workspace query failed: {n}")
+        ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
+        _lib.check(lib.ctrlsim_forward_loss(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), ws.data_ptr(),
+                                            sums.data_ptr(), _lib.ptr(pc), _lib.ptr(rn), st), "forward_loss")
         return sums, pc, rn                 # enqueued on the current stream; reading the tensors waits for it
 
     def compute_loss(self, data, preds=None):

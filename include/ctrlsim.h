@@ -385,6 +385,46 @@ int ctrlsim_dataset_rewards(int S, int N, int T, int T1, const float* hist_state
 int ctrlsim_dataset_rtgs(int S, int N, int T, const double* ag_rewards, const double* veh_veh, const double* veh_edge,
                          const double* exist, const ctrlsim_dataset_cfg* cfg, double* rtgs, hipStream_t stream);
 
+/* ---- open-loop training windows (csrc/window.hip) --------------------------------------------------------------------
+ * Replaces the training-mode half of RLWaymoDatasetCtRLSim.get_data (datasets/rl_waymo/dataset_ctrl_sim.py:99-160 with
+ * select_relevant_agents and normalize_scene, dataset.py:278-319,390-428; host form ingest.training_window) for B windows per launch,
+ * cut from a batch of S scenes of equal vehicle count N <= 64 and equal step count Td >= T that is already on the device, and written
+ * straight into the context tensors ctrlsim_forward_loss reads.  Float inputs are float64 and hold the values of the `*_physics.pkl`
+ * dictionary: ag_data [S,N,Td,8] (x, y, vx, vy, heading, length, width, existence), actions [S,N,Td,2], rtgs [S,N,Td,5] (the five
+ * returns-to-go of ctrlsim_dataset_rtgs; components 0, 3, 4 are used), goals5 [S,N,5], types [S,N,5], road_points [S,Pmax,NP,3],
+ * road_types [S,Pmax,8], n_polys [S] i32 (rows beyond n_polys[s] are never read).  Window b is (win_scn[b], win_t0[b], win_agent[b]):
+ * scene, first step, and the origin agent as an index into the scene's FILTERED agents (those that exist at dataset step 0, ascending).
+ * out: st12 [B,T,A,12], exist [B,T,A], goal5 [B,A,5], act_tok [B,T,A], rtg_bin [B,T,A,3] (bins, or float32 bits of the normalised
+ * returns when cfg.continuous_rtg), tstep [B,T], road_pts [B,P,NP,3], road_types [B,P,8], slot_gid [B,A] = 0 .. A-1 (nullable);
+ * moving [B,A] u8 (moving_agent_mask); status [B] i32.  Agents: the A nearest filtered agents at the window's first step, intersected
+ * with distance < agent_dist_threshold, in ascending agent order; padded slots hold the transform of a zero state, types -1, the token
+ * of the zero action and zero returns.  Roads: n_polys[s] > P keeps the P polylines of smallest max(existing point distance), nearest
+ * first; otherwise all in order, the rest zeros with types -1.  Ties in either ranking go to the lower index.  Geometry is float64 in
+ * the origin agent's frame (x' = c dx - s dy, y' = s dx + c dy, no FMA contraction), rounded once to float32; device sin / cos may
+ * differ from libm by an ulp, integers (tokens, bins, time steps, selections away from ties) are exact.
+ * A triple that cannot be served reads nothing of the dataset, leaves an all-padding window (zero states, types -1, zero-action
+ * tokens, zero returns and time steps, zero polylines with types -1, nothing moving) and a non-zero status; valid windows get 0. */
+enum {
+  CTRLSIM_WINDOW_OK = 0,
+  CTRLSIM_WINDOW_SCENE = 1,     /* win_scn outside [0, S) */
+  CTRLSIM_WINDOW_STEP = 2,      /* win_t0 < 0 or win_t0 + T > Td */
+  CTRLSIM_WINDOW_AGENT = 3,     /* win_agent outside the scene's filtered agents */
+  CTRLSIM_WINDOW_ABSENT = 4,    /* the origin agent does not exist at the window's first step */
+  CTRLSIM_WINDOW_STILL = 5      /* the origin agent is not a moving agent */
+};
+typedef struct ctrlsim_window_cfg {
+  double agent_dist_threshold, moving_threshold;     // cfg.dataset.waymo.agent_dist_threshold, moving_threshold
+  double rtg_lo[3], rtg_hi[3];                       // min / max_rtg_pos, _veh, _road
+  double min_accel, max_accel, min_steer, max_steer; // discretize_actions (ctrlsim_amd/discretize.py)
+  int rtg_discretization, accel_discretization, steer_discretization;
+  int continuous_rtg;                                // Decision Transformer: rtg_bin holds float32 bits
+} ctrlsim_window_cfg;
+int ctrlsim_window_build(int B, int S, int N, int Td, int T, int A, int Pmax, int P, int NP, const double* ag_data,
+                         const double* actions, const double* rtgs, const double* goals5, const double* types,
+                         const double* road_points, const double* road_types, const int* n_polys, const int* win_scn,
+                         const int* win_t0, const int* win_agent, const ctrlsim_window_cfg* cfg, const ctrlsim_ctx* out,
+                         uint8_t* moving, int* status, hipStream_t stream);
+
 /* ---- metrics ----------------------------------------------------------------------------------------------------
  * Replaces PolicyEvaluator.update_running_statistics (evaluators/policy_evaluator.py:162-248) with compute_reward's goal latch
  * (utils/sim.py:99-104) and compute_nearest_dist_all (evaluators/evaluator.py:87-103) for S finished rollouts: out[0 ..
