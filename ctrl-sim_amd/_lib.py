@@ -136,6 +136,10 @@ SIGNATURES = {
     "ctrlsim_forward_all": (I, [P, I, I, C.POINTER(Ctx), P, P, P, P, P]),
     "ctrlsim_forward_loss_workspace_bytes": (L, [C.POINTER(Dims), I, I]),
     "ctrlsim_forward_loss": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), P, P, P, P, P]),
+    "ctrlsim_head_grad_layout": (I, [C.POINTER(Dims), I, I, P, P]),
+    "ctrlsim_head_grads_workspace_bytes": (L, [C.POINTER(Dims), I, I]),
+    "ctrlsim_heads_loss_grad": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P]),
+    "ctrlsim_forward_loss_grad": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P]),
     "ctrlsim_head_ce": (I, [P, I, P, P, P, I, I, I, P, P]),
     "ctrlsim_loss_scratch_bytes": (L, [I, I, I]),
     "ctrlsim_loss_from_preds": (I, [C.POINTER(Dims), I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), P, P, P, P, P, P, P, P]),

@@ -802,12 +802,29 @@ int head_ce(const Mlp& h, const void* ce_blk, const float* ce_bias, const float*
   }
   return 0;
 }
+// The loss heads on the decoder output X (plain layout, rows = B Tq A token triples): (log-sum-exp, target logit) pairs of the action and
+// return heads, the future-state predictions, then the masked sums and counts.  hid: [rows, 256] scratch.
+int heads_loss(const ctrlsim_model* m, const float* X, int rows, float* hid, const LossReq& lq, const ctrlsim_ctx* c, int B, int Tq,
+               hipStream_t st) {
+  const ctrlsim_dims& d = m->d;
+  const int variant = tok_variant(d.variant), k_act = variant == 0 ? 1 : variant == 2 ? 2 : 0;
+  const LossReq* loss = &lq;
+  // Trajeglish (models/ctrl_sim.py:50-67): the logits of step tt against the action of step tt + 1 — the target d.A rows further on
+  CHK(head_ce(m->head_action, m->ce_act, m->ce_act_b, X + k_act * DM, rows, hid, d.V, 1, c->act_tok, variant == 2 ? d.A : 0, *loss, 0, st));
+  if (variant == 0)
+    CHK(head_ce(m->head_rtg, m->ce_rtg, m->ce_rtg_b, X, rows, hid, d.R, d.C, c->rtg_bin, 0, *loss, 1, st));
+  if (m->has_fut) CHK(mlp_tail(m->head_fut, X + 2 * DM, rows, hid, loss->fut, 2 * d.T, st, 3 * DM));
+  return launch_loss_reduce(loss->LT, c->exist, loss->moving, c->st12, m->has_fut ? loss->fut : nullptr, loss->row_nll,
+                            loss->per_ctx ? loss->per_ctx : loss->per_ctx_ws, loss->sums, B, Tq, d.A, d.T, variant == 0,
+                            variant == 2, loss->cfg.supervise_moving, loss->cfg.local_frame_predictions, st);
+}
 // What a full forward computes — exactly one of: logits (the rollout head on the Areg queried rows per context), all (every head on every
 // token), loss (the same heads reduced to sums and counts)
 struct FullReq {
   float* logits = nullptr; const AllOut* all = nullptr; const LossReq* loss = nullptr;
   bool split_tail = false; hipStream_t st_tail = nullptr;   // rollout: the few-row tail on st_tail, event-ordered behind the full-row part
   float* dbg_seg_emb = nullptr;                             // debug output of the scene side: the polylines' compact rows [sum B*P, 256]
+  float** x_seen = nullptr;                                 // receives the address of the decoder output rows in the workspace
 };
 int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, const ctrlsim_ctx* ctx, int Tq, void* workspace, hipStream_t st,
                  const FullReq& rq) {
@@ -822,6 +839,7 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
   FewScope few_scope(false);           // profiling rows: full-row part, then the few-row tail
   bt.contig = bt.n > 1 && ctx_contiguous(d, bt, Tq);
   const Ws w = carve(d, bt, static_cast<char*>(workspace));
+  if (rq.x_seen) *rq.x_seen = w.X;
   const int ti = Tq - 1, rL = (int)bt.rL, rQ = (int)bt.rQ;
   CHK(launch_fill_index(bt, w, d.P, ti, Tq, qoff, false, st));
   // ---- token embeddings (encoder.py:95-153)
@@ -865,17 +883,7 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
     // type is a strided view of X (leading dimension 3*DM).  Action head: the rtg token (CtRL-Sim), the state token (IL, and DT,
     // whose token order is rtg, state, action), the action token (Trajeglish); rtg head: state tokens; future states: action tokens.
     const int rows = rL / 3, k_act = variant == 0 ? 1 : variant == 2 ? 2 : 0;
-    if (loss) {
-      // Trajeglish (models/ctrl_sim.py:50-67): the logits of step tt against the action of step tt + 1 — the target d.A rows further on
-      const ctrlsim_ctx* c = bt.c[0].ctx;
-      CHK(head_ce(m->head_action, m->ce_act, m->ce_act_b, w.X + k_act * DM, rows, w.att, d.V, 1, c->act_tok, variant == 2 ? d.A : 0, *loss, 0, st));
-      if (variant == 0)
-        CHK(head_ce(m->head_rtg, m->ce_rtg, m->ce_rtg_b, w.X, rows, w.att, d.R, d.C, c->rtg_bin, 0, *loss, 1, st));
-      if (m->has_fut) CHK(mlp_tail(m->head_fut, w.X + 2 * DM, rows, w.att, loss->fut, 2 * d.T, st, 3 * DM));
-      return launch_loss_reduce(loss->LT, c->exist, loss->moving, c->st12, m->has_fut ? loss->fut : nullptr, loss->row_nll,
-                                loss->per_ctx ? loss->per_ctx : loss->per_ctx_ws, loss->sums, bt.c[0].B, Tq, d.A, d.T, variant == 0,
-                                variant == 2, loss->cfg.supervise_moving, loss->cfg.local_frame_predictions, st);
-    }
+    if (loss) return heads_loss(m, w.X, rows, w.att, *loss, bt.c[0].ctx, bt.c[0].B, Tq, st);
     CHK(mlp_tail(m->head_action, w.X + k_act * DM, rows, w.att, all->act, d.V, st, 3 * DM));
     if (all->rtg) CHK(mlp_tail(m->head_rtg, w.X, rows, w.att, all->rtg, d.R * d.C, st, 3 * DM));
     if (all->fut) CHK(mlp_tail(m->head_fut, w.X + 2 * DM, rows, w.att, all->fut, 2 * d.T, st, 3 * DM));
@@ -952,6 +960,121 @@ extern "C" int ctrlsim_forward_loss(const ctrlsim_model* m, int B, int Tq, const
   FullReq rq; rq.loss = &lq;
   return forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq);
 }
+// ---- training, first stage: the gradient of final_loss (models/ctrl_sim.py:207-214) through the heads (csrc/head_grad.hip)
+namespace {
+struct GradHeadDesc { const char* name; int n, nsm, k, kind, sm0; };
+// the heads a model of these dims has, in weights.py order, and the float offset of each head's six tensors in `grads`
+int grad_heads(const ctrlsim_dims& d, bool has_fut, GradHeadDesc (&h)[3], long (&off)[4]) {
+  const int variant = tok_variant(d.variant);
+  int n = 0;
+  h[n++] = GradHeadDesc{"decoder.predict_action", d.V, 1, variant == 0 ? 1 : variant == 2 ? 2 : 0, 0, 0};
+  if (variant == 0) h[n++] = GradHeadDesc{"decoder.predict_rtg", d.R, d.C, 0, 1, 1};
+  if (has_fut) h[n++] = GradHeadDesc{"decoder.predict_future_states", 2 * d.T, 1, 2, 2, 4};
+  off[0] = 0;
+  for (int i = 0; i < n; ++i) off[i + 1] = off[i] + (long)DM * DM + 3 * DM + (long)h[i].n * h[i].nsm * DM + (long)h[i].n * h[i].nsm;
+  return n;
+}
+int grad_nmax(const ctrlsim_dims& d) {
+  const int a = d.V > d.R * d.C ? d.V : d.R * d.C;
+  return a > 2 * d.T ? a : 2 * d.T;
+}
+struct GradLayout { size_t base; LossWs l; HeadGradWs g; };
+bool grad_layout(const ctrlsim_dims& d, int B, int Tq, GradLayout& o) {
+  const int64_t base = ctrlsim_forward_workspace_bytes(&d, B, Tq);
+  if (base < 0) return false;
+  o.base = (size_t)base;
+  o.l = loss_carve(d, o.base, B, Tq);
+  o.g = head_grad_carve(o.l.bytes, (long)B * Tq * d.A, grad_nmax(d));
+  return true;
+}
+int head_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving, const ctrlsim_loss_cfg& cfg,
+               float action_coef, const float* X, char* ws, const GradLayout& L, const double* sums, float* grads, float* dX, hipStream_t st) {
+  const ctrlsim_dims& d = m->d;
+  GradHeadDesc hd[3];
+  long off[4];
+  HeadGradArgs a{};
+  a.nheads = grad_heads(d, m->has_fut, hd, off);
+  const Mlp* mlps[3] = {&m->head_action, &m->head_rtg, &m->head_fut};
+  for (int i = 0; i < a.nheads; ++i) {
+    const Mlp& p = *mlps[hd[i].kind];
+    a.h[i] = HeadGradHead{p.l0.w, p.l0.b, p.ln.g, p.ln.b, p.l3.w, p.l3.b, hd[i].n, hd[i].nsm, hd[i].k, hd[i].kind, hd[i].sm0,
+                          hd[i].kind == 0 ? c->act_tok : hd[i].kind == 1 ? c->rtg_bin : nullptr, off[i]};
+  }
+  a.X = X; a.B = B; a.Tq = Tq; a.A = d.A; a.nfut = d.T;
+  a.exist = c->exist; a.st12 = c->st12; a.moving = moving;
+  a.shift = tok_variant(d.variant) == 2 ? d.A : 0;
+  a.supervise_moving = cfg.supervise_moving; a.local_frame = cfg.local_frame_predictions; a.action_coef = action_coef;
+  a.sums = sums; a.grads = grads; a.dX = dX;
+  auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
+  a.Z = f(L.g.Z); a.H = f(L.g.H); a.dH = f(L.g.dH); a.G = f(L.g.G); a.slab = f(L.g.slab); a.part = f(L.g.part);
+  a.chunk_rows = L.g.chunk_rows; a.ldg = L.g.ldg;
+  return launch_head_grads(a, st);
+}
+LossReq grad_loss_req(const unsigned char* moving, const ctrlsim_loss_cfg& cfg, double* sums, double* per_ctx, char* ws, const LossWs& l) {
+  return LossReq{moving, cfg, sums, per_ctx, nullptr, reinterpret_cast<float*>(ws + l.LT), reinterpret_cast<float*>(ws + l.fut),
+                 reinterpret_cast<float*>(ws + l.chunk), reinterpret_cast<double*>(ws + l.per_ctx), l.chunk_rows};
+}
+bool grad_args_ok(const ctrlsim_model* m, int B, int Tq) {
+  return m && B >= 1 && Tq >= 1 && Tq <= m->d.T && !(tok_variant(m->d.variant) == 0 && m->d.C != 3);
+}
+}  // namespace
+
+extern "C" int ctrlsim_head_grad_layout(const ctrlsim_dims* d, int has_future_states, int cap, const char** names, int64_t* offsets) {
+  static const char* const parts[6] = {".mlp.0.weight", ".mlp.0.bias", ".mlp.1.weight", ".mlp.1.bias", ".mlp.3.weight", ".mlp.3.bias"};
+  static std::string store[18];
+  if (!d) return CTRLSIM_EINVAL;
+  GradHeadDesc hd[3];
+  long off[4];
+  const int nh = grad_heads(*d, has_future_states != 0, hd, off);
+  if ((names || offsets) && cap < 6 * nh) return CTRLSIM_EINVAL;
+  for (int i = 0; i < nh; ++i) {
+    const long w = (long)hd[i].n * hd[i].nsm;
+    const long sz[6] = {(long)DM * DM, DM, DM, DM, w * DM, w};
+    long o = off[i];
+    for (int j = 0; j < 6; ++j) {
+      const int slot = 6 * hd[i].kind + j;
+      if (names) { store[slot] = std::string(hd[i].name) + parts[j]; names[6 * i + j] = store[slot].c_str(); }
+      if (offsets) offsets[6 * i + j] = o;
+      o += sz[j];
+    }
+  }
+  if (offsets && cap > 6 * nh) offsets[6 * nh] = off[nh];      // (room for one more: the total)
+  return 6 * nh;
+}
+extern "C" int64_t ctrlsim_head_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq) {
+  GradLayout L;
+  if (!d || B < 1 || Tq < 1 || !grad_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
+  return (int64_t)L.g.bytes;
+}
+extern "C" int ctrlsim_heads_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                       const ctrlsim_loss_cfg* cfg, float loss_action_coef, const float* X, void* workspace, double* sums,
+                                       double* per_ctx, float* grads, float* dX, hipStream_t st) {
+  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !X || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
+  GradLayout L;
+  if (!grad_layout(m->d, B, Tq, L)) return CTRLSIM_EINVAL;
+  char* ws = static_cast<char*>(workspace);
+  const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.l);
+  CHK(heads_loss(m, X, B * Tq * m->d.A, reinterpret_cast<float*>(ws + L.g.H), lq, c, B, Tq, st));
+  return head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L, sums, grads, dX, st);
+}
+extern "C" int ctrlsim_forward_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                         const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
+                                         double* per_ctx, float* grads, float* dX, float* x_out, hipStream_t st) {
+  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
+  GradLayout L;
+  if (!grad_layout(m->d, B, Tq, L)) return CTRLSIM_EINVAL;
+  char* ws = static_cast<char*>(workspace);
+  const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.l);
+  const int A = m->d.A;
+  float* X = nullptr;
+  FullReq rq; rq.loss = &lq; rq.x_seen = &X;
+  CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
+  if (!X) return CTRLSIM_EINVAL;
+  if (x_out && hipMemcpyAsync(x_out, X, (size_t)B * Tq * A * 3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return CTRLSIM_ELAUNCH;
+  return head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L, sums, grads, dX, st);
+}
+
 // The same sums and counts from logits in memory — compute_loss(data, preds) on the tensors of ctrlsim_forward_all (token-row order
 // [B,Tq,A,.]; rtg_preds / state_preds NULL for a model without the head).  scratch: B * Tq * A * 8 floats + B * 10 doubles.
 extern "C" int64_t ctrlsim_loss_scratch_bytes(int B, int Tq, int A) {

@@ -111,6 +111,26 @@ int launch_loss_reduce(const float* LT, const float* exist, const unsigned char*
                        double* per_ctx, double* sums, int B, int Tq, int A, int nfut, int has_rtg, int shift, int supervise_moving, int local_frame,
                        hipStream_t st);
 
+// ---- head_grad.hip: the loss gradient through the MLP heads (f32-input MFMA from the fp32 master weights: independent of the split)
+struct HeadGradHead {
+  const float *w0, *b0, *g, *be, *w3, *b3;   // mlp.0 weight / bias, mlp.1 (LayerNorm) weight / bias, mlp.3 weight / bias
+  int n, nsm;                                // nsm interleaved softmaxes of n classes (future states: n = 2 T outputs, nsm = 1)
+  int k;                                     // token type the head reads: row 3 i + k of X
+  int kind;                                  // 0 action (coef, Trajeglish shift), 1 returns, 2 future states
+  int sm0;                                   // first softmax slot in LT / first term in sums
+  const int* tgt;                            // [rows, nsm] target classes (kinds 0, 1)
+  long goff;                                 // float offset of the head's six tensors in `grads`
+};
+struct HeadGradWs { size_t Z, H, dH, G, slab, part, bytes; int chunk_rows; int ldg; };
+HeadGradWs head_grad_carve(size_t base, long rows, int nmax);
+struct HeadGradArgs {
+  const float* X; int B, Tq, A, nfut, nheads; HeadGradHead h[3];
+  const float *exist, *st12; const unsigned char* moving; long shift; int supervise_moving, local_frame; float action_coef;
+  const double* sums; float *grads, *dX;
+  float *Z, *H, *dH, *G, *slab, *part; int chunk_rows, ldg;
+};
+int launch_head_grads(const HeadGradArgs& a, hipStream_t st);
+
 // ---- sim.hip
 int launch_sim_init(int S, int N, int E, const float* init_pose, const float* size, const float* edges, const unsigned char* exists, float* phys,
                     float* hist_states, unsigned char* coll, int Tmax1, float* contact_state, hipStream_t st);

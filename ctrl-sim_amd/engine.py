@@ -69,6 +69,8 @@ class HipModel:
         _lib.check(self.lib.ctrlsim_model_create(C.byref(self.cdims), self.flat.data_ptr(), len(names), self._names,
                                                  self._offsets, C.byref(h)), "model_create")
         self.handle = h
+        self._offset = {n: int(o) for n, o in zip(names, offsets)}
+        self._heads = {k: np.array(v, np.float32) for k, v in weights.items() if k.startswith(_pack.HEAD_PREFIXES)}   # host masters of update()
         self.split_fallback = False     # an engine of this model met non-finite values under f16x3: later split="auto" engines
                                         # (the policy surface opens one per scenario session) start on bf16x6 right away
 
@@ -77,6 +79,29 @@ class HipModel:
         if n < 0:
             raise RuntimeError(f"workspace query failed: {n}")
         return int(n)
+
+    def update(self, named_tensors):
+        """New fp32 values for tensors of the MLP heads (state-dict names under pack.HEAD_PREFIXES -> torch tensor / ndarray of the
+        tensor's shape): written into the packed buffer at the existing offsets, and every packed image `pack.pack` derives from them
+        (operand planes of both splits, the cross-entropy image and its padded bias) re-derived on the host and copied in place.
+        Offsets never move: the ctrlsim_model handle and everything that points into the buffer stay valid.  A value beyond the fp16
+        range of the two-plane split raises pack's FloatingPointError before anything is written."""
+        new = {}
+        for k, v in named_tensors.items():
+            if k not in self._heads:
+                raise KeyError(f"{k}: update() takes the tensors of the MLP heads this model has ({', '.join(_pack.HEAD_PREFIXES)})")
+            v = np.ascontiguousarray((v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)), dtype=np.float32)
+            if v.shape != self._heads[k].shape:
+                raise ValueError(f"{k}: expected shape {self._heads[k].shape}, got {v.shape}")
+            new[k] = v
+        prefixes = {k.rsplit(".mlp.", 1)[0] for k in new}
+        heads = {k: new.get(k, v) for k, v in self._heads.items() if k.rsplit(".mlp.", 1)[0] in prefixes}
+        images = _pack.head_images(self.dims, heads, self._offset)          # (raises before the first write)
+        for k, v in list(new.items()) + list(images.items()):     # (stream-ordered behind the kernels already enqueued)
+            v = v.reshape(-1)
+            o = self._offset[k]
+            self.flat[o:o + v.size].copy_(torch.from_numpy(v))
+        self._heads.update(new)
 
     def __del__(self):
         try:

@@ -6,7 +6,10 @@ Lightning checkpoint whose `hyper_parameters` carry the cfg (eval_sim.py:52, pol
 Here the object owns the packed device weights (`HipModel`); the HIP forward is driven by the policy/engine through
 the C ABI; `forward` on reference-layout tensors is the reference's return contract ([B,A,T,.] logits of every head,
 teacher-forced), or — with `token_index` — the two-pass logits of one timestep, the slice AutoregressivePolicy reads.
-`compute_loss` / `validation_step` (models/ctrl_sim.py:48-189,217-228) score logged windows: ctrlsim_forward_loss, no logits tensor."""
+`compute_loss` / `validation_step` (models/ctrl_sim.py:48-189,217-228) score logged windows: ctrlsim_forward_loss, no logits tensor.
+`training_step` / `configure_optimizers` / `optimizer_step` (models/ctrl_sim.py:190-214,242-282) train the three MLP heads over a frozen
+trunk: ctrlsim_forward_loss_grad gives the loss and the head gradients (csrc/head_grad.hip), torch's AdamW steps the fp32 masters,
+`HipModel.update` puts them back into the packed buffer.  The trunk's backward pass is not built; `dX` is where it will start."""
 from __future__ import annotations
 
 import numpy as np
@@ -204,3 +207,162 @@ class CtRLSim:
     def validation_step(self, data, batch_idx=0):
         """The values the reference logs per validation batch (models/ctrl_sim.py:217-228), under its names."""
         return {self.VAL_NAMES[k]: v for k, v in self.compute_loss(data).items()}
+
+    # ---- training, first stage: the heads over a frozen trunk (reference: models/ctrl_sim.py:190-214, 242-282)
+    TRAIN_NAMES = {"loss_actions": "loss", "loss_rtg_goal": "loss_rtg_goal", "loss_rtg_veh": "loss_rtg_veh",
+                   "loss_rtg_road": "loss_rtg_road", "loss_state": "loss_state"}
+
+    def head_grad_layout(self):
+        """[(state-dict name, offset in floats, shape)] of the flat gradient buffer, and its length (ctrlsim_head_grad_layout)."""
+        import ctypes as C
+        from .. import _lib
+        from ..engine import _dims_struct
+        lib = _lib.lib()
+        has_fut = int("decoder.predict_future_states.mlp.0.weight" in self.weights)
+        cd = _dims_struct(self.dims)
+        n = lib.ctrlsim_head_grad_layout(C.byref(cd), has_fut, 0, None, None)
+        names, offs = (C.c_char_p * n)(), (C.c_int64 * (n + 1))()
+        if n < 0 or lib.ctrlsim_head_grad_layout(C.byref(cd), has_fut, n + 1, names, offs) != n:
+            raise RuntimeError("head gradient layout query failed")
+        out = [(names[i].decode(), int(offs[i]), tuple(np.asarray(self.weights[names[i].decode()]).shape)) for i in range(n)]
+        return out, int(offs[n])
+
+    def head_parameters(self):
+        """state-dict name -> torch.nn.Parameter over the fp32 master values of the heads this model has (created once; the
+        optimiser's state hangs on these objects)."""
+        import torch
+        if getattr(self, "_head_params", None) is None:
+            self._head_params = {k: torch.nn.Parameter(torch.from_numpy(np.array(self.weights[k], np.float32)).to(self.device))
+                                 for k, _, _ in self.head_grad_layout()[0]}
+        return self._head_params
+
+    def head_grad_workspace_bytes(self, B):
+        import ctypes as C
+        from .. import _lib
+        n = _lib.lib().ctrlsim_head_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T)
+        if n < 0:
+            raise RuntimeError(f"head gradient workspace query failed: {n}")
+        return int(n)
+
+    def loss_and_head_grads_ctx(self, cb, moving, B, fused=True, dX=False, x_out=False, X=None, workspace=None):
+        """One teacher-forced forward + loss + head gradients over the first B contexts of `cb` (engine.CtxBuffers on the device:
+        ctx_from_reference_layout, or windows.build_windows) with moving [B,A] uint8 or None -> (sums [5,2] float64 on the device,
+        {state-dict name: gradient tensor} — views of one flat buffer —, dX [B*T*A*3,256] or None, x_out likewise).  X given (decoder
+        output rows, plain layout): no forward, loss and gradients from those rows (ctrlsim_heads_loss_grad).  workspace: a uint8
+        device tensor of at least head_grad_workspace_bytes(B) to use instead of a fresh one."""
+        import ctypes as C
+        import torch
+        from .. import _lib
+        d, dev = self.dims, self.device
+        lib, st = _lib.lib(), _lib.stream_ptr()
+        layout, total = self.head_grad_layout()
+        sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
+        grads = torch.empty(total, device=dev)
+        rows3 = B * d.T * d.A * 3
+        dx = torch.empty(rows3, d.D, device=dev) if dX else None
+        xo = torch.empty(rows3, d.D, device=dev) if x_out and X is None else None
+        cfg = self.loss_cfg(fused)
+        coef = float(self.cfg.model.get("loss_action_coef", 1.0))
+        n = self.head_grad_workspace_bytes(B)
+        ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= n
+        if X is None:
+            _lib.check(lib.ctrlsim_forward_loss_grad(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
+                                                     ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo), st),
+                       "forward_loss_grad")
+        else:
+            assert X.dtype == torch.float32 and tuple(X.shape) == (rows3, d.D)
+            _lib.check(lib.ctrlsim_heads_loss_grad(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
+                                                   _lib.ptr(X), ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), st),
+                       "heads_loss_grad")
+        named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
+        return sums, named, dx, xo          # enqueued on the current stream; reading the tensors waits for it
+
+    def _ctx_of(self, data):
+        import torch
+        from ..engine import ctx_from_reference_layout
+        d, dev = self.dims, self.device
+        arrs = self._arrays(data)
+        B = arrs["agent_states"].shape[0]
+        ag = data["agent"]
+        mv = ag.get("moving_agent_mask") if isinstance(ag, dict) else getattr(ag, "moving_agent_mask", None)
+        moving = None
+        if mv is not None:
+            mv = np.asarray(mv.cpu() if hasattr(mv, "cpu") else mv)
+            moving = torch.from_numpy(np.ascontiguousarray(mv != 0).astype(np.uint8)).to(dev)
+        cb = ctx_from_reference_layout(d, arrs, d.T, dev)
+        cb.slot_gid.copy_(torch.arange(d.A, dtype=torch.int32, device=dev).expand(B, d.A))
+        return cb, moving, B
+
+    def loss_and_head_grads(self, data, fused=True, dX=False, x_out=False):
+        """loss_and_head_grads_ctx over reference-layout windows `data`."""
+        cb, moving, B = self._ctx_of(data)
+        return self.loss_and_head_grads_ctx(cb, moving, B, fused=fused, dX=dX, x_out=x_out)
+
+    def final_loss(self, losses):
+        """models/ctrl_sim.py:207-214 over the terms this model has (loss_actions already carries loss_action_coef)."""
+        return float(sum(np.float64(losses[k]) for k in self.loss_keys()))
+
+    def _train_backward(self, sums, grads):
+        for k, p in self.head_parameters().items():
+            p.grad = grads[k].clone()
+        losses = self.losses_from_sums(sums.cpu().numpy())
+        self.logged = {self.TRAIN_NAMES[k]: v for k, v in losses.items()}
+        return self.final_loss(losses)
+
+    def training_step(self, data, batch_idx=0):
+        """The reference's training_step for the heads: final_loss of the batch; `.grad` of head_parameters() is filled with its gradient
+        (the trunk is frozen: it has no parameters here), `self.logged` holds what the reference logs per step, under its names."""
+        sums, grads, _, _ = self.loss_and_head_grads(data)
+        return self._train_backward(sums, grads)
+
+    def training_step_ctx(self, cb, moving, B):
+        """training_step on contexts that are already on the device (windows.build_windows)."""
+        sums, grads, _, _ = self.loss_and_head_grads_ctx(cb, moving, B)
+        return self._train_backward(sums, grads)
+
+    @staticmethod
+    def param_groups(names):
+        """The reference's AdamW groups (models/ctrl_sim.py:242-268) restricted to `names`: the weight of a Linear decays; every bias
+        and the LayerNorm weight (mlp.1 of an MLPLayer, utils/layers.py:6-19) do not.  Both lists sorted, as there."""
+        decay = sorted(k for k in names if k.endswith(".weight") and not k.endswith(".mlp.1.weight"))
+        no_decay = sorted(k for k in names if k not in set(decay))
+        return decay, no_decay
+
+    @staticmethod
+    def lr_lambda(train_cfg):
+        """utils/train_utils.py:5-12 (create_lambda_lr): linear warm-up over warmup_steps, then linear decay to 0 at max_steps."""
+        warm, total = train_cfg["warmup_steps"], train_cfg["max_steps"]
+        return lambda step: step / warm if step < warm else max(0.0, (total - step) / (total - warm))
+
+    def configure_optimizers(self):
+        """(optimizer, scheduler): torch.optim.AdamW over head_parameters() in the reference's two groups with cfg.train.lr /
+        weight_decay, LambdaLR with the reference's warm-up / decay, stepped once per optimiser step."""
+        import torch
+        tr = self.cfg.train
+        params = self.head_parameters()
+        decay, no_decay = self.param_groups(list(params))
+        groups = [{"params": [params[k] for k in decay], "weight_decay": tr["weight_decay"]},
+                  {"params": [params[k] for k in no_decay], "weight_decay": 0.0}]
+        opt = torch.optim.AdamW(groups, lr=tr["lr"], weight_decay=tr["weight_decay"])
+        return opt, torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=self.lr_lambda(tr))
+
+    def optimizer_step(self, optimizer, scheduler=None):
+        """Clip the global 2-norm of the head gradients at cfg.train.gradient_clip_val (Lightning clips the norm over the whole model;
+        only the heads have gradients here, so the norm is theirs alone), step, advance the schedule, and write the new values into
+        the packed device weights (HipModel.update).  -> the gradient norm before clipping."""
+        import torch
+        params = self.head_parameters()
+        clip = self.cfg.train.get("gradient_clip_val", None)
+        if clip:
+            norm = torch.nn.utils.clip_grad_norm_(list(params.values()), float(clip))
+        else:
+            norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(p.grad) for p in params.values()]))
+        optimizer.step()
+        if scheduler is not None:
+            scheduler.step()
+        optimizer.zero_grad(set_to_none=True)
+        new = {k: p.detach().cpu().numpy() for k, p in params.items()}
+        self.hip.update(new)
+        self.weights.update({k: v.copy() for k, v in new.items()})
+        return float(norm)

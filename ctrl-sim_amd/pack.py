@@ -215,6 +215,29 @@ def outproj_q_planes(Wo: np.ndarray, Wq: np.ndarray, scheme=1):
     return row_blocks(np.asarray(Wo, np.float32), scheme), row_blocks(np.ascontiguousarray(Wq[:, acc_order_perm(Wq.shape[1])]), scheme)
 
 
+HEAD_PREFIXES = ("decoder.predict_action", "decoder.predict_rtg", "decoder.predict_future_states")
+
+
+def head_images(dims: Dims, w: dict, present) -> dict:
+    """The packed images `pack` derives from the tensors of the MLP heads in `w` (state-dict names under HEAD_PREFIXES), re-derived:
+    {image name: flat float32 array} for every image name in `present` (the names of the model's packed buffer — an image that `pack`
+    left out, because its values were beyond the two-plane range then, has no place to go).  Raises the FloatingPointError of the
+    two-fp16-plane split when a value no longer fits an image that exists."""
+    out = {}
+    for k, v in w.items():
+        v = np.asarray(v, np.float32)
+        if k.startswith(HEAD_PREFIXES) and v.ndim == 2 and v.shape[1] % 16 == 0 and v.shape[1] >= 32 and k.endswith("weight"):
+            for sch, suffix in PLANES_SUFFIX.items():
+                if k + suffix in present:
+                    out[k + suffix] = split3_planes(v, sch).reshape(-1).view(np.float32)
+    for k, nsm in (("decoder.predict_action.mlp.3", 1), ("decoder.predict_rtg.mlp.3", dims.C)):
+        if k + ".weight" in w and k + ".weight#ce" + PLANES_SUFFIX[1] in present:
+            blk, bias = head_ce_image(w[k + ".weight"], w[k + ".bias"], nsm, 1)
+            out[k + ".weight#ce" + PLANES_SUFFIX[1]] = blk.reshape(-1).view(np.float32)
+            out[k + ".bias#ce"] = bias
+    return out
+
+
 def pack(dims: Dims, w: dict):
     """-> (flat float32 ndarray, names list, offsets int64 ndarray in floats)."""
     allw = dict(w)

@@ -101,6 +101,12 @@ EVAL_PLANNER_ADVERSARY = dict(
     adversary=dict(POLICY, goal_tilt=0, veh_veh_tilt=-10, veh_edge_tilt=0),
 )
 
+# cfgs/train/base.yaml (the fields the optimiser, its schedule and the gradient clip read) and what cfgs/train/ctrl_sim_finetuning.yaml
+# changes in it (make_cfg(**{'train__' + k: v for k, v in TRAIN_FINETUNING.items()}) selects that set)
+TRAIN = dict(seed=0, max_steps=200000, warmup_steps=500, lr=5e-4, weight_decay=1e-4, gradient_clip_val=10.0, precision="32-true",
+             finetuning=False)
+TRAIN_FINETUNING = dict(TRAIN, max_steps=1440, warmup_steps=250, lr=5e-4, finetuning=True)
+
 
 def make_cfg(**overrides):
     """Build the attribute-style cfg. `overrides` are dotted keys with '__' separators,
@@ -108,7 +114,7 @@ def make_cfg(**overrides):
     cfg = _wrap(dict(
         dataset=dict(waymo=dict(WAYMO)), model=dict(MODEL), nocturne=copy.deepcopy(NOCTURNE),
         eval=dict(EVAL, policy=dict(POLICY)), eval_planner_adversary=copy.deepcopy(EVAL_PLANNER_ADVERSARY),
-        dataset_root="", nocturne_waymo_val_folder="",
+        train=dict(TRAIN), dataset_root="", nocturne_waymo_val_folder="",
     ))
     for k, v in overrides.items():
         node = cfg

@@ -280,6 +280,31 @@ int64_t ctrlsim_forward_loss_workspace_bytes(const ctrlsim_dims* dims, int B, in
 int ctrlsim_forward_loss(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
                          const ctrlsim_loss_cfg* cfg, void* workspace, double* sums, double* per_ctx, float* row_nll,
                          hipStream_t stream);
+/* ---- training, first stage: head gradients of the open-loop loss (csrc/head_grad.hip) ----------------------------------------
+ * The derivative of the reference's training loss, final_loss = loss_action_coef * loss_actions + loss_rtg_goal + loss_rtg_veh +
+ * loss_rtg_road + loss_state over the terms the model has (models/ctrl_sim.py:48-214), through the three MLP heads predict_action,
+ * predict_rtg, predict_future_states (modules/decoder.py:23-35, utils/layers.py:6-19) down to the decoder's output rows.  X is the
+ * decoder output [B*Tq*A*3, 256] in the plain layout (token type k of (b, tt, a) is row ((b*Tq + tt)*A + a)*3 + k).
+ * grads: ONE flat float32 buffer holding, per head in the parameter-table order (action, returns, future states; only the heads
+ * the model has), mlp.0.weight [256,256], mlp.0.bias, mlp.1.weight, mlp.1.bias (the LayerNorm), mlp.3.weight [n,256], mlp.3.bias.
+ * The layout query fills names[i] (state-dict names, static storage) and offsets[i] (in floats) for cap >= count entries and, if cap > count,
+ * offsets[count] = the total length; it returns the count and needs no device.  dX (nullable) [B*Tq*A*3, 256]: the gradient at the decoder
+ * output, every row written, zeros on rows no head reads.  sums / per_ctx as for ctrlsim_forward_loss; the per-row scales divide by the
+ * counts found in `sums` after this call's own reduction, on the device: hand in zeroed sums for the gradient of this batch's loss.
+ * A term whose count is 0 has a NaN loss and NaN gradients, as autograd gives the reference.  Arithmetic: f32-input MFMA from the
+ * fp32 master weights under either operand split of the forward; sums across workgroups go through partial slabs and a second,
+ * fixed-order stage, no atomics: identical bits from run to run.  Workspace: the head-gradient workspace query (the forward-loss
+ * workspace, then Z, H, dH [B*Tq*A, 256], a logits chunk of <= 8192 rows, and the partial slabs).
+ * The second entry runs the teacher-forced forward first, on its own X (x_out, nullable, receives a copy); its sums are bit-identical
+ * to ctrlsim_forward_loss on the same inputs. */
+int ctrlsim_head_grad_layout(const ctrlsim_dims* dims, int has_future_states, int cap, const char** names, int64_t* offsets);
+int64_t ctrlsim_head_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq);
+int ctrlsim_heads_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                            const ctrlsim_loss_cfg* cfg, float loss_action_coef, const float* X, void* workspace, double* sums,
+                            double* per_ctx, float* grads, float* dX, hipStream_t stream);
+int ctrlsim_forward_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                              const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
+                              float* grads, float* dX, float* x_out, hipStream_t stream);
 /* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
  * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
  * scratch: ctrlsim_loss_scratch_bytes. */

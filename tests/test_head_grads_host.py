@@ -1,0 +1,213 @@
+"""CPU tests of the head-gradient path's host side and of its checker:
+  * tests/head_grad_ref.py (float64 autograd restatement) against the UNMODIFIED reference's own backward pass recorded in
+    tests/golden/head_grads.part*.npz (tools/gen_golden_head_grads.py), every recorded array, on the reference's recorded decoder output;
+  * the same restatement against an analytic NumPy backward written from the formulas of the kernels' specification (full dims);
+  * AdamW parameter groups and the learning-rate schedule against the reference's recorded lists and values;
+  * the flat gradient layout against the parameter table's order.
+
+Bound of the fixture comparison: the recorded gradients are float32 autograd values.  The restatement evaluated in float32 is the same
+arithmetic class; its distance e32 from its own float64 evaluation (relative to max |T|) measures that class on the same data, and the
+recorded values must lie within 8 max(e32, 2^-24) of the float64 values (three bits: other summation orders in three chained products)."""
+import numpy as np
+import pytest
+import torch
+
+from helpers import golden
+from ctrlsim_amd import spec, weights
+from ctrlsim_amd.models import CtRLSim
+import loss_ref
+import head_grad_ref as hgr
+
+TINY_CASES = (0, 1, 2, 4, 5, 6)
+FLOOR = 2.0 ** -24
+
+
+def _case(i):
+    cfg = loss_ref.case_cfg(i)
+    d = spec.Dims(cfg)
+    m = cfg.model
+    kw = dict(variant=d.VARIANT, coef=float(m.get("loss_action_coef", 1.0)), supervise_moving=bool(m.get("supervise_moving", True)),
+              local_frame=bool(m.get("local_frame_predictions", False)))
+    return cfg, d, loss_ref.case_weights(i, d), hgr.ctx_from_inputs(loss_ref.case_inputs(i, d)), kw
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return golden("head_grads")
+
+
+@pytest.mark.parametrize("case", TINY_CASES)
+def test_restatement_matches_reference_backward(case, fixture):
+    g = fixture
+    cfg, d, w, ctx, kw = _case(case)
+    P = f"c{case}_"
+    Xr = g[P + "X"]
+    X = np.zeros((Xr.shape[0], 3, d.D), np.float32)
+    X[:, g[P + "X_types"]] = Xr
+    X = X.reshape(-1, d.D)
+    losses, final, gr, dX = hgr.loss_and_grads(X, w, ctx, **kw)
+    _, _, g32, dX32 = hgr.loss_and_grads(X, w, ctx, dtype=torch.float32, **kw)
+    keys = [str(k) for k in g[P + "keys"]]
+    assert list(losses) == keys
+    np.testing.assert_allclose([losses[k] for k in keys], g[P + "loss"], rtol=2e-6)      # float32 loss values of the reference
+    np.testing.assert_allclose(final, float(g[P + "final"]), rtol=2e-6)
+    worst = 0.0
+
+    def check(tag, got_ref, want64, got32):
+        nonlocal worst
+        scale = np.abs(want64).max()
+        e32 = np.abs(got32 - want64).max() / scale
+        err = np.abs(got_ref - want64).max() / scale
+        worst = max(worst, err / max(e32, FLOOR))
+        assert err <= 8 * max(e32, FLOOR), (tag, err, e32)
+
+    for name in hgr.head_names(w):
+        if gr[name].ndim == 1:
+            check(name, g[P + "g_" + name].astype(np.float64), gr[name], g32[name])
+        else:
+            rows = g[P + "r_" + name]
+            # sampled rows, column sums and norm are judged on the scale of the whole matrix
+            scale = np.abs(gr[name]).max()
+            e32 = max(np.abs(g32[name] - gr[name]).max() / scale, FLOOR)
+            assert np.abs(g[P + "s_" + name] - gr[name][rows]).max() / scale <= 8 * e32, name
+            n_rows = gr[name].shape[0]
+            assert np.abs(g[P + "c_" + name] - gr[name].sum(0)).max() <= 8 * e32 * scale * n_rows, name
+            assert abs(float(g[P + "n_" + name]) - np.linalg.norm(gr[name])) <= 8 * e32 * np.linalg.norm(gr[name]), name
+    rows = g[P + "dx_rows"]
+    scale = np.abs(dX).max()
+    e32 = max(np.abs(dX32 - dX).max() / scale, FLOOR)
+    assert np.abs(g[P + "dx"] - dX[rows]).max() / scale <= 8 * e32
+    assert abs(float(g[P + "dx_norm"]) - np.linalg.norm(dX)) <= 8 * e32 * np.linalg.norm(dX)
+    # rows of token types no head reads carry no gradient
+    read = set(int(k) for k in g[P + "X_types"])
+    for k in range(3):
+        if k not in read:
+            assert not dX.reshape(-1, 3, d.D)[:, k].any()
+    print(f"case {case}: worst recorded / float32-class error ratio {worst:.2f}")
+
+
+def _analytic(X, w, ctx, variant, coef, supervise_moving, local_frame):
+    """The backward pass written out (float64 NumPy): G per head from the softmax / MSE formulas, then dW3 = G^T H, db3 = sum G,
+    dH = G W3, ReLU and LayerNorm backward with mean / rstd recomputed from Z, dW0 = dZ^T X_k, db0 = sum dZ, dX_k = dZ W0."""
+    f8 = lambda a: np.asarray(a, np.float64)
+    X = f8(X)
+    ex, st, mov = f8(ctx["exist"]), f8(ctx["st12"]), f8(ctx["moving"])
+    B, T, A = ex.shape
+    rows = B * T * A
+    mask = ex * (mov[:, None, :] if supervise_moving else 1.0)
+    Xt = X.reshape(rows, 3, -1)
+    grads, dX = {}, np.zeros_like(Xt)
+
+    def head(h, k, make_G):
+        W0, b0, gam, bet = (f8(w[h + p]) for p in hgr.PARTS[:4])
+        W3, b3 = f8(w[h + hgr.PARTS[4]]), f8(w[h + hgr.PARTS[5]])
+        Z = Xt[:, k] @ W0.T + b0
+        mu = Z.mean(1, keepdims=True)
+        rstd = 1.0 / np.sqrt(((Z - mu) ** 2).mean(1, keepdims=True) + 1e-5)
+        xh = (Z - mu) * rstd
+        Y0 = xh * gam + bet
+        H = np.maximum(Y0, 0.0)
+        G = make_G(H @ W3.T + b3)
+        dH = G @ W3
+        dy = dH * (Y0 > 0)
+        dxh = dy * gam
+        dZ = rstd * (dxh - dxh.mean(1, keepdims=True) - xh * (dxh * xh).mean(1, keepdims=True))
+        for p, v in zip(hgr.PARTS, (dZ.T @ Xt[:, k], dZ.sum(0), (dy * xh).sum(0), dy.sum(0), G.T @ H, G.sum(0))):
+            grads[h + p] = v
+        dX[:, k] += dZ @ W0
+
+    def softmax_G(Y, tgt, m, scale):
+        p = np.exp(Y - Y.max(1, keepdims=True))
+        p /= p.sum(1, keepdims=True)
+        oh = np.zeros_like(p)
+        ok = tgt >= 0
+        oh[np.nonzero(ok)[0], tgt[ok]] = 1.0
+        return (p - oh) * (scale * m / m.sum())[:, None]
+
+    tok = np.asarray(ctx["act_tok"]).reshape(-1)
+    if variant == 2:
+        m = np.concatenate([mask[:, 1:], np.zeros((B, 1, A))], 1).reshape(-1)
+        tgt = np.concatenate([np.asarray(ctx["act_tok"])[:, 1:], -np.ones((B, 1, A), np.int64)], 1).reshape(-1)
+    else:
+        m, tgt = mask.reshape(-1), tok
+    head(hgr.HEADS[0], hgr.action_type(variant), lambda Y: softmax_G(Y, tgt, m, coef))
+    if hgr.HEADS[1] + hgr.PARTS[0] in w:
+        bins = np.asarray(ctx["rtg_bin"]).reshape(rows, 3).astype(np.int64)
+
+        def rtg_G(Y):
+            G = np.zeros_like(Y)
+            for c in range(3):
+                G[:, c::3] = softmax_G(Y[:, c::3], bins[:, c], mask.reshape(-1), 1.0)
+            return G
+        head(hgr.HEADS[1], 0, rtg_G)
+    if hgr.HEADS[2] + hgr.PARTS[0] in w:
+        smask = ex if local_frame else mask
+
+        def state_G(Y):
+            Yr = Y.reshape(B, T, A, -1, 2)
+            G = np.zeros_like(Yr)
+            cnt = 0.0
+            for i in range(T):
+                for j in range(min(Yr.shape[3], T - i - 1)):
+                    tg = st[:, i + 1 + j, :, :2]
+                    if local_frame:
+                        dd = tg - st[:, i, :, :2]
+                        yaw = st[:, i, :, 4]
+                        c_, s_ = np.cos(-yaw), np.sin(-yaw)
+                        tg = np.stack([c_ * dd[..., 0] - s_ * dd[..., 1], s_ * dd[..., 0] + c_ * dd[..., 1]], -1)
+                    mk = smask[:, i + 1 + j]
+                    G[:, i, :, j] = 2.0 * (Yr[:, i, :, j] - tg) * mk[..., None]
+                    cnt += mk.sum()
+            return (G / (200.0 * cnt)).reshape(rows, -1)
+        head(hgr.HEADS[2], 2, state_G)
+    return grads, dX.reshape(-1, X.shape[1])
+
+
+@pytest.mark.parametrize("case", [7, 8, 9, 5])
+def test_restatement_matches_analytic_backward(case):
+    """Full dims (cases 7-9: all heads with coef 2, local frame without the moving mask, Trajeglish) and the tiny Trajeglish case, from a
+    seeded random X of trained-like magnitude: autograd and the written-out formulas are two float64 evaluations of one function."""
+    cfg, d, w, ctx, kw = _case(case)
+    rs = np.random.RandomState(50 + case)
+    rows3 = ctx["exist"].size * 3
+    X = (rs.standard_normal((rows3, d.D)) * np.exp(rs.uniform(-1, 1, (rows3, 1)))).astype(np.float32)
+    _, _, gr, dX = hgr.loss_and_grads(X, w, ctx, **kw)
+    ga, dXa = _analytic(X, w, ctx, **kw)
+    assert list(gr) == list(hgr.head_names(w)) and set(ga) == set(gr)
+    for k in gr:
+        assert np.abs(ga[k] - gr[k]).max() <= 1e-11 * np.abs(gr[k]).max(), k
+    assert np.abs(dXa - dX).max() <= 1e-11 * np.abs(dX).max()
+
+
+def test_param_groups_and_schedule_match_reference(fixture):
+    g = fixture
+    cfg = loss_ref.case_cfg(0)
+    d = spec.Dims(cfg)
+    names = hgr.head_names(weights.generate(d, 0))
+    decay, no_decay = CtRLSim.param_groups(names)
+    assert decay == [str(k) for k in g["decay"]]
+    assert no_decay == [str(k) for k in g["no_decay"]]
+    steps = [int(s) for s in g["lr_steps"]]
+    assert steps == [0, 1, 249, 250, 500, 1440, 200000]
+    for tag, tr in (("base", spec.TRAIN), ("finetuning", spec.TRAIN_FINETUNING)):
+        lam = CtRLSim.lr_lambda(tr)
+        assert [lam(s) for s in steps] == list(g["lr_" + tag]), tag
+    assert cfg.train.lr == 5e-4 and cfg.train.weight_decay == 1e-4 and cfg.train.gradient_clip_val == 10.0 and not cfg.train.finetuning
+    assert spec.TRAIN_FINETUNING["max_steps"] == 1440 and spec.TRAIN_FINETUNING["warmup_steps"] == 250 and spec.TRAIN_FINETUNING["finetuning"]
+
+
+@pytest.mark.parametrize("case", [0, 4, 7])
+def test_gradient_layout_follows_parameter_table(case):
+    """ctrlsim_head_grad_layout: the head tensors in weights.param_table order, back to back (needs the library, not a device)."""
+    cfg = loss_ref.case_cfg(case)
+    d = spec.Dims(cfg)
+    w = loss_ref.case_weights(case, d)
+    model = CtRLSim(cfg, w, device="cpu")
+    layout, total = model.head_grad_layout()
+    table = [(n, s) for n, s, _, _ in weights.param_table(d) if n.startswith("decoder.predict_") and n in w]
+    assert [(n, s) for n, _, s in layout] == [(n, tuple(s)) for n, s in table]
+    off = 0
+    for _, o, s in layout:
+        assert o == off
+        off += int(np.prod(s))
+    assert total == off
