@@ -543,8 +543,10 @@ int mlp_tail(const Mlp& m, const float* h_in, int rows, float* hid, float* out, 
 // what follows a decoder layer's self-attention, shared by the full-row and compact-row paths (post-LN): out-projection + residual + norm1
 // and the cross-attention query projection (ONE kernel with option 3 = 3 and the images of pack.py:outproj_q_planes), cross-attention,
 // its out-projection + norm2 + feed-forward block.  att holds the self-attention output on entry.
+// u_store (FullReq::u_store, the training entry's last layer): the out-projection + norm2 and the feed-forward block as two kernels, with
+// the block's input rows copied to u_store between them — the fused kernel keeps that row in registers and overwrites x in place.
 int cross_and_ffn(const ctrlsim_model* m, const Batch& bt, const DecLayer& Ld, int layer, const Ws& w, float* x, float* tmp,
-                  float* att, float* qc, float* ffn, long rows, QKind q, int Rn_mul, hipStream_t st) {
+                  float* att, float* qc, float* ffn, long rows, QKind q, int Rn_mul, hipStream_t st, float* u_store = nullptr) {
   const ctrlsim_dims& d = m->d;
   if (Ld.sq_wop && Ld.sq_wqp && ctrlsim_option(OPT_SPLIT) && ctrlsim_option(OPT_FFN_FUSED) >= 3 && ctrlsim_option(OPT_GEMM_IMPL) == 1) {
     CHK(launch_outproj_ln_q(att, DM, x, DM, Ld.sq_wop, Ld.out.b, Ld.n1.g, Ld.n1.b, Ld.sq_wqp, Ld.cq.b, x, DM, qc, DM, (int)rows, st));
@@ -554,6 +556,11 @@ int cross_and_ffn(const ctrlsim_model* m, const Batch& bt, const DecLayer& Ld, i
   }
   CHK(attention(bt, w, AttnCall{0, q, qc, DM, w.memkv[layer], w.memkv[layer] + DM, 2 * DM, w.img_mem[layer], true, att, 0, 0,
                                    Rn_mul}, st));
+  if (u_store) {
+    CHK(gemm_ln(Ld.cout, Ld.n2, att, DM, x, DM, x, DM, tmp, (int)rows, DM, 0, st));
+    if (hipMemcpyAsync(u_store, x, (size_t)rows * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+    return ffn_block(Ld.lin1, Ld.lin2, Ld.n3, Ld.fp, x, ffn, tmp, (int)rows, d.F, st);
+  }
   return outproj_ln_ffn(Ld.cout, Ld.n2, Ld.lin1, Ld.lin2, Ld.n3, Ld.fp, att, x, ffn, tmp, (int)rows, d.F, st);
 }
 // The engine carves the context tensors of a batch's classes out of shared buffers back to back (CtxBuffers.class_structs);
@@ -825,6 +832,8 @@ struct FullReq {
   bool split_tail = false; hipStream_t st_tail = nullptr;   // rollout: the few-row tail on st_tail, event-ordered behind the full-row part
   float* dbg_seg_emb = nullptr;                             // debug output of the scene side: the polylines' compact rows [sum B*P, 256]
   float** x_seen = nullptr;                                 // receives the address of the decoder output rows in the workspace
+  float* u_store = nullptr;                                 // every-token passes: receives the rows that enter the LAST decoder layer's
+                                                            // feed-forward block (its norm2 output), which then runs as a kernel of its own
 };
 int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, const ctrlsim_ctx* ctx, int Tq, void* workspace, hipStream_t st,
                  const FullReq& rq) {
@@ -860,7 +869,7 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
     if (!last_few) {
       CHK(attention(bt, w, AttnCall{amode, Q_ALL, w.qkv[i], 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false,
                                        w.att, Tq, Tq, 0, use_tbl}, st));
-      CHK(cross_and_ffn(m, bt, Ld, i, w, w.X, w.tmp, w.att, w.qc, w.ffn, bt.rL, Q_ALL, 0, st));
+      CHK(cross_and_ffn(m, bt, Ld, i, w, w.X, w.tmp, w.att, w.qc, w.ffn, bt.rL, Q_ALL, 0, st, i == d.ND - 1 ? rq.u_store : nullptr));
     } else {
       // last layer: only the queried tokens of the current timestep (state tokens; Trajeglish: action tokens) of the regular slots.
       // From here on every kernel touches Areg rows per context; a caller with a second stream gets this tail there, ordered
@@ -1073,6 +1082,79 @@ extern "C" int ctrlsim_forward_loss_grad(const ctrlsim_model* m, int B, int Tq, 
   if (x_out && hipMemcpyAsync(x_out, X, (size_t)B * Tq * A * 3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     return CTRLSIM_ELAUNCH;
   return head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L, sums, grads, dX, st);
+}
+
+// ---- training, second stage (a): heads + the last decoder layer's feed-forward block (csrc/ffn_grad.hip)
+namespace {
+// behind the head-gradient workspace: U and a dX of its own [B*Tq*A*3, 256], then the block's workspace
+struct TrainLayout { GradLayout g; size_t U, dX; FfnGradWs f; };
+bool train_layout(const ctrlsim_dims& d, int B, int Tq, TrainLayout& o) {
+  if (!grad_layout(d, B, Tq, o.g)) return false;
+  const size_t rows3 = (size_t)B * Tq * d.A * 3, n = (rows3 * DM * sizeof(float) + 255) & ~size_t(255);
+  o.U = (o.g.g.bytes + 255) & ~size_t(255);
+  o.dX = o.U + n;
+  o.f = ffn_grad_carve(o.dX + n, (long)rows3, d.F);
+  return true;
+}
+}  // namespace
+
+extern "C" int ctrlsim_train_grad_layout(const ctrlsim_dims* d, int has_future_states, int scope, int cap, const char** names,
+                                         int64_t* offsets) {
+  static const char* const parts[6] = {".linear1.weight", ".linear1.bias", ".linear2.weight", ".linear2.bias", ".norm3.weight", ".norm3.bias"};
+  static std::string store[6];
+  if (!d || scope < 0 || scope > 1 || (scope == 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
+  if (scope == 0) return ctrlsim_head_grad_layout(d, has_future_states, cap, names, offsets);
+  const int nh = ctrlsim_head_grad_layout(d, has_future_states, 0, nullptr, nullptr);
+  if (nh < 0) return nh;
+  if (!names && !offsets) return nh + 6;
+  if (cap < nh + 6) return CTRLSIM_EINVAL;
+  std::vector<int64_t> ho(nh + 1);
+  if (ctrlsim_head_grad_layout(d, has_future_states, nh + 1, names, ho.data()) != nh) return CTRLSIM_EINVAL;
+  if (offsets) for (int i = 0; i < nh; ++i) offsets[i] = ho[i];
+  int64_t total = ho[nh];
+  const int64_t sz[6] = {(int64_t)d->F * DM, d->F, (int64_t)DM * d->F, DM, DM, DM};
+  const std::string pre = "decoder.transformer_decoder.layers." + std::to_string(d->ND - 1);
+  for (int j = 0; j < 6; ++j) {
+    if (names) { store[j] = pre + parts[j]; names[nh + j] = store[j].c_str(); }
+    if (offsets) offsets[nh + j] = total;
+    total += sz[j];
+  }
+  if (offsets && cap > nh + 6) offsets[nh + 6] = total;      // (room for one more: the total)
+  return nh + 6;
+}
+extern "C" int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq, int scope) {
+  if (!d || B < 1 || Tq < 1 || scope < 0 || scope > 1) return CTRLSIM_EINVAL;
+  if (scope == 0) return ctrlsim_head_grads_workspace_bytes(d, B, Tq);
+  TrainLayout L;
+  if (d->F < 1 || !train_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
+  return (int64_t)L.f.bytes;
+}
+extern "C" int ctrlsim_forward_loss_grad_ffn(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                             const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
+                                             double* per_ctx, float* grads, float* dX, float* x_out, float* dU, float* u_out,
+                                             hipStream_t st) {
+  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads || m->d.ND < 1) return CTRLSIM_EINVAL;
+  TrainLayout L;
+  if (!train_layout(m->d, B, Tq, L)) return CTRLSIM_EINVAL;
+  char* ws = static_cast<char*>(workspace);
+  const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.g.l);
+  const int A = m->d.A;
+  const size_t rows3 = (size_t)B * Tq * A * 3;
+  float* X = nullptr;
+  float* U = reinterpret_cast<float*>(ws + L.U);
+  if (!dX) dX = reinterpret_cast<float*>(ws + L.dX);
+  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U;
+  CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
+  if (!X) return CTRLSIM_EINVAL;
+  if (x_out && hipMemcpyAsync(x_out, X, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+  if (u_out && hipMemcpyAsync(u_out, U, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+  CHK(head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L.g, sums, grads, dX, st));
+  GradHeadDesc hd[3];
+  long off[4];
+  const int nh = grad_heads(m->d, m->has_fut, hd, off);
+  const DecLayer& Ld = m->dec[m->d.ND - 1];
+  return launch_ffn_block_grad(U, DM, dX, DM, Ld.lin1.w, Ld.lin1.b, Ld.lin2.w, Ld.lin2.b, Ld.n3.g, Ld.n3.b, (long)rows3, m->d.F, ws, L.f,
+                               grads + off[nh], dU, DM, st);
 }
 
 // The same sums and counts from logits in memory — compute_loss(data, preds) on the tensors of ctrlsim_forward_all (token-row order

@@ -131,6 +131,13 @@ struct HeadGradArgs {
 };
 int launch_head_grads(const HeadGradArgs& a, hipStream_t st);
 
+// ---- ffn_grad.hip: the backward of a post-LN feed-forward block (f32-input MFMA from the fp32 master weights)
+struct FfnGradWs { size_t H, S, dS, slab, part_ln, part_cs, bytes; int chunk_rows, ldh; long nln, ncs; };
+FfnGradWs ffn_grad_carve(size_t base, long rows, int F);
+int launch_ffn_block_grad(const float* U, int ldu, const float* dY, int lddy, const float* W1, const float* b1, const float* W2,
+                          const float* b2, const float* gamma, const float* beta, long rows, int F, char* ws, const FfnGradWs& w,
+                          float* grads, float* dU, int lddu, hipStream_t st);
+
 // ---- sim.hip
 int launch_sim_init(int S, int N, int E, const float* init_pose, const float* size, const float* edges, const unsigned char* exists, float* phys,
                     float* hist_states, unsigned char* coll, int Tmax1, float* contact_state, hipStream_t st);

@@ -71,6 +71,10 @@ class HipModel:
         self.handle = h
         self._offset = {n: int(o) for n, o in zip(names, offsets)}
         self._heads = {k: np.array(v, np.float32) for k, v in weights.items() if k.startswith(_pack.HEAD_PREFIXES)}   # host masters of update()
+        # ... and of the last decoder layer's feed-forward block; its out-projection weight (never updated) is an input of the .ffn#wop image
+        self._ffn_layer = f"decoder.transformer_decoder.layers.{self.dims.ND - 1}"
+        self._ffn = {self._ffn_layer + s: np.array(weights[self._ffn_layer + s], np.float32) for s in _pack.TRAINABLE_FFN_SUFFIXES}
+        self._ffn_wo = np.array(weights[self._ffn_layer + ".multihead_attn.out_proj.weight"], np.float32)
         self.split_fallback = False     # an engine of this model met non-finite values under f16x3: later split="auto" engines
                                         # (the policy surface opens one per scenario session) start on bf16x6 right away
 
@@ -81,27 +85,35 @@ class HipModel:
         return int(n)
 
     def update(self, named_tensors):
-        """New fp32 values for tensors of the MLP heads (state-dict names under pack.HEAD_PREFIXES -> torch tensor / ndarray of the
-        tensor's shape): written into the packed buffer at the existing offsets, and every packed image `pack.pack` derives from them
-        (operand planes of both splits, the cross-entropy image and its padded bias) re-derived on the host and copied in place.
-        Offsets never move: the ctrlsim_model handle and everything that points into the buffer stay valid.  A value beyond the fp16
-        range of the two-plane split raises pack's FloatingPointError before anything is written."""
+        """New fp32 values for tensors of the MLP heads (state-dict names under pack.HEAD_PREFIXES) and of the last decoder layer's
+        feed-forward block (its linear1, linear2 and norm3: pack.TRAINABLE_FFN_SUFFIXES) -> torch tensor / ndarray of the tensor's
+        shape: written into the packed buffer at the existing offsets, and every packed image `pack.pack` derives from them (operand
+        planes of both splits, the cross-entropy image and its padded bias; the fused feed-forward kernels' images) re-derived on the
+        host and copied in place.  Offsets never move: the ctrlsim_model handle and everything that points into the buffer stay valid.
+        A value beyond the fp16 range of the two-plane split raises pack's FloatingPointError before anything is written."""
         new = {}
         for k, v in named_tensors.items():
-            if k not in self._heads:
-                raise KeyError(f"{k}: update() takes the tensors of the MLP heads this model has ({', '.join(_pack.HEAD_PREFIXES)})")
+            master = self._heads if k in self._heads else self._ffn
+            if k not in master:
+                raise KeyError(f"{k}: update() takes the tensors of the MLP heads this model has ({', '.join(_pack.HEAD_PREFIXES)}) and "
+                               f"of {self._ffn_layer}'s feed-forward block")
             v = np.ascontiguousarray((v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)), dtype=np.float32)
-            if v.shape != self._heads[k].shape:
-                raise ValueError(f"{k}: expected shape {self._heads[k].shape}, got {v.shape}")
+            if v.shape != master[k].shape:
+                raise ValueError(f"{k}: expected shape {master[k].shape}, got {v.shape}")
             new[k] = v
-        prefixes = {k.rsplit(".mlp.", 1)[0] for k in new}
+        prefixes = {k.rsplit(".mlp.", 1)[0] for k in new if k in self._heads}
         heads = {k: new.get(k, v) for k, v in self._heads.items() if k.rsplit(".mlp.", 1)[0] in prefixes}
         images = _pack.head_images(self.dims, heads, self._offset)          # (raises before the first write)
+        if any(k in self._ffn and k.endswith(".weight") and ".linear" in k for k in new):
+            layer = {k: new.get(k, v) for k, v in self._ffn.items() if k.endswith(".weight") and ".linear" in k}
+            layer[self._ffn_layer + ".multihead_attn.out_proj.weight"] = self._ffn_wo
+            images.update(_pack.ffn_images(self.dims, layer, self._offset))
         for k, v in list(new.items()) + list(images.items()):     # (stream-ordered behind the kernels already enqueued)
             v = v.reshape(-1)
             o = self._offset[k]
             self.flat[o:o + v.size].copy_(torch.from_numpy(v))
-        self._heads.update(new)
+        for k, v in new.items():
+            (self._heads if k in self._heads else self._ffn)[k] = v
 
     def __del__(self):
         try:

@@ -9,7 +9,9 @@ teacher-forced), or — with `token_index` — the two-pass logits of one timest
 `compute_loss` / `validation_step` (models/ctrl_sim.py:48-189,217-228) score logged windows: ctrlsim_forward_loss, no logits tensor.
 `training_step` / `configure_optimizers` / `optimizer_step` (models/ctrl_sim.py:190-214,242-282) train the three MLP heads over a frozen
 trunk: ctrlsim_forward_loss_grad gives the loss and the head gradients (csrc/head_grad.hip), torch's AdamW steps the fp32 masters,
-`HipModel.update` puts them back into the packed buffer.  The trunk's backward pass is not built; `dX` is where it will start."""
+`HipModel.update` puts them back into the packed buffer.  `set_trainable("heads+ffn")` adds the last decoder layer's feed-forward block
+(linear1, linear2, norm3): ctrlsim_forward_loss_grad_ffn (csrc/ffn_grad.hip) differentiates it too and returns `dU`, the gradient at
+that block's input, where the cross-attention's backward will start.  The rest of the trunk's backward pass is not built."""
 from __future__ import annotations
 
 import numpy as np
@@ -27,6 +29,7 @@ class CtRLSim:
         self.device = device
         self._hip = None
         self.training = False
+        self._scope = "heads"
 
     @classmethod
     def load_from_checkpoint(cls, path, cfg=None, device="cuda:0"):
@@ -303,8 +306,90 @@ class CtRLSim:
         """models/ctrl_sim.py:207-214 over the terms this model has (loss_actions already carries loss_action_coef)."""
         return float(sum(np.float64(losses[k]) for k in self.loss_keys()))
 
+    # ---- training, second stage (a): the heads and the last decoder layer's feed-forward block
+    SCOPES = ("heads", "heads+ffn")
+
+    def set_trainable(self, scope="heads"):
+        """What training_step / configure_optimizers / optimizer_step train: "heads" (the default: the three MLP heads) or "heads+ffn"
+        (the heads and linear1, linear2, norm3 of the last decoder layer).  Choose before configure_optimizers."""
+        if scope not in self.SCOPES:
+            raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES}")
+        self._scope = scope
+        return self
+
+    def train_grad_layout(self, scope=None):
+        """head_grad_layout for a scope (ctrlsim_train_grad_layout): "heads" gives exactly head_grad_layout's answer, "heads+ffn" appends
+        the six tensors of the last decoder layer's feed-forward block.  Needs no device."""
+        import ctypes as C
+        from .. import _lib
+        from ..engine import _dims_struct
+        lib = _lib.lib()
+        sc = self.SCOPES.index(self._scope if scope is None else scope)
+        has_fut = int("decoder.predict_future_states.mlp.0.weight" in self.weights)
+        cd = _dims_struct(self.dims)
+        n = lib.ctrlsim_train_grad_layout(C.byref(cd), has_fut, sc, 0, None, None)
+        names, offs = (C.c_char_p * max(n, 1))(), (C.c_int64 * (max(n, 0) + 1))()
+        if n < 0 or lib.ctrlsim_train_grad_layout(C.byref(cd), has_fut, sc, n + 1, names, offs) != n:
+            raise RuntimeError("training gradient layout query failed")
+        out = [(names[i].decode(), int(offs[i]), tuple(np.asarray(self.weights[names[i].decode()]).shape)) for i in range(n)]
+        return out, int(offs[n])
+
+    def trainable_parameters(self):
+        """state-dict name -> torch.nn.Parameter of the selected scope, in layout order: head_parameters() (the same objects), then under
+        "heads+ffn" the six tensors of the last decoder layer's feed-forward block (created once)."""
+        import torch
+        params = dict(self.head_parameters())
+        if self._scope == "heads+ffn":
+            if getattr(self, "_ffn_params", None) is None:
+                names = [k for k, _, _ in self.train_grad_layout("heads+ffn")[0] if k not in params]
+                self._ffn_params = {k: torch.nn.Parameter(torch.from_numpy(np.array(self.weights[k], np.float32)).to(self.device))
+                                    for k in names}
+            params.update(self._ffn_params)
+        return params
+
+    def train_grad_workspace_bytes(self, B, scope="heads+ffn"):
+        import ctypes as C
+        from .. import _lib
+        n = _lib.lib().ctrlsim_train_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T, self.SCOPES.index(scope))
+        if n < 0:
+            raise RuntimeError(f"training gradient workspace query failed: {n}")
+        return int(n)
+
+    def loss_and_train_grads_ctx(self, cb, moving, B, dX=False, dU=False, x_out=False, u_out=False, workspace=None):
+        """loss_and_head_grads_ctx for the scope "heads+ffn" (ctrlsim_forward_loss_grad_ffn): one teacher-forced forward + loss + the
+        gradients of the heads and of the last decoder layer's feed-forward block -> (sums, {state-dict name: gradient tensor} in
+        train_grad_layout("heads+ffn") order, dX, dU, x_out, u_out), each of the last four [B*T*A*3, 256] or None: the gradient at the
+        decoder output, the gradient at the block's input U, the decoder output and U itself.  The gradients are those of the function
+        this call evaluated (the block applied to U as stored)."""
+        import ctypes as C
+        import torch
+        from .. import _lib
+        d, dev = self.dims, self.device
+        lib, st = _lib.lib(), _lib.stream_ptr()
+        layout, total = self.train_grad_layout("heads+ffn")
+        sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
+        grads = torch.empty(total, device=dev)
+        rows3 = B * d.T * d.A * 3
+        buf = lambda want: torch.empty(rows3, d.D, device=dev) if want else None
+        dx, du, xo, uo = buf(dX), buf(dU), buf(x_out), buf(u_out)
+        cfg = self.loss_cfg(True)
+        coef = float(self.cfg.model.get("loss_action_coef", 1.0))
+        n = self.train_grad_workspace_bytes(B)
+        ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= n
+        _lib.check(lib.ctrlsim_forward_loss_grad_ffn(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
+                                                     ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo),
+                                                     _lib.ptr(du), _lib.ptr(uo), st), "forward_loss_grad_ffn")
+        named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
+        return sums, named, dx, du, xo, uo   # enqueued on the current stream; reading the tensors waits for it
+
+    def loss_and_train_grads(self, data, dX=False, dU=False, x_out=False, u_out=False):
+        """loss_and_train_grads_ctx over reference-layout windows `data`."""
+        cb, moving, B = self._ctx_of(data)
+        return self.loss_and_train_grads_ctx(cb, moving, B, dX=dX, dU=dU, x_out=x_out, u_out=u_out)
+
     def _train_backward(self, sums, grads):
-        for k, p in self.head_parameters().items():
+        for k, p in self.trainable_parameters().items():
             p.grad = grads[k].clone()
         losses = self.losses_from_sums(sums.cpu().numpy())
         self.logged = {self.TRAIN_NAMES[k]: v for k, v in losses.items()}
@@ -313,19 +398,28 @@ class CtRLSim:
     def training_step(self, data, batch_idx=0):
         """The reference's training_step for the heads: final_loss of the batch; `.grad` of head_parameters() is filled with its gradient
         (the trunk is frozen: it has no parameters here), `self.logged` holds what the reference logs per step, under its names."""
-        sums, grads, _, _ = self.loss_and_head_grads(data)
+        if self._scope == "heads+ffn":
+            sums, grads = self.loss_and_train_grads(data)[:2]
+        else:
+            sums, grads, _, _ = self.loss_and_head_grads(data)
         return self._train_backward(sums, grads)
 
     def training_step_ctx(self, cb, moving, B):
         """training_step on contexts that are already on the device (windows.build_windows)."""
-        sums, grads, _, _ = self.loss_and_head_grads_ctx(cb, moving, B)
+        if self._scope == "heads+ffn":
+            sums, grads = self.loss_and_train_grads_ctx(cb, moving, B)[:2]
+        else:
+            sums, grads, _, _ = self.loss_and_head_grads_ctx(cb, moving, B)
         return self._train_backward(sums, grads)
 
     @staticmethod
     def param_groups(names):
         """The reference's AdamW groups (models/ctrl_sim.py:242-268) restricted to `names`: the weight of a Linear decays; every bias
-        and the LayerNorm weight (mlp.1 of an MLPLayer, utils/layers.py:6-19) do not.  Both lists sorted, as there."""
-        decay = sorted(k for k in names if k.endswith(".weight") and not k.endswith(".mlp.1.weight"))
+        and every LayerNorm weight (mlp.1 of an MLPLayer, utils/layers.py:6-19; norm1 / norm2 / norm3 of a transformer layer: the
+        reference groups by module type) do not.  Both lists sorted, as there."""
+        import re
+        ln = re.compile(r"\.(mlp\.1|norm\d*)\.weight$")
+        decay = sorted(k for k in names if k.endswith(".weight") and not ln.search(k))
         no_decay = sorted(k for k in names if k not in set(decay))
         return decay, no_decay
 
@@ -336,11 +430,11 @@ class CtRLSim:
         return lambda step: step / warm if step < warm else max(0.0, (total - step) / (total - warm))
 
     def configure_optimizers(self):
-        """(optimizer, scheduler): torch.optim.AdamW over head_parameters() in the reference's two groups with cfg.train.lr /
+        """(optimizer, scheduler): torch.optim.AdamW over trainable_parameters() in the reference's two groups with cfg.train.lr /
         weight_decay, LambdaLR with the reference's warm-up / decay, stepped once per optimiser step."""
         import torch
         tr = self.cfg.train
-        params = self.head_parameters()
+        params = self.trainable_parameters()
         decay, no_decay = self.param_groups(list(params))
         groups = [{"params": [params[k] for k in decay], "weight_decay": tr["weight_decay"]},
                   {"params": [params[k] for k in no_decay], "weight_decay": 0.0}]
@@ -348,11 +442,11 @@ class CtRLSim:
         return opt, torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=self.lr_lambda(tr))
 
     def optimizer_step(self, optimizer, scheduler=None):
-        """Clip the global 2-norm of the head gradients at cfg.train.gradient_clip_val (Lightning clips the norm over the whole model;
-        only the heads have gradients here, so the norm is theirs alone), step, advance the schedule, and write the new values into
+        """Clip the global 2-norm of the trainable gradients at cfg.train.gradient_clip_val (Lightning clips the norm over the whole model;
+        only trainable_parameters() have gradients here, so the norm is theirs alone), step, advance the schedule, and write the new values into
         the packed device weights (HipModel.update).  -> the gradient norm before clipping."""
         import torch
-        params = self.head_parameters()
+        params = self.trainable_parameters()
         clip = self.cfg.train.get("gradient_clip_val", None)
         if clip:
             norm = torch.nn.utils.clip_grad_norm_(list(params.values()), float(clip))

@@ -238,6 +238,38 @@ def head_images(dims: Dims, w: dict, present) -> dict:
     return out
 
 
+TRAINABLE_FFN_SUFFIXES = (".linear1.weight", ".linear1.bias", ".linear2.weight", ".linear2.bias", ".norm3.weight", ".norm3.bias")
+
+
+def ffn_images(dims: Dims, w: dict, present) -> dict:
+    """The packed images `pack` derives from a transformer layer's linear1 / linear2 weights, re-derived: `w` holds, under their state-dict
+    names, <layer>.linear1.weight and <layer>.linear2.weight and — for the images with the attention out-projection in front of the
+    block — the layer's (unchanged) multihead_attn.out_proj.weight (decoder) or self_attn.out_proj.weight (encoder).  -> {image name:
+    flat float32 array} for every image name in `present`: the operand planes of both splits, .ffn#w1p / .ffn#w2p of both splits,
+    .ffn#w1q and .ffn#wop.  Raises the FloatingPointError of the two-fp16-plane split when a value no longer fits an image that exists."""
+    out = {}
+    f4 = lambda k: np.asarray(w[k], np.float32)
+    for k in w:
+        if not k.endswith(".linear1.weight"):
+            continue
+        pre = k[:-len(".linear1.weight")]
+        W1, W2 = f4(k), f4(pre + ".linear2.weight")
+        for sch, suffix in PLANES_SUFFIX.items():
+            for name, v in ((k, W1), (pre + ".linear2.weight", W2)):
+                if name + suffix in present:
+                    out[name + suffix] = split3_planes(v, sch).reshape(-1).view(np.float32)
+            if pre + ".ffn#w1p" + suffix in present:
+                w1p, w2p = ffn_planes(W1, W2, sch)
+                out[pre + ".ffn#w1p" + suffix] = w1p.reshape(-1).view(np.float32)
+                out[pre + ".ffn#w2p" + suffix] = w2p.reshape(-1).view(np.float32)
+        if pre + ".ffn#w1q" + PLANES_SUFFIX[1] in present:
+            ok = pre + (".multihead_attn.out_proj.weight" if (pre + ".multihead_attn.out_proj.weight") in w else ".self_attn.out_proj.weight")
+            wop, w1q, _ = ffn_planes_pre(f4(ok), W1, W2, 1)
+            out[pre + ".ffn#wop" + PLANES_SUFFIX[1]] = wop.reshape(-1).view(np.float32)
+            out[pre + ".ffn#w1q" + PLANES_SUFFIX[1]] = w1q.reshape(-1).view(np.float32)
+    return out
+
+
 def pack(dims: Dims, w: dict):
     """-> (flat float32 ndarray, names list, offsets int64 ndarray in floats)."""
     allw = dict(w)

@@ -305,6 +305,39 @@ int ctrlsim_heads_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim
 int ctrlsim_forward_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
                               float* grads, float* dX, float* x_out, hipStream_t stream);
+/* ---- training, second stage (a): the feed-forward block's backward (csrc/ffn_grad.hip) -------------------------------------------
+ * The op.  Forward being differentiated, per row (width 256, hidden width F, LayerNorm eps 1e-5, relu'(0) = 0):
+ *   Hp = U W1^T + b1,  H = relu(Hp),  S = U + H W2^T + b2,  Y = LayerNorm(S; gamma, beta)
+ * — the post-LN block every encoder / decoder layer ends in (linear1, linear2, the layer's last norm).  U [rows, 256] and dY [rows, 256]
+ * with leading dimensions >= 256 (floats); W1 [F,256], b1 [F], W2 [256,F], b2, gamma, beta [256]: the fp32 master tensors.
+ * grads: ONE flat float32 buffer dW1 [F,256], db1 [F], dW2 [256,F], db2 [256], dgamma [256], dbeta [256] — the state-dict order
+ * linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm.weight, norm.bias.  dU (nullable) [rows, 256], leading dimension
+ * lddu: the gradient at the block's input.  dU MAY be dY itself with lddu == lddy (a row of dY is consumed before that row of dU is
+ * written); any other overlap of dU with an input is undefined.  U and dY are not written.  rows < 1, F < 1 or a null pointer other than dU: CTRLSIM_EINVAL; any
+ * F >= 1 works.  Nothing of the forward is kept: H and S are recomputed a chunk of rows at a time (ctrlsim_ffn_block_grad_chunk_rows:
+ * <= 8192, fewer where F > 1024).  Arithmetic: f32-input MFMA, independent of the forward's operand split; no float atomics, sums in
+ * fixed orders: identical bits from run to run, whatever the workspace held. */
+int64_t ctrlsim_ffn_block_grad_workspace_bytes(int rows, int F);
+int ctrlsim_ffn_block_grad_chunk_rows(int rows, int F);
+int ctrlsim_ffn_block_grad(const float* U, int ldu, const float* dY, int lddy, const float* W1, const float* b1, const float* W2,
+                           const float* b2, const float* gamma, const float* beta, int rows, int F, void* workspace, float* grads,
+                           float* dU, int lddu, hipStream_t stream);
+/* Heads + the LAST decoder layer's feed-forward block.  ctrlsim_forward_loss_grad with two more outputs: grads continues behind the
+ * head tensors with the six tensors decoder.transformer_decoder.layers.{ND-1}.linear1.weight, .linear1.bias, .linear2.weight,
+ * .linear2.bias, .norm3.weight, .norm3.bias (ctrlsim_train_grad_layout with scope 1; scope 0 = exactly ctrlsim_head_grad_layout), and
+ * dU (nullable) [B*Tq*A*3, 256] is the gradient at that block's input — the layer's norm2 output — where a cross-attention backward
+ * will start.  u_out (nullable) receives those input rows U, x_out the decoder output.  The forward of this entry is the forward of
+ * ctrlsim_forward_loss_grad except in the last decoder layer, whose cross-attention out-projection + norm2 and feed-forward block run
+ * as two kernels with U copied to the workspace between them (the fused kernel never writes U).  The gradients are those of the
+ * function THIS call evaluated: the block applied to U as stored, the heads applied to the decoder output as stored.  Rows of dX no
+ * head reads are zero; their dU is what the block's Jacobian makes of a zero row.  A term with count 0 gives NaN gradients.
+ * Accepted for the models ctrlsim_forward_loss_grad accepts.  Workspace: ctrlsim_train_grads_workspace_bytes(dims, B, Tq, 1) (the
+ * head-gradient workspace, then U, a dX, the H / S / dS chunks, the slabs and partials). */
+int ctrlsim_train_grad_layout(const ctrlsim_dims* dims, int has_future_states, int scope, int cap, const char** names, int64_t* offsets);
+int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq, int scope);
+int ctrlsim_forward_loss_grad_ffn(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                                  const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
+                                  float* grads, float* dX, float* x_out, float* dU, float* u_out, hipStream_t stream);
 /* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
  * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
  * scratch: ctrlsim_loss_scratch_bytes. */

@@ -22,7 +22,8 @@ from ctrlsim_amd.engine import CtxBuffers  # noqa: E402
 from ctrlsim_amd.windows import launch_windows  # noqa: E402
 
 
-def main():
+def main(scope="heads"):
+    """scope: what CtRLSim.set_trainable takes (tools/ffn_finetune.py runs this loop with "heads+ffn")."""
     arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default
     steps, B, S, N, T1, polys = arg(1, 20), arg(2, 32), arg(3, 4), arg(4, 16), arg(5, 60), arg(6, 64)
     cfg = spec.make_cfg(nocturne__steps=T1, **{"train__" + k: v for k, v in spec.TRAIN_FINETUNING.items()})
@@ -38,7 +39,7 @@ def main():
     up = lambda x: torch.from_numpy(x).to(dev)
     cb, moving, status = launch_windows(ds, up(scn), up(t), up(a), B, out=CtxBuffers(d, B, dev))
     assert int(status.abs().sum()) == 0
-    model = CtRLSim(cfg, weights.generate_trained_like(d, 0), device=dev)
+    model = CtRLSim(cfg, weights.generate_trained_like(d, 0), device=dev).set_trainable(scope)
     opt, sched = model.configure_optimizers()
     first = last = None
     for step in range(steps):
@@ -48,7 +49,7 @@ def main():
         print(json.dumps({"step": step, "final_loss": loss, "lr": lr, "grad_norm": norm, **model.logged}))
         first = loss if first is None else first
         last = loss
-    print(f"{B} windows of {S} scenes, {steps} steps: final_loss {first:.6f} -> {last:.6f}")
+    print(f"{B} windows of {S} scenes, scope {scope}, {steps} steps: final_loss {first:.6f} -> {last:.6f}")
     assert last < first, "the loss did not fall"
 
 
