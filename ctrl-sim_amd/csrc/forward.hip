@@ -545,8 +545,10 @@ int mlp_tail(const Mlp& m, const float* h_in, int rows, float* hid, float* out, 
 // its out-projection + norm2 + feed-forward block.  att holds the self-attention output on entry.
 // u_store (FullReq::u_store, the training entry's last layer): the out-projection + norm2 and the feed-forward block as two kernels, with
 // the block's input rows copied to u_store between them — the fused kernel keeps that row in registers and overwrites x in place.
+// x1_store (FullReq::x1_store): receives the norm1 output rows, the cross-attention sublayer's input, before norm2 overwrites them.
 int cross_and_ffn(const ctrlsim_model* m, const Batch& bt, const DecLayer& Ld, int layer, const Ws& w, float* x, float* tmp,
-                  float* att, float* qc, float* ffn, long rows, QKind q, int Rn_mul, hipStream_t st, float* u_store = nullptr) {
+                  float* att, float* qc, float* ffn, long rows, QKind q, int Rn_mul, hipStream_t st, float* u_store = nullptr,
+                  float* x1_store = nullptr) {
   const ctrlsim_dims& d = m->d;
   if (Ld.sq_wop && Ld.sq_wqp && ctrlsim_option(OPT_SPLIT) && ctrlsim_option(OPT_FFN_FUSED) >= 3 && ctrlsim_option(OPT_GEMM_IMPL) == 1) {
     CHK(launch_outproj_ln_q(att, DM, x, DM, Ld.sq_wop, Ld.out.b, Ld.n1.g, Ld.n1.b, Ld.sq_wqp, Ld.cq.b, x, DM, qc, DM, (int)rows, st));
@@ -554,6 +556,8 @@ int cross_and_ffn(const ctrlsim_model* m, const Batch& bt, const DecLayer& Ld, i
     CHK(gemm_ln(Ld.out, Ld.n1, att, DM, x, DM, x, DM, tmp, (int)rows, DM, 0, st));
     CHK(gemm(Ld.cq, x, DM, nullptr, 0, qc, DM, (int)rows, DM, DM, 0, st));
   }
+  if (x1_store && hipMemcpyAsync(x1_store, x, (size_t)rows * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return CTRLSIM_ELAUNCH;
   CHK(attention(bt, w, AttnCall{0, q, qc, DM, w.memkv[layer], w.memkv[layer] + DM, 2 * DM, w.img_mem[layer], true, att, 0, 0,
                                    Rn_mul}, st));
   if (u_store) {
@@ -834,6 +838,9 @@ struct FullReq {
   float** x_seen = nullptr;                                 // receives the address of the decoder output rows in the workspace
   float* u_store = nullptr;                                 // every-token passes: receives the rows that enter the LAST decoder layer's
                                                             // feed-forward block (its norm2 output), which then runs as a kernel of its own
+  float* x1_store = nullptr;                                // ... and the rows that enter its cross-attention sublayer (its norm1 output)
+  const float** mem_seen = nullptr;                         // receive the addresses of the scene encoder's output rows and their key-padding
+  const unsigned char** pad_seen = nullptr;                 // bytes in the workspace: written by the scene side, only read from there on
 };
 int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, const ctrlsim_ctx* ctx, int Tq, void* workspace, hipStream_t st,
                  const FullReq& rq) {
@@ -849,6 +856,8 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
   bt.contig = bt.n > 1 && ctx_contiguous(d, bt, Tq);
   const Ws w = carve(d, bt, static_cast<char*>(workspace));
   if (rq.x_seen) *rq.x_seen = w.X;
+  if (rq.mem_seen) *rq.mem_seen = w.src;
+  if (rq.pad_seen) *rq.pad_seen = w.src_pad;
   const int ti = Tq - 1, rL = (int)bt.rL, rQ = (int)bt.rQ;
   CHK(launch_fill_index(bt, w, d.P, ti, Tq, qoff, false, st));
   // ---- token embeddings (encoder.py:95-153)
@@ -869,7 +878,8 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
     if (!last_few) {
       CHK(attention(bt, w, AttnCall{amode, Q_ALL, w.qkv[i], 3 * DM, w.qkv[i] + DM, w.qkv[i] + 2 * DM, 3 * DM, w.img_dec[i], false,
                                        w.att, Tq, Tq, 0, use_tbl}, st));
-      CHK(cross_and_ffn(m, bt, Ld, i, w, w.X, w.tmp, w.att, w.qc, w.ffn, bt.rL, Q_ALL, 0, st, i == d.ND - 1 ? rq.u_store : nullptr));
+      CHK(cross_and_ffn(m, bt, Ld, i, w, w.X, w.tmp, w.att, w.qc, w.ffn, bt.rL, Q_ALL, 0, st, i == d.ND - 1 ? rq.u_store : nullptr,
+                        i == d.ND - 1 ? rq.x1_store : nullptr));
     } else {
       // last layer: only the queried tokens of the current timestep (state tokens; Trajeglish: action tokens) of the regular slots.
       // From here on every kernel touches Areg rows per context; a caller with a second stream gets this tail there, ordered
@@ -1096,35 +1106,55 @@ bool train_layout(const ctrlsim_dims& d, int B, int Tq, TrainLayout& o) {
   o.f = ffn_grad_carve(o.dX + n, (long)rows3, d.F);
   return true;
 }
+// scope 2, behind that: X1 and a dU of its own [B*Tq*A*3, 256], then the attention sublayer's workspace (queries: a context's 3 Tq A token
+// rows; keys: its M scene rows)
+struct CrossLayout { TrainLayout t; size_t X1, dU; AttnGradWs a; int M; };
+bool cross_layout(const ctrlsim_dims& d, int B, int Tq, CrossLayout& o) {
+  if (!train_layout(d, B, Tq, o.t)) return false;
+  const size_t rows3 = (size_t)B * Tq * d.A * 3, n = (rows3 * DM * sizeof(float) + 255) & ~size_t(255);
+  o.M = (d.P + d.A + 3) & ~3;
+  o.X1 = (o.t.f.bytes + 255) & ~size_t(255);
+  o.dU = o.X1 + n;
+  o.a = attn_grad_carve(o.dU + n, B, Tq * d.A * 3, o.M);
+  return true;
+}
 }  // namespace
 
 extern "C" int ctrlsim_train_grad_layout(const ctrlsim_dims* d, int has_future_states, int scope, int cap, const char** names,
                                          int64_t* offsets) {
-  static const char* const parts[6] = {".linear1.weight", ".linear1.bias", ".linear2.weight", ".linear2.bias", ".norm3.weight", ".norm3.bias"};
-  static std::string store[6];
-  if (!d || scope < 0 || scope > 1 || (scope == 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
+  static const char* const parts[12] = {".linear1.weight", ".linear1.bias", ".linear2.weight", ".linear2.bias", ".norm3.weight", ".norm3.bias",
+                                        ".multihead_attn.in_proj_weight", ".multihead_attn.in_proj_bias", ".multihead_attn.out_proj.weight",
+                                        ".multihead_attn.out_proj.bias", ".norm2.weight", ".norm2.bias"};
+  static std::string store[12];
+  if (!d || scope < 0 || scope > 2 || (scope >= 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
+  const int ne = scope == 2 ? 12 : 6;
   if (scope == 0) return ctrlsim_head_grad_layout(d, has_future_states, cap, names, offsets);
   const int nh = ctrlsim_head_grad_layout(d, has_future_states, 0, nullptr, nullptr);
   if (nh < 0) return nh;
-  if (!names && !offsets) return nh + 6;
-  if (cap < nh + 6) return CTRLSIM_EINVAL;
+  if (!names && !offsets) return nh + ne;
+  if (cap < nh + ne) return CTRLSIM_EINVAL;
   std::vector<int64_t> ho(nh + 1);
   if (ctrlsim_head_grad_layout(d, has_future_states, nh + 1, names, ho.data()) != nh) return CTRLSIM_EINVAL;
   if (offsets) for (int i = 0; i < nh; ++i) offsets[i] = ho[i];
   int64_t total = ho[nh];
-  const int64_t sz[6] = {(int64_t)d->F * DM, d->F, (int64_t)DM * d->F, DM, DM, DM};
+  const int64_t sz[12] = {(int64_t)d->F * DM, d->F, (int64_t)DM * d->F, DM, DM, DM, 3LL * DM * DM, 3 * DM, (int64_t)DM * DM, DM, DM, DM};
   const std::string pre = "decoder.transformer_decoder.layers." + std::to_string(d->ND - 1);
-  for (int j = 0; j < 6; ++j) {
+  for (int j = 0; j < ne; ++j) {
     if (names) { store[j] = pre + parts[j]; names[nh + j] = store[j].c_str(); }
     if (offsets) offsets[nh + j] = total;
     total += sz[j];
   }
-  if (offsets && cap > nh + 6) offsets[nh + 6] = total;      // (room for one more: the total)
-  return nh + 6;
+  if (offsets && cap > nh + ne) offsets[nh + ne] = total;    // (room for one more: the total)
+  return nh + ne;
 }
 extern "C" int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq, int scope) {
-  if (!d || B < 1 || Tq < 1 || scope < 0 || scope > 1) return CTRLSIM_EINVAL;
+  if (!d || B < 1 || Tq < 1 || scope < 0 || scope > 2) return CTRLSIM_EINVAL;
   if (scope == 0) return ctrlsim_head_grads_workspace_bytes(d, B, Tq);
+  if (scope == 2) {
+    CrossLayout C;
+    if (d->F < 1 || !cross_layout(*d, B, Tq, C)) return CTRLSIM_EINVAL;
+    return (int64_t)C.a.bytes;
+  }
   TrainLayout L;
   if (d->F < 1 || !train_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
   return (int64_t)L.f.bytes;
@@ -1155,6 +1185,51 @@ extern "C" int ctrlsim_forward_loss_grad_ffn(const ctrlsim_model* m, int B, int 
   const DecLayer& Ld = m->dec[m->d.ND - 1];
   return launch_ffn_block_grad(U, DM, dX, DM, Ld.lin1.w, Ld.lin1.b, Ld.lin2.w, Ld.lin2.b, Ld.n3.g, Ld.n3.b, (long)rows3, m->d.F, ws, L.f,
                                grads + off[nh], dU, DM, st);
+}
+
+// ---- training, second stage (b): ... + the last decoder layer's cross-attention sublayer (csrc/attn_grad.hip).  The forward of the _ffn
+// entry with one more copy: the rows behind norm1 (X1) go to the workspace before the out-projection + norm2 overwrite them.  Mem and its
+// padding bytes are read where the scene side left them: forward_full writes w.src / w.src_pad in scene_side only, the decoder and the
+// heads read them.
+extern "C" int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
+                                               double* per_ctx, float* grads, float* dX, float* x_out, float* dU, float* u_out,
+                                               float* dX1, float* dMem, float* x1_out, float* mem_out, hipStream_t st) {
+  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads || m->d.ND < 1) return CTRLSIM_EINVAL;
+  CrossLayout C;
+  if (!cross_layout(m->d, B, Tq, C)) return CTRLSIM_EINVAL;
+  const TrainLayout& L = C.t;
+  char* ws = static_cast<char*>(workspace);
+  const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.g.l);
+  const int A = m->d.A;
+  const size_t rows3 = (size_t)B * Tq * A * 3;
+  float* X = nullptr;
+  const float* Mem = nullptr;
+  const unsigned char* pad = nullptr;
+  float* U = reinterpret_cast<float*>(ws + L.U);
+  float* X1 = reinterpret_cast<float*>(ws + C.X1);
+  if (!dX) dX = reinterpret_cast<float*>(ws + L.dX);
+  if (!dU) dU = reinterpret_cast<float*>(ws + C.dU);
+  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.mem_seen = &Mem; rq.pad_seen = &pad;
+  CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
+  if (!X || !Mem || !pad) return CTRLSIM_EINVAL;
+  if (x_out && hipMemcpyAsync(x_out, X, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+  if (u_out && hipMemcpyAsync(u_out, U, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+  if (x1_out && hipMemcpyAsync(x1_out, X1, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+  if (mem_out && hipMemcpyAsync(mem_out, Mem, (size_t)B * C.M * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return CTRLSIM_ELAUNCH;
+  CHK(head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L.g, sums, grads, dX, st));
+  GradHeadDesc hd[3];
+  long off[4];
+  const int nh = grad_heads(m->d, m->has_fut, hd, off);
+  const DecLayer& Ld = m->dec[m->d.ND - 1];
+  const long F = m->d.F;
+  CHK(launch_ffn_block_grad(U, DM, dX, DM, Ld.lin1.w, Ld.lin1.b, Ld.lin2.w, Ld.lin2.b, Ld.n3.g, Ld.n3.b, (long)rows3, m->d.F, ws, L.f,
+                            grads + off[nh], dU, DM, st));
+  // the in_proj master [768, 256] = (Wq; Wk; Wv): the query projection's rows, then the memory projection's
+  if (Ld.ckv.w != Ld.cq.w + (long)DM * DM || Ld.ckv.b != Ld.cq.b + DM) return CTRLSIM_EINVAL;
+  return launch_attn_block_grad(X1, DM, Mem, DM, pad, dU, DM, Ld.cq.w, Ld.cq.b, Ld.cout.w, Ld.cout.b, Ld.n2.g, Ld.n2.b, B, Tq * A * 3, C.M,
+                                ws, C.a, grads + off[nh] + 2 * F * DM + F + 3 * DM, dX1, DM, dMem, DM, st);
 }
 
 // The same sums and counts from logits in memory — compute_loss(data, preds) on the tensors of ctrlsim_forward_all (token-row order

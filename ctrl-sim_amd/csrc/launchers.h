@@ -138,6 +138,14 @@ int launch_ffn_block_grad(const float* U, int ldu, const float* dY, int lddy, co
                           const float* b2, const float* gamma, const float* beta, long rows, int F, char* ws, const FfnGradWs& w,
                           float* grads, float* dU, int lddu, hipStream_t st);
 
+// ---- attn_grad.hip: the backward of a post-LN attention sublayer with a key-padding mask (f32-input MFMA from the fp32 master weights)
+struct AttnGradWs { size_t KV, dKV, Q, O, S, dS, dQ, stat, slab, part_ln, part_cq, part_ck, bytes; int chunk_ctx; long nln, ncq, nck; };
+AttnGradWs attn_grad_carve(size_t base, int B, int Lq, int Lk);
+int launch_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, const unsigned char* key_pad, const float* dY, int lddy,
+                           const float* Win, const float* bin, const float* Wo, const float* bo, const float* gamma, const float* beta,
+                           int B, int Lq, int Lk, char* ws, const AttnGradWs& w, float* grads, float* dX, int lddx, float* dMem, int lddm,
+                           hipStream_t st);
+
 // ---- sim.hip
 int launch_sim_init(int S, int N, int E, const float* init_pose, const float* size, const float* edges, const unsigned char* exists, float* phys,
                     float* hist_states, unsigned char* coll, int Tmax1, float* contact_state, hipStream_t st);

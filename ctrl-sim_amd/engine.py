@@ -71,10 +71,11 @@ class HipModel:
         self.handle = h
         self._offset = {n: int(o) for n, o in zip(names, offsets)}
         self._heads = {k: np.array(v, np.float32) for k, v in weights.items() if k.startswith(_pack.HEAD_PREFIXES)}   # host masters of update()
-        # ... and of the last decoder layer's feed-forward block; its out-projection weight (never updated) is an input of the .ffn#wop image
+        # ... and of the last decoder layer's feed-forward block
         self._ffn_layer = f"decoder.transformer_decoder.layers.{self.dims.ND - 1}"
         self._ffn = {self._ffn_layer + s: np.array(weights[self._ffn_layer + s], np.float32) for s in _pack.TRAINABLE_FFN_SUFFIXES}
-        self._ffn_wo = np.array(weights[self._ffn_layer + ".multihead_attn.out_proj.weight"], np.float32)
+        # ... and of its cross-attention sublayer (update(..., cross=True)); the out-projection weight among them is an input of .ffn#wop
+        self._cross = {self._ffn_layer + s: np.array(weights[self._ffn_layer + s], np.float32) for s in _pack.TRAINABLE_CROSS_SUFFIXES}
         self.split_fallback = False     # an engine of this model met non-finite values under f16x3: later split="auto" engines
                                         # (the policy surface opens one per scenario session) start on bf16x6 right away
 
@@ -84,16 +85,19 @@ class HipModel:
             raise RuntimeError(f"workspace query failed: {n}")
         return int(n)
 
-    def update(self, named_tensors):
+    def update(self, named_tensors, cross=False):
         """New fp32 values for tensors of the MLP heads (state-dict names under pack.HEAD_PREFIXES) and of the last decoder layer's
         feed-forward block (its linear1, linear2 and norm3: pack.TRAINABLE_FFN_SUFFIXES) -> torch tensor / ndarray of the tensor's
         shape: written into the packed buffer at the existing offsets, and every packed image `pack.pack` derives from them (operand
         planes of both splits, the cross-entropy image and its padded bias; the fused feed-forward kernels' images) re-derived on the
         host and copied in place.  Offsets never move: the ctrlsim_model handle and everything that points into the buffer stay valid.
-        A value beyond the fp16 range of the two-plane split raises pack's FloatingPointError before anything is written."""
+        A value beyond the fp16 range of the two-plane split raises pack's FloatingPointError before anything is written.
+        cross=True (the training scope "heads+ffn+cross") also takes that layer's cross-attention sublayer (multihead_attn.in_proj /
+        out_proj and norm2: pack.TRAINABLE_CROSS_SUFFIXES) and re-derives pack.cross_images; without it those names are refused like
+        any other trunk tensor, so that a caller in a narrower scope cannot move them by mistake."""
         new = {}
         for k, v in named_tensors.items():
-            master = self._heads if k in self._heads else self._ffn
+            master = self._heads if k in self._heads else self._cross if cross and k in self._cross else self._ffn
             if k not in master:
                 raise KeyError(f"{k}: update() takes the tensors of the MLP heads this model has ({', '.join(_pack.HEAD_PREFIXES)}) and "
                                f"of {self._ffn_layer}'s feed-forward block")
@@ -106,14 +110,18 @@ class HipModel:
         images = _pack.head_images(self.dims, heads, self._offset)          # (raises before the first write)
         if any(k in self._ffn and k.endswith(".weight") and ".linear" in k for k in new):
             layer = {k: new.get(k, v) for k, v in self._ffn.items() if k.endswith(".weight") and ".linear" in k}
-            layer[self._ffn_layer + ".multihead_attn.out_proj.weight"] = self._ffn_wo
+            ko = self._ffn_layer + ".multihead_attn.out_proj.weight"
+            layer[ko] = new.get(ko, self._cross[ko])
             images.update(_pack.ffn_images(self.dims, layer, self._offset))
+        if any(k in self._cross and k.endswith("weight") and ".multihead_attn." in k for k in new):
+            layer = {k: new.get(k, v) for k, v in self._cross.items() if k.endswith("weight") and ".multihead_attn." in k}
+            images.update(_pack.cross_images(self.dims, layer, self._offset))
         for k, v in list(new.items()) + list(images.items()):     # (stream-ordered behind the kernels already enqueued)
             v = v.reshape(-1)
             o = self._offset[k]
             self.flat[o:o + v.size].copy_(torch.from_numpy(v))
         for k, v in new.items():
-            (self._heads if k in self._heads else self._ffn)[k] = v
+            (self._heads if k in self._heads else self._cross if k in self._cross else self._ffn)[k] = v
 
     def __del__(self):
         try:

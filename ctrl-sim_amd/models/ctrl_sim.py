@@ -11,7 +11,9 @@ teacher-forced), or — with `token_index` — the two-pass logits of one timest
 trunk: ctrlsim_forward_loss_grad gives the loss and the head gradients (csrc/head_grad.hip), torch's AdamW steps the fp32 masters,
 `HipModel.update` puts them back into the packed buffer.  `set_trainable("heads+ffn")` adds the last decoder layer's feed-forward block
 (linear1, linear2, norm3): ctrlsim_forward_loss_grad_ffn (csrc/ffn_grad.hip) differentiates it too and returns `dU`, the gradient at
-that block's input, where the cross-attention's backward will start.  The rest of the trunk's backward pass is not built."""
+that block's input; `set_trainable("heads+ffn+cross")` adds that layer's cross-attention sublayer (multihead_attn, norm2):
+ctrlsim_forward_loss_grad_cross (csrc/attn_grad.hip) starts from `dU` and returns `dX1` and `dMem`, the gradients at the layer's norm1
+output and at the scene encoder's output.  The rest of the trunk's backward pass is not built."""
 from __future__ import annotations
 
 import numpy as np
@@ -307,11 +309,12 @@ class CtRLSim:
         return float(sum(np.float64(losses[k]) for k in self.loss_keys()))
 
     # ---- training, second stage (a): the heads and the last decoder layer's feed-forward block
-    SCOPES = ("heads", "heads+ffn")
+    SCOPES = ("heads", "heads+ffn", "heads+ffn+cross")
 
     def set_trainable(self, scope="heads"):
-        """What training_step / configure_optimizers / optimizer_step train: "heads" (the default: the three MLP heads) or "heads+ffn"
-        (the heads and linear1, linear2, norm3 of the last decoder layer).  Choose before configure_optimizers."""
+        """What training_step / configure_optimizers / optimizer_step train: "heads" (the default: the three MLP heads), "heads+ffn"
+        (the heads and linear1, linear2, norm3 of the last decoder layer) or "heads+ffn+cross" (and that layer's cross-attention:
+        multihead_attn.in_proj / out_proj and norm2).  Choose before configure_optimizers."""
         if scope not in self.SCOPES:
             raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES}")
         self._scope = scope
@@ -319,7 +322,8 @@ class CtRLSim:
 
     def train_grad_layout(self, scope=None):
         """head_grad_layout for a scope (ctrlsim_train_grad_layout): "heads" gives exactly head_grad_layout's answer, "heads+ffn" appends
-        the six tensors of the last decoder layer's feed-forward block.  Needs no device."""
+        the six tensors of the last decoder layer's feed-forward block, "heads+ffn+cross" the six of its cross-attention sublayer behind
+        them.  Needs no device."""
         import ctypes as C
         from .. import _lib
         from ..engine import _dims_struct
@@ -336,15 +340,19 @@ class CtRLSim:
 
     def trainable_parameters(self):
         """state-dict name -> torch.nn.Parameter of the selected scope, in layout order: head_parameters() (the same objects), then under
-        "heads+ffn" the six tensors of the last decoder layer's feed-forward block (created once)."""
+        "heads+ffn" the six tensors of the last decoder layer's feed-forward block, under "heads+ffn+cross" the six of its cross-attention
+        sublayer too (each created once)."""
         import torch
         params = dict(self.head_parameters())
-        if self._scope == "heads+ffn":
+        make = lambda names: {k: torch.nn.Parameter(torch.from_numpy(np.array(self.weights[k], np.float32)).to(self.device)) for k in names}
+        if self._scope != "heads":
             if getattr(self, "_ffn_params", None) is None:
-                names = [k for k, _, _ in self.train_grad_layout("heads+ffn")[0] if k not in params]
-                self._ffn_params = {k: torch.nn.Parameter(torch.from_numpy(np.array(self.weights[k], np.float32)).to(self.device))
-                                    for k in names}
+                self._ffn_params = make([k for k, _, _ in self.train_grad_layout("heads+ffn")[0] if k not in params])
             params.update(self._ffn_params)
+        if self._scope == "heads+ffn+cross":
+            if getattr(self, "_cross_params", None) is None:
+                self._cross_params = make([k for k, _, _ in self.train_grad_layout("heads+ffn+cross")[0] if k not in params])
+            params.update(self._cross_params)
         return params
 
     def train_grad_workspace_bytes(self, B, scope="heads+ffn"):
@@ -355,18 +363,30 @@ class CtRLSim:
             raise RuntimeError(f"training gradient workspace query failed: {n}")
         return int(n)
 
-    def loss_and_train_grads_ctx(self, cb, moving, B, dX=False, dU=False, x_out=False, u_out=False, workspace=None):
+    def loss_and_train_grads_ctx(self, cb, moving, B, dX=False, dU=False, x_out=False, u_out=False, workspace=None, dX1=False, dMem=False,
+                                 x1_out=False, mem_out=False, scope=None):
         """loss_and_head_grads_ctx for the scope "heads+ffn" (ctrlsim_forward_loss_grad_ffn): one teacher-forced forward + loss + the
         gradients of the heads and of the last decoder layer's feed-forward block -> (sums, {state-dict name: gradient tensor} in
         train_grad_layout("heads+ffn") order, dX, dU, x_out, u_out), each of the last four [B*T*A*3, 256] or None: the gradient at the
         decoder output, the gradient at the block's input U, the decoder output and U itself.  The gradients are those of the function
-        this call evaluated (the block applied to U as stored)."""
+        this call evaluated (the block applied to U as stored).
+        scope (default: the trainable scope, "heads+ffn" under "heads"): under "heads+ffn+cross" (ctrlsim_forward_loss_grad_cross) the
+        gradients continue with the six cross-attention tensors and the tuple with (dX1, dMem, x1_out, mem_out): the gradient at the
+        layer's norm1 output [B*T*A*3, 256], this layer's share of the gradient at the scene encoder's output [B*M, 256], M = (P + A + 3)
+        & ~3, and the two inputs themselves; everything the narrower scope returns is bit for bit what it returns."""
         import ctypes as C
         import torch
         from .. import _lib
         d, dev = self.dims, self.device
         lib, st = _lib.lib(), _lib.stream_ptr()
-        layout, total = self.train_grad_layout("heads+ffn")
+        if scope is None:
+            scope = self._scope if self._scope != "heads" else "heads+ffn"
+        if scope not in self.SCOPES[1:]:
+            raise ValueError(f"loss_and_train_grads scope {scope!r}: one of {self.SCOPES[1:]}")
+        cross = scope == "heads+ffn+cross"
+        if not cross and (dX1 or dMem or x1_out or mem_out):
+            raise ValueError("dX1, dMem, x1_out and mem_out exist under the scope \"heads+ffn+cross\" only")
+        layout, total = self.train_grad_layout(scope)
         sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
         grads = torch.empty(total, device=dev)
         rows3 = B * d.T * d.A * 3
@@ -374,19 +394,29 @@ class CtRLSim:
         dx, du, xo, uo = buf(dX), buf(dU), buf(x_out), buf(u_out)
         cfg = self.loss_cfg(True)
         coef = float(self.cfg.model.get("loss_action_coef", 1.0))
-        n = self.train_grad_workspace_bytes(B)
+        n = self.train_grad_workspace_bytes(B, scope)
         ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
         assert ws.dtype == torch.uint8 and ws.numel() >= n
+        if cross:
+            rowsm = B * ((d.P + d.A + 3) & ~3)
+            dx1, x1o = buf(dX1), buf(x1_out)
+            dm, mo = (torch.empty(rowsm, d.D, device=dev) if want else None for want in (dMem, mem_out))
+            _lib.check(lib.ctrlsim_forward_loss_grad_cross(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
+                                                           ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo),
+                                                           _lib.ptr(du), _lib.ptr(uo), _lib.ptr(dx1), _lib.ptr(dm), _lib.ptr(x1o), _lib.ptr(mo),
+                                                           st), "forward_loss_grad_cross")
+            named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
+            return sums, named, dx, du, xo, uo, dx1, dm, x1o, mo
         _lib.check(lib.ctrlsim_forward_loss_grad_ffn(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
                                                      ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo),
                                                      _lib.ptr(du), _lib.ptr(uo), st), "forward_loss_grad_ffn")
         named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
         return sums, named, dx, du, xo, uo   # enqueued on the current stream; reading the tensors waits for it
 
-    def loss_and_train_grads(self, data, dX=False, dU=False, x_out=False, u_out=False):
-        """loss_and_train_grads_ctx over reference-layout windows `data`."""
+    def loss_and_train_grads(self, data, dX=False, dU=False, x_out=False, u_out=False, **more):
+        """loss_and_train_grads_ctx over reference-layout windows `data` (more: dX1, dMem, x1_out, mem_out, scope)."""
         cb, moving, B = self._ctx_of(data)
-        return self.loss_and_train_grads_ctx(cb, moving, B, dX=dX, dU=dU, x_out=x_out, u_out=u_out)
+        return self.loss_and_train_grads_ctx(cb, moving, B, dX=dX, dU=dU, x_out=x_out, u_out=u_out, **more)
 
     def _train_backward(self, sums, grads):
         for k, p in self.trainable_parameters().items():
@@ -398,7 +428,7 @@ class CtRLSim:
     def training_step(self, data, batch_idx=0):
         """The reference's training_step for the heads: final_loss of the batch; `.grad` of head_parameters() is filled with its gradient
         (the trunk is frozen: it has no parameters here), `self.logged` holds what the reference logs per step, under its names."""
-        if self._scope == "heads+ffn":
+        if self._scope != "heads":
             sums, grads = self.loss_and_train_grads(data)[:2]
         else:
             sums, grads, _, _ = self.loss_and_head_grads(data)
@@ -406,7 +436,7 @@ class CtRLSim:
 
     def training_step_ctx(self, cb, moving, B):
         """training_step on contexts that are already on the device (windows.build_windows)."""
-        if self._scope == "heads+ffn":
+        if self._scope != "heads":
             sums, grads = self.loss_and_train_grads_ctx(cb, moving, B)[:2]
         else:
             sums, grads, _, _ = self.loss_and_head_grads_ctx(cb, moving, B)
@@ -416,10 +446,11 @@ class CtRLSim:
     def param_groups(names):
         """The reference's AdamW groups (models/ctrl_sim.py:242-268) restricted to `names`: the weight of a Linear decays; every bias
         and every LayerNorm weight (mlp.1 of an MLPLayer, utils/layers.py:6-19; norm1 / norm2 / norm3 of a transformer layer: the
-        reference groups by module type) do not.  Both lists sorted, as there."""
+        reference groups by module type) do not; an attention's in_proj_weight is a weight of a whitelisted module there and decays.
+        Both lists sorted, as there."""
         import re
         ln = re.compile(r"\.(mlp\.1|norm\d*)\.weight$")
-        decay = sorted(k for k in names if k.endswith(".weight") and not ln.search(k))
+        decay = sorted(k for k in names if k.endswith((".weight", ".in_proj_weight")) and not ln.search(k))
         no_decay = sorted(k for k in names if k not in set(decay))
         return decay, no_decay
 
@@ -457,6 +488,6 @@ class CtRLSim:
             scheduler.step()
         optimizer.zero_grad(set_to_none=True)
         new = {k: p.detach().cpu().numpy() for k, p in params.items()}
-        self.hip.update(new)
+        self.hip.update(new, cross=self._scope == "heads+ffn+cross")
         self.weights.update({k: v.copy() for k, v in new.items()})
         return float(norm)

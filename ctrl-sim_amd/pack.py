@@ -270,6 +270,40 @@ def ffn_images(dims: Dims, w: dict, present) -> dict:
     return out
 
 
+TRAINABLE_CROSS_SUFFIXES = (".multihead_attn.in_proj_weight", ".multihead_attn.in_proj_bias", ".multihead_attn.out_proj.weight",
+                            ".multihead_attn.out_proj.bias", ".norm2.weight", ".norm2.bias")
+
+
+def cross_images(dims: Dims, w: dict, present) -> dict:
+    """The packed images `pack` derives from a decoder layer's cross-attention weights, re-derived: `w` holds, under their state-dict
+    names, <layer>.multihead_attn.in_proj_weight and <layer>.multihead_attn.out_proj.weight.  -> {image name: flat float32 array} for
+    every image name in `present`: the operand planes of both splits of the two matrices (the query and the memory projections read
+    row ranges of the in_proj planes), the in_proj's 32-column row blocks, .selfq#wqp (the query projection behind the self-attention
+    out-projection: outproj_q_planes' second image; its first comes from self_attn.out_proj) and .ffn#wop (the out-projection in front
+    of the feed-forward block: ffn_planes_pre's first image; the other two come from linear1 / linear2).  The biases and norm2 have
+    no image but their fp32 rows.  Raises the FloatingPointError of the two-fp16-plane split when a value no longer fits an image that
+    exists."""
+    out = {}
+    sfx = ".multihead_attn.in_proj_weight"
+    for k in w:
+        if not k.endswith(sfx):
+            continue
+        pre = k[:-len(sfx)]
+        Win, Wo = np.asarray(w[k], np.float32), np.asarray(w[pre + ".multihead_attn.out_proj.weight"], np.float32)
+        for sch, suffix in PLANES_SUFFIX.items():
+            for name, v in ((k, Win), (pre + ".multihead_attn.out_proj.weight", Wo)):
+                if name + suffix in present:
+                    out[name + suffix] = split3_planes(v, sch).reshape(-1).view(np.float32)
+        if k + "#blk" + PLANES_SUFFIX[1] in present:
+            out[k + "#blk" + PLANES_SUFFIX[1]] = row_blocks(Win, 1).reshape(-1).view(np.float32)
+        if pre + ".selfq#wqp" + PLANES_SUFFIX[1] in present:
+            Wq = Win[:256]
+            out[pre + ".selfq#wqp" + PLANES_SUFFIX[1]] = row_blocks(np.ascontiguousarray(Wq[:, acc_order_perm(Wq.shape[1])]), 1).reshape(-1).view(np.float32)
+        if pre + ".ffn#wop" + PLANES_SUFFIX[1] in present:
+            out[pre + ".ffn#wop" + PLANES_SUFFIX[1]] = row_blocks(Wo, 1).reshape(-1).view(np.float32)
+    return out
+
+
 def pack(dims: Dims, w: dict):
     """-> (flat float32 ndarray, names list, offsets int64 ndarray in floats)."""
     allw = dict(w)

@@ -338,6 +338,41 @@ int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int
 int ctrlsim_forward_loss_grad_ffn(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
                                   const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
                                   float* grads, float* dX, float* x_out, float* dU, float* u_out, hipStream_t stream);
+/* ---- training, second stage (b): the attention sublayer's backward (csrc/attn_grad.hip) -------------------------------------------
+ * The op.  Forward being differentiated, per context of Lq query rows and Lk memory rows (width 256, 8 heads x 32, LayerNorm eps 1e-5):
+ *   Q = X Wq^T + bq,  K = Mem Wk^T + bk,  V = Mem Wv^T + bv            (in_proj_weight [768,256] = Wq; Wk; Wv, in_proj_bias [768])
+ *   O = concat_h softmax_keys(Q_h K_h^T / sqrt(32)) V_h                 (keys with key_pad = 1 excluded; every key excluded: O = 0)
+ *   S = X + O Wo^T + bo,  Y = LayerNorm(S; gamma, beta)
+ * — the post-LN attention sublayer of torch.nn.TransformerDecoderLayer (cross-attention: Mem = the memory) and, with X = Mem, of
+ * torch.nn.TransformerEncoderLayer.  X [B*Lq, 256], Mem [B*Lk, 256], dY [B*Lq, 256] with leading dimensions >= 256 (floats);
+ * key_pad [B, Lk] bytes, 1 = ignore, NULL = no key padded.  grads: ONE flat float32 buffer d in_proj_weight [768,256], d in_proj_bias
+ * [768], d out_proj.weight [256,256], d out_proj.bias, dgamma, dbeta [256], back to back.  dX (nullable) [B*Lq, 256]: the gradient at X
+ * (residual and query paths); it MAY be dY itself with lddx == lddy.  dMem (nullable) [B*Lk, 256]: the gradient at Mem through K and V
+ * only (with X = Mem the caller adds dX); rows of padded keys are exactly 0.  Any other overlap of an output with an input is undefined.
+ * B, Lq or Lk < 1, a leading dimension below 256 or a null pointer other than key_pad, dX, dMem: CTRLSIM_EINVAL, nothing launched.
+ * Nothing of a forward pass is read but X, Mem and key_pad: Q, K, V, the softmax statistics, O and S are recomputed on the f32-input
+ * MFMA from the fp32 masters, the query rows a chunk of whole contexts at a time (ctrlsim_attn_block_grad_chunk_contexts: <= 8192 rows
+ * where a context has no more).  The gradient is that of the function evaluated this way.  No float atomics, sums in fixed orders:
+ * identical bits from run to run, whatever the workspace held. */
+int64_t ctrlsim_attn_block_grad_workspace_bytes(int B, int Lq, int Lk);
+int ctrlsim_attn_block_grad_chunk_contexts(int B, int Lq, int Lk);
+int ctrlsim_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, const uint8_t* key_pad, const float* dY, int lddy,
+                            const float* in_proj_weight, const float* in_proj_bias, const float* out_proj_weight,
+                            const float* out_proj_bias, const float* gamma, const float* beta, int B, int Lq, int Lk, void* workspace,
+                            float* grads, float* dX, int lddx, float* dMem, int lddm, hipStream_t stream);
+/* Heads + the LAST decoder layer's feed-forward block + its cross-attention sublayer.  ctrlsim_forward_loss_grad_ffn with four more
+ * outputs: grads continues behind the feed-forward tensors with decoder.transformer_decoder.layers.{ND-1}.multihead_attn.in_proj_weight,
+ * .in_proj_bias, .out_proj.weight, .out_proj.bias, .norm2.weight, .norm2.bias (ctrlsim_train_grad_layout with scope 2; scopes 0 and 1
+ * answer as before).  dX1 (nullable) [B*Tq*A*3, 256]: the gradient at the layer's norm1 output, where the self-attention backward will
+ * start; dMem (nullable) [B*M, 256], M = (P + A + 3) & ~3 scene rows per context: this layer's contribution to the gradient at the
+ * scene encoder's output.  x1_out / mem_out (nullable) receive the norm1 output rows and the encoder output the backward read.  The
+ * forward is the _ffn entry's with one more row copy; loss sums, head and feed-forward gradients, dX and dU are bit-identical to that
+ * entry's.  The gradients are those of the sublayer applied to X1 and Mem as stored.  Workspace:
+ * ctrlsim_train_grads_workspace_bytes(dims, B, Tq, 2). */
+int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                                    const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
+                                    float* grads, float* dX, float* x_out, float* dU, float* u_out, float* dX1, float* dMem,
+                                    float* x1_out, float* mem_out, hipStream_t stream);
 /* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
  * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
  * scratch: ctrlsim_loss_scratch_bytes. */
