@@ -1,4 +1,11 @@
-"""GPU parity of the building-block kernels against plain PyTorch fp32 references (tolerances are fp32 rounding)."""
+"""GPU parity of the building-block kernels against plain PyTorch fp32 references (tolerances are fp32 rounding).
+
+Every test that launches a split-operand entry names its operand split (tests/op_cases.py: the `split` fixture binds it before the test
+packs a weight and binds the process default again afterwards) and runs under both: two fp16 planes / three products (namespace s1) and
+three bf16 planes / six products (s0, what split="auto" falls back to).  The bounds are the same under both.  What s0 does not build
+(csrc/gemm_bf16x6.hip, csrc/ffn_fused.hip: the row-stationary in_proj, gemm256_rows, ffn_fused_pre, outproj_ln_q) must refuse with the
+documented return value and leave its output alone.  The "hot" tests at the end run s0 beyond the fp16 range."""
+import functools
 import math
 
 import numpy as np
@@ -10,6 +17,20 @@ pytestmark = pytest.mark.gpu
 from ctrlsim_amd import _lib  # noqa: E402
 import model_oracle as mo  # noqa: E402
 from gpu_utils import DEV, gemm, gemm_bf16x6  # noqa: E402
+import op_cases as oc  # noqa: E402
+from op_cases import split, split_cases  # noqa: E402,F401  (split: the fixture)
+
+EINVAL = -22                                                    # include/ctrlsim.h: CTRLSIM_EINVAL
+NAN = float("nan")
+
+
+def _nel(split):
+    """16-bit elements of one 64-key K / V tile image of one head: NPL planes x (K + V) x 64 x 32."""
+    return 8192 if split == "f16x3" else 12288
+
+
+def _planes16(a):
+    return torch.from_numpy(a.view(np.int16).copy()).to(DEV)
 
 
 @pytest.mark.parametrize("M,N,K,relu,resid", [(128, 128, 256, False, False), (300, 1050, 256, False, False),
@@ -36,21 +57,36 @@ def test_gemm_nt(M, N, K, relu, resid):
     assert torch.equal(out2, W.T[torch.arange(M) % K])
 
 
-@pytest.mark.parametrize("M,N,K,relu,resid,n0", [(128, 256, 256, False, False, 0), (300, 1050, 256, False, False, 0),
-                                                 (1000, 768, 256, True, False, 0), (777, 256, 1024, False, True, 0),
-                                                 (5000, 256, 256, False, False, 256), (24, 1000, 256, False, False, 0),
-                                                 (4097, 512, 512, False, False, 256),
-                                                 # one, odd and few k-steps: prologue / tail of the operand pipeline
-                                                 (300, 200, 16, False, False, 0), (257, 384, 48, True, False, 0),
-                                                 (1000, 130, 80, False, True, 0), (64, 128, 32, False, False, 128)])
-def test_gemm_bf16x6_has_fp32_class_accuracy(M, N, K, relu, resid, n0):
-    """The split-bf16 GEMM must be as accurate as the f32-input MFMA GEMM: both are compared with an fp64 reference."""
+@pytest.fixture
+def gemm6_tile(request):
+    """OPT_GEMM6_TILE (csrc/common.h) for the length of a test: 0 = auto, 1 = 128 x 128, 2 = 64 x 256."""
+    def select(v):
+        _lib.check(_lib.lib().ctrlsim_set_option(2, v))
+    yield select
+    _lib.lib().ctrlsim_set_option(2, 0)
+
+
+@split_cases("M,N,K,relu,resid,n0", [(128, 256, 256, False, False, 0), (300, 1050, 256, False, False, 0),
+                                     (1000, 768, 256, True, False, 0), (777, 256, 1024, False, True, 0),
+                                     (5000, 256, 256, False, False, 256), (24, 1000, 256, False, False, 0),
+                                     (4097, 512, 512, False, False, 256),
+                                     # one, odd and few k-steps: prologue / tail of the operand pipeline
+                                     (300, 200, 16, False, False, 0), (257, 384, 48, True, False, 0),
+                                     (1000, 130, 80, False, True, 0), (64, 128, 32, False, False, 128)],
+             # s0 has the tiled kernel only: one row, around the 32-row wave tile, around the 128- and 256-row tiles, many tiles; one
+             # ragged / one full / several column tiles, with and without a row offset into the planes; one, odd, few and many k-steps
+             [(1, 32, 16, False, False, 0), (31, 130, 48, True, False, 0), (32, 256, 256, False, True, 0),
+              (33, 1050, 80, False, False, 0), (127, 256, 1024, False, True, 256), (129, 130, 256, True, False, 256),
+              (257, 1050, 256, False, False, 0), (1003, 32, 1024, False, False, 256), (1003, 256, 48, False, True, 0),
+              (257, 130, 80, True, False, 256)])
+def test_gemm_bf16x6_has_fp32_class_accuracy(split, gemm6_tile, M, N, K, relu, resid, n0):
+    """The split-operand GEMM must be as accurate as the f32-input MFMA GEMM: both are compared with an fp64 reference.  Under bf16x6
+    every shape goes through the tiled kernel, with both tile shapes (OPT_GEMM6_TILE 1 and 2)."""
     g = torch.Generator().manual_seed(M + N + 7)
     A = (torch.randn(M, K, generator=g) * torch.exp(torch.randn(M, 1, generator=g))).to(DEV)     # rows of varying scale
     Wfull = (torch.randn(n0 + N, K, generator=g) * 0.1)
     b = torch.randn(N, generator=g).to(DEV)
     R = torch.randn(M, N, generator=g).to(DEV) if resid else None
-    out = gemm_bf16x6(A, Wfull, b, R, relu, n0=n0, n=N)
     Wd = Wfull[n0:n0 + N].to(DEV).contiguous()
     out32 = gemm(A, Wd, b, R, relu) if K % 32 == 0 else None       # the f32-input kernel steps K by 32
     ref = A.double() @ Wd.double().T + b.double()
@@ -62,16 +98,21 @@ def test_gemm_bf16x6_has_fp32_class_accuracy(M, N, K, relu, resid, n0):
     if resid:
         scale = scale + R.double().abs()
     scale = scale.clamp_min(1e-30)
-    e6 = ((out.double() - ref).abs() / scale).max().item()
     e32 = ((out32.double() - ref).abs() / scale).max().item() if out32 is not None else 1.0
-    print(f"relative-to-sum|ab| error: bf16x6 {e6:.2e}  f32 mfma {e32:.2e}")
-    assert e6 < 4e-7 and e6 < 8 * e32 + 1e-9, (e6, e32)
+    for tile in ((0,) if split == "f16x3" else (1, 2)):
+        gemm6_tile(tile)
+        out = gemm_bf16x6(A, Wfull, b, R, relu, n0=n0, n=N)
+        e6 = ((out.double() - ref).abs() / scale).max().item()
+        print(f"relative-to-sum|ab| error: {split} tile {tile} {e6:.2e}  f32 mfma {e32:.2e}")
+        assert e6 < 4e-7 and e6 < 8 * e32 + 1e-9, (split, tile, e6, e32)
 
 
-@pytest.mark.parametrize("M,K,relu,resid,ldc", [(1003, 256, False, True, 256), (130, 1024, False, True, 256),
-                                                 (517, 512, True, False, 512), (24, 256, True, False, 256),
-                                                 (333, 16, False, True, 256), (200, 48, False, False, 256)])
-def test_gemm_bf16x6_fused_layernorm(M, K, relu, resid, ldc):
+@split_cases("M,K,relu,resid,ldc", [(1003, 256, False, True, 256), (130, 1024, False, True, 256),
+                                    (517, 512, True, False, 512), (24, 256, True, False, 256),
+                                    (333, 16, False, True, 256), (200, 48, False, False, 256)],
+             [(1, 16, False, True, 256), (31, 48, True, False, 256), (32, 80, False, True, 512), (33, 256, True, True, 256),
+              (127, 1024, False, True, 256), (129, 256, True, False, 512), (257, 256, False, False, 256), (1003, 256, False, True, 512)])
+def test_gemm_bf16x6_fused_layernorm(split, M, K, relu, resid, ldc):
     """LayerNorm in the GEMM epilogue (in place over the residual when there is one) against torch in float64."""
     g = torch.Generator().manual_seed(M + K)
     A = torch.randn(M, K, generator=g).to(DEV)
@@ -91,7 +132,14 @@ def test_gemm_bf16x6_fused_layernorm(M, K, relu, resid, ldc):
         assert torch.equal(out[:, 256:], before[:, 256:])     # columns beyond N untouched
 
 
-@pytest.fixture(params=[0, 7], ids=["tiled", "weight-stationary"])
+_WS_IDS = {"ws_option": {0: "tiled", 7: "weight-stationary"}}
+
+
+def _with_ws(cases, options=(0, 7)):
+    return [(o,) + tuple(c) for o in options for c in cases]
+
+
+@pytest.fixture
 def ws_option(request):
     """OPT_GEMM_WS (csrc/common.h): every Linear(256 -> 256 G) family through the tiled kernel, or through the weight-stationary one."""
     _lib.lib().ctrlsim_set_option(6, request.param)
@@ -99,10 +147,14 @@ def ws_option(request):
     _lib.lib().ctrlsim_set_option(6, 15)                    # the default (common.h: weight-stationary + row-stationary in_proj)
 
 
-@pytest.mark.parametrize("M,relu,resid,ln", [(5000, False, False, False), (8191, False, True, False), (4097, True, False, False),
-                                              (31, False, True, True), (32, True, True, True), (33, False, False, True),
-                                              (16385, False, True, True), (20000, True, False, True)])
-def test_linear256_both_kernels(ws_option, M, relu, resid, ln):
+@split_cases("ws_option,M,relu,resid,ln",
+             _with_ws([(5000, False, False, False), (8191, False, True, False), (4097, True, False, False),
+                       (31, False, True, True), (32, True, True, True), (33, False, False, True),
+                       (16385, False, True, True), (20000, True, False, True)]),
+             # s0 has no weight-stationary kernel (the option is not read there): once, through the tiled one
+             _with_ws([(1, False, True, False), (31, False, True, True), (32, True, True, True), (33, False, False, True),
+                       (129, True, False, False), (257, False, True, False), (1003, False, False, False)], (0,)), ids=_WS_IDS)
+def test_linear256_both_kernels(split, ws_option, M, relu, resid, ln):
     """Linear(256 -> 256) [+ residual] [+ LayerNorm] [+ ReLU] against float64, for both kernels that serve the shape (row counts
     around the 32-row block of the weight-stationary kernel and beyond one block per compute unit)."""
     g = torch.Generator().manual_seed(M)
@@ -122,25 +174,31 @@ def test_linear256_both_kernels(ws_option, M, relu, resid, ln):
     assert (out.double() - ref).abs().max().item() < 2e-5 * max(1.0, scale / 50)
 
 
-@pytest.mark.parametrize("M", [33, 5000, 40000])
-def test_linear256_with_scattered_row_store(M):
+@split_cases("M", [33, 5000, 40000], [33])
+def test_linear256_with_scattered_row_store(split, M):
     """Round 6: the plain Linear(256 -> 256) of the weight-stationary kernel writing result row i to row c_rows[i] of a LARGER row space
     (ctrlsim_gemm256_rows; the map encoder's last Linear fills the polyline rows of the scene-encoder source — modules/encoder.py:155-158's
     concatenation — without a copy kernel): bit-identical to Linear + row copy, entries < 0 are not stored, every other row of the
-    destination is untouched."""
+    destination is untouched.  Under bf16x6 the kernel does not exist: the entry returns 1, nothing launched (include/ctrlsim.h)."""
     from ctrlsim_amd.pack import split3_planes
     g = torch.Generator().manual_seed(M)
     A = torch.randn(M, 256, generator=g).to(DEV)
     W = torch.randn(512, 256, generator=g) * 0.1
     b = torch.randn(256, generator=g).to(DEV)
-    ref = gemm_bf16x6(A, W, b, n0=256, n=256)
     rows = M + M // 8 + 24                                               # 200 polyline rows + 24 vehicle rows per context, as the real map
     perm = torch.randperm(rows, generator=g)[:M].to(torch.int32)
     perm[::97] = -1
     idx = perm.to(DEV)
-    dst = torch.full((rows, 256), 7.5, device=DEV)
     planes = torch.from_numpy(split3_planes(W.numpy()).view(np.int16).copy()).to(DEV)
     p = _lib.ptr
+    if split == "bf16x6":
+        dst = torch.full((rows, 256), NAN, device=DEV)
+        rc = _lib.lib().ctrlsim_gemm256_rows(p(A), 256, p(planes), 512, 256, p(b), p(dst), 256, p(idx), M, _lib.stream_ptr())
+        torch.cuda.synchronize()
+        assert rc == 1 and torch.isnan(dst).all(), rc
+        return
+    ref = gemm_bf16x6(A, W, b, n0=256, n=256)
+    dst = torch.full((rows, 256), 7.5, device=DEV)
     rc = _lib.lib().ctrlsim_gemm256_rows(p(A), 256, p(planes), 512, 256, p(b), p(dst), 256, p(idx), M, _lib.stream_ptr())
     assert rc == 0, rc                                                   # (1 = kernel not applicable: the shipped default must take it)
     torch.cuda.synchronize()
@@ -153,8 +211,9 @@ def test_linear256_with_scattered_row_store(M):
 
 # (160 x 288 = 46 080 rows = 1 440 row blocks of 32: more than four per compute unit, so every persistent workgroup of the weight-stationary
 #  kernel runs its multi-job ring with result stores and the next blocks' requests in flight across the counted-vmcnt barriers)
-@pytest.mark.parametrize("B,L,col0", [(3, 224, 256), (2, 96, 256), (5, 160, 0), (1, 2304, 256), (160, 288, 256), (150, 292, 0)])
-def test_linear_with_kv_image_epilogue(ws_option, B, L, col0):
+@split_cases("ws_option,B,L,col0", _with_ws([(3, 224, 256), (2, 96, 256), (5, 160, 0), (1, 2304, 256), (160, 288, 256), (150, 292, 0)]),
+             _with_ws([(3, 224, 256), (2, 96, 256), (5, 160, 0), (1, 2304, 256), (2, 224, 0)], (0,)), ids=_WS_IDS)
+def test_linear_with_kv_image_epilogue(split, ws_option, B, L, col0):
     """The in_proj Linear whose key / value columns leave as split K / V tile images (ctrlsim_gemm_nt_kv): the images must drive
     the attention kernel to the same output as images split from the fp32 result of the plain Linear, and the fp32 (query)
     columns must match it."""
@@ -180,20 +239,19 @@ def test_linear_with_kv_image_epilogue(ws_option, B, L, col0):
     for im, O in ((img_ref, O0), (img, O1)):
         _lib.check(lib.ctrlsim_attention_presplit(0, p(Q), 256, L * 256, p(im), nkt, p(O), 256, L * 256, None, p(pad), B, L, L, 1, st))
     assert torch.isfinite(O1).all() and (O0 - O1).abs().max().item() < 2e-5
-    used = B * 8 * nkt * (8192 if lib.ctrlsim_split_scheme() == 1 else 12288)
+    used = B * 8 * nkt * _nel(split)
     same = (img.view(-1)[:used] == img_ref.view(-1)[:used]).float().mean().item()   # the leading planes agree bit for bit almost everywhere
     assert same > 0.6, same
 
 
-@pytest.mark.parametrize("B,L,col0", [(3, 224, 256), (2, 96, 256), (5, 160, 0), (1, 2304, 256), (160, 288, 256), (300, 288, 256), (450, 292, 0)])
-def test_row_stationary_linear_with_kv_images(B, L, col0):
+@split_cases("B,L,col0", [(3, 224, 256), (2, 96, 256), (5, 160, 0), (1, 2304, 256), (160, 288, 256), (300, 288, 256), (450, 292, 0)],
+             [(3, 224, 256)])
+def test_row_stationary_linear_with_kv_images(split, B, L, col0):
     """The same in_proj through the ROW-stationary kernel (ctrlsim_gemm_kv_blocks: rows in registers, 32-column weight blocks streamed
     through LDS; one job = 256 rows, so the cases cover a partial single job, one job per compute unit, and more than one job per
     workgroup with the counted waits in flight and a partial last job): query columns and attention driven by its K / V images against the
-    plain Linear + split pass."""
+    plain Linear + split pass.  Under bf16x6 the kernel does not exist: CTRLSIM_EINVAL (include/ctrlsim.h), rows and images untouched."""
     lib = _lib.lib()
-    if lib.ctrlsim_split_scheme() != 1:
-        pytest.skip("two-fp16-plane scheme only")
     g = torch.Generator().manual_seed(7 * B * L + col0)
     N, M, nkt = col0 + 512, B * L, (L + 63) // 64
     A = (torch.randn(M, 256, generator=g) * torch.exp(0.3 * torch.randn(M, 1, generator=g))).to(DEV)
@@ -205,6 +263,12 @@ def test_row_stationary_linear_with_kv_images(B, L, col0):
     from ctrlsim_amd.pack import row_blocks
     blocks = torch.from_numpy(row_blocks(W.numpy(), 1).view(np.int16).copy()).to(DEV)
     C = torch.full((M, max(col0, 4)), float("nan"), device=DEV)
+    if split == "bf16x6":
+        img = torch.full_like(img_ref, 0x7FC0)
+        rc = lib.ctrlsim_gemm_kv_blocks(p(A), 256, p(blocks), p(b), p(C), C.stride(0), M, N, p(img), L, nkt, col0, st)
+        torch.cuda.synchronize()
+        assert rc == EINVAL and torch.isnan(C).all() and bool((img == 0x7FC0).all()), rc
+        return
     img = torch.zeros_like(img_ref)
     _lib.check(lib.ctrlsim_gemm_kv_blocks(p(A), 256, p(blocks), p(b), p(C), C.stride(0), M, N, p(img), L, nkt, col0, st))
     if col0:
@@ -228,12 +292,11 @@ def test_row_stationary_linear_with_kv_images(B, L, col0):
         assert (ktail == 0).all()
 
 
-@pytest.mark.parametrize("M,N", [(300, 256), (65536, 256), (70001, 512), (16385, 64)])
-def test_row_stationary_plain_linear(M, N):
-    """ctrlsim_gemm_kv_blocks without images: a plain Linear(256 -> N) through the row-stationary kernel, against float64."""
+@split_cases("M,N", [(300, 256), (65536, 256), (70001, 512), (16385, 64)], [(300, 256)])
+def test_row_stationary_plain_linear(split, M, N):
+    """ctrlsim_gemm_kv_blocks without images: a plain Linear(256 -> N) through the row-stationary kernel, against float64.  Under bf16x6:
+    CTRLSIM_EINVAL, nothing written."""
     lib = _lib.lib()
-    if lib.ctrlsim_split_scheme() != 1:
-        pytest.skip("two-fp16-plane scheme only")
     g = torch.Generator().manual_seed(M + N)
     A = (torch.randn(M, 256, generator=g) * torch.exp(0.3 * torch.randn(M, 1, generator=g))).to(DEV)
     W = torch.randn(N, 256, generator=g) * 0.1
@@ -242,6 +305,11 @@ def test_row_stationary_plain_linear(M, N):
     blocks = torch.from_numpy(row_blocks(W.numpy(), 1).view(np.int16).copy()).to(DEV)
     C = torch.full((M, N + 4), float("nan"), device=DEV)
     p = _lib.ptr
+    if split == "bf16x6":
+        rc = lib.ctrlsim_gemm_kv_blocks(p(A), 256, p(blocks), p(b), p(C), C.stride(0), M, N, None, 0, 0, 0, _lib.stream_ptr())
+        torch.cuda.synchronize()
+        assert rc == EINVAL and torch.isnan(C).all(), rc
+        return
     _lib.check(lib.ctrlsim_gemm_kv_blocks(p(A), 256, p(blocks), p(b), p(C), C.stride(0), M, N, None, 0, 0, 0, _lib.stream_ptr()))
     ref = A.double() @ W.to(DEV).double().T + b.double()
     scale = (A.double().abs() @ W.to(DEV).double().abs().T + 1).max().item()
@@ -274,15 +342,27 @@ def _attn_ref(q, k, v, vis):  # q [B,H,Lq,32] ... vis bool [B,1|H,Lq,Lk]
     return (torch.softmax(s, -1) @ v.double())
 
 
-@pytest.fixture(params=[0, 1], ids=["f32mfma", "bf16x6"])
+_IMPL_IDS = {"attn_impl": {0: "f32mfma", 1: "bf16x6"}}      # OPT_ATTN_IMPL: the f32-input family, the split-operand family
+
+
+def _with_impl(cases, impls=(0, 1)):
+    return [(i,) + (tuple(c) if isinstance(c, tuple) else (c,)) for i in impls for c in cases]
+
+
+def _both_impls(argnames, cases):
+    """Under f16x3 both kernel families; the f32-input family has no operand split, so under bf16x6 the split family only."""
+    return split_cases("attn_impl," + argnames, _with_impl(cases), _with_impl(cases, (1,)), ids=_IMPL_IDS)
+
+
+@pytest.fixture
 def attn_impl(request):
     _lib.lib().ctrlsim_set_option(0, request.param)
     yield request.param
     _lib.lib().ctrlsim_set_option(0, 1)
 
 
-@pytest.mark.parametrize("A,T", [(24, 32), (4, 4), (6, 8), (24, 7)])
-def test_attention_structured_causal_mask(A, T, attn_impl):
+@_both_impls("A,T", [(24, 32), (4, 4), (6, 8), (24, 7)])
+def test_attention_structured_causal_mask(split, A, T, attn_impl):
     B, H = 2, 8
     L = A * T * 3
     g = torch.Generator().manual_seed(A * T)
@@ -305,8 +385,8 @@ def test_attention_structured_causal_mask(A, T, attn_impl):
     assert (Oc.double() - ref[:, pos.long()]).abs().max().item() < 2e-5
 
 
-@pytest.mark.parametrize("kind", ["sharp", "rising", "falling"])
-def test_attention_sharp_logits_exercise_speculative_and_rescale_paths(kind, attn_impl):
+@_both_impls("kind", ["sharp", "rising", "falling"])
+def test_attention_sharp_logits_exercise_speculative_and_rescale_paths(split, kind, attn_impl):
     """The split-operand kernel exponentiates against its current softmax base and moves the base only when a row sum reaches
     2^15 (a probability would leave the fp16 range of the split's leading plane).  Sharp logits (std 6), keys whose scores rise
     steadily (new maxima in every tile until the bound trips, again and again) and keys whose scores fall (tiny probabilities
@@ -335,9 +415,11 @@ def test_attention_sharp_logits_exercise_speculative_and_rescale_paths(kind, att
     assert (O.double() - ref).abs().max().item() < 3e-5
 
 
-@pytest.mark.parametrize("mode", [2, 3], ids=["il", "trajeglish"])
-@pytest.mark.parametrize("A,T", [(24, 32), (6, 8), (24, 7)])
-def test_attention_mask_variants_of_the_baselines(A, T, mode):
+_AT_MODE = [(A, T, m) for A, T in [(24, 32), (6, 8), (24, 7)] for m in (2, 3)]
+
+
+@split_cases("A,T,mode", _AT_MODE, _AT_MODE, ids={"mode": {2: "il", 3: "trajeglish"}})
+def test_attention_mask_variants_of_the_baselines(split, A, T, mode):
     """Modes 2 / 3 of the structured mask: the IL (state, action) and Trajeglish (action only) models keep the 3-slot token layout
     and the token types they lack are dead as keys.  Restricted to the live tokens the visibility must be get_causal_mask with
     2 / 1 token types (oracle closed form, pinned against the reference in tests/golden/variants.npz)."""
@@ -367,8 +449,8 @@ def test_attention_mask_variants_of_the_baselines(A, T, mode):
     assert (Oc.double() - O[:, pos.long()].double()).abs().max().item() < 2e-5
 
 
-@pytest.mark.parametrize("A,T", [(24, 32), (6, 8), (24, 7), (5, 13), (2, 9)])
-def test_attention_mask_with_attend_own_return_action(A, T):
+@split_cases("A,T", *2 * ([(24, 32), (6, 8), (24, 7), (5, 13), (2, 9)],))
+def test_attention_mask_with_attend_own_return_action(split, A, T):
     """Mode 5 (round 6): the CtRL-Sim mask under cfg.model.attend_own_return_action (utils/train_utils.py:114-129) — of the earlier
     timesteps a query sees the state tokens and its own agent's return / action tokens only — against float64 attention under the
     oracle's closed form (pinned to the reference's get_causal_mask: tests/golden/own_return.npz), over all rows and over the gathered
@@ -395,8 +477,8 @@ def test_attention_mask_with_attend_own_return_action(A, T):
         assert (Oc.double() - ref[:, pos.long()]).abs().max().item() < 2e-5
 
 
-@pytest.mark.parametrize("A,T", [(24, 32), (6, 8), (24, 7), (5, 13)])
-def test_attention_mask_of_the_decision_transformer(A, T):
+@split_cases("A,T", *2 * ([(24, 32), (6, 8), (24, 7), (5, 13)],))
+def test_attention_mask_of_the_decision_transformer(split, A, T):
     """Mode 4: get_causal_mask with state_index 1 for the token order (rtg, state, action), evaluated on tokens stored in the
     slots (state, rtg, action) — i.e. the reference's mask with rows and columns permuted accordingly."""
     B, H = 2, 8
@@ -416,8 +498,8 @@ def test_attention_mask_of_the_decision_transformer(A, T):
     assert (O.double() - ref).abs().max().item() < 2e-5
 
 
-@pytest.mark.parametrize("Lq,Lk", [(224, 224), (2304, 224), (10, 10), (24, 224), (130, 67)])
-def test_attention_key_padding(Lq, Lk, attn_impl):
+@_both_impls("Lq,Lk", [(224, 224), (2304, 224), (10, 10), (24, 224), (130, 67)])
+def test_attention_key_padding(split, Lq, Lk, attn_impl):
     B, H = 3, 8
     g = torch.Generator().manual_seed(Lq + Lk)
     Q = torch.randn(B, Lq, 256, generator=g).to(DEV)
@@ -444,8 +526,9 @@ def _kv_images(K_ptr, V_ptr, ldkv, kbs, B, rows, nkt, pos=None, img=None):
     return img
 
 
+@functools.lru_cache(maxsize=None)
 def _compact_masks(Areg, T, rep):
-    """(visible, m-fold) boolean matrices [L, L] of a compact context's row order — regular rows (t, a < Areg, k) at (t Areg + a) 3 + k,
+    """(Computed once per class and shared by the tests and schemes that need it; nobody writes to it.)  (visible, m-fold) boolean matrices [L, L] of a compact context's row order — regular rows (t, a < Areg, k) at (t Areg + a) 3 + k,
     then, with rep, the representative's rows (t, k) at Lreg + 3 t + k — written from the rules, not from the kernel: a query of step
     tq sees every key of an earlier step, of its own step the state tokens (k = 0) and its own slot's tokens up to itself
     (utils/train_utils.py:81-129); the representative stands for `mult` equal padded slots, so its keys count mult-fold, except that its
@@ -464,8 +547,8 @@ def _compact_masks(Areg, T, rep):
     return vis, mul
 
 
-@pytest.mark.parametrize("Actx,T", [(24, 32), (8, 32), (12, 32), (5, 7), (4, 32), (16, 9), (20, 3), (7, 1)])
-def test_attention_with_mask_tables_equals_in_kernel_masks_and_float64(Actx, T):
+@split_cases("Actx,T", *2 * ([(24, 32), (8, 32), (12, 32), (5, 7), (4, 32), (16, 9), (20, 3), (7, 1)],))
+def test_attention_with_mask_tables_equals_in_kernel_masks_and_float64(split, Actx, T):
     """Round 4: the causal launches over the token rows take their visibility masks from a per-class table (ctrlsim_attention_mask_table,
     one v_cndmask per score) instead of building them per query.  Plain (24-slot) and compact classes, full and short windows (key ranges
     that end inside a sub-tile, query groups that straddle the regular / representative boundary): against float64 with the mask written
@@ -483,7 +566,7 @@ def test_attention_with_mask_tables_equals_in_kernel_masks_and_float64(Actx, T):
     qkv = torch.randn(B, L, 768, generator=g).to(DEV)
     Kp, Vp = qkv.data_ptr() + 1024, qkv.data_ptr() + 2048
     key_pos = torch.tensor([i if i < Lreg else rep_k0 + (i - Lreg) for i in range(L)], dtype=torch.int32, device=DEV)
-    nel = 8192 if lib.ctrlsim_split_scheme() == 1 else 12288
+    nel = _nel(split)
     img = torch.zeros(B * 8 * nkt * nel, dtype=torch.int16, device=DEV)
     _kv_images(Kp, Vp, 768, L * 768, B, L, nkt, pos=key_pos, img=img)
     O_old = torch.zeros(B, L, 256, device=DEV); O_new = torch.full_like(O_old, float("nan"))
@@ -510,9 +593,9 @@ def test_attention_with_mask_tables_equals_in_kernel_masks_and_float64(Actx, T):
         assert (O_old - O_new).abs().max().item() < 5e-6
 
 
-@pytest.mark.parametrize("Actx,T,which", [(24, 32, "last3"), (24, 32, "state"), (8, 32, "last3"), (12, 9, "last3"), (5, 32, "state"),
-                                          (16, 20, "mixed"), (4, 3, "last3")])
-def test_attention_few_query_streaming_form(Actx, T, which):
+@split_cases("Actx,T,which", *2 * ([(24, 32, "last3"), (24, 32, "state"), (8, 32, "last3"), (12, 9, "last3"), (5, 32, "state"),
+                                     (16, 20, "mixed"), (4, 3, "last3")],))
+def test_attention_few_query_streaming_form(split, Actx, T, which):
     """Round 4, option 9: launches with at most 96 queries per context (the second pass, the last decoder layer on the queried rows, the
     K/V-cached steps) run one wave per (context, head, 32 queries) with the K / V fragments read straight from the tile images.  Same
     arithmetic in the same order as the LDS-staged form: bit-identical; and against float64 with the mask written from the rules.
@@ -530,7 +613,7 @@ def test_attention_few_query_streaming_form(Actx, T, which):
     qkv = torch.randn(B, L, 768, generator=g).to(DEV)
     Kp, Vp = qkv.data_ptr() + 1024, qkv.data_ptr() + 2048
     key_pos = torch.tensor([i if i < Lreg else rep_k0 + (i - Lreg) for i in range(L)], dtype=torch.int32, device=DEV)
-    nel = 8192 if lib.ctrlsim_split_scheme() == 1 else 12288
+    nel = _nel(split)
     img = torch.zeros(B * 8 * nkt * nel, dtype=torch.int16, device=DEV)
     _kv_images(Kp, Vp, 768, L * 768, B, L, nkt, pos=key_pos, img=img)
     rows_of = lambda t, ks: [(t * Areg + a) * 3 + k for a in range(Areg) for k in ks] + ([Lreg + 3 * t + k for k in ks] if rep else [])
@@ -568,8 +651,8 @@ def test_attention_few_query_streaming_form(Actx, T, which):
     assert torch.equal(outs[0], outs[1])
 
 
-@pytest.mark.parametrize("Lq,Lk", [(24, 224), (72, 224), (1, 67), (96, 130)])
-def test_attention_few_query_streaming_form_key_padding(Lq, Lk):
+@split_cases("Lq,Lk", *2 * ([(24, 224), (72, 224), (1, 67), (96, 130)],))
+def test_attention_few_query_streaming_form_key_padding(split, Lq, Lk):
     """The same for the key-padding mode over pre-split images (cross attention of the few-row passes)."""
     lib, st, p = _lib.lib(), _lib.stream_ptr(), _lib.ptr
     B, H = 4, 8
@@ -600,8 +683,8 @@ def test_attention_few_query_streaming_form_key_padding(Lq, Lk):
     assert torch.equal(outs[0], outs[1])
 
 
-@pytest.mark.parametrize("A,T", [(24, 32), (6, 8), (24, 7)])
-def test_attention_presplit_images_match_in_kernel_split(A, T):
+@split_cases("A,T", *2 * ([(24, 32), (6, 8), (24, 7)],))
+def test_attention_presplit_images_match_in_kernel_split(split, A, T):
     """K/V split once into bf16 images + DMA staging must give bit-identical output to the in-kernel split, for the
     full build, for a row-scatter (KV-cache) build, and in both mask modes."""
     B = 2
@@ -641,8 +724,11 @@ def test_attention_presplit_images_match_in_kernel_split(A, T):
     assert torch.equal(Oa, Ob) and torch.isfinite(Ob).all()
 
 
-@pytest.mark.parametrize("M,F", [(128, 1024), (1000, 1024), (37, 64), (4133, 512)])
-def test_ffn_fused_block(M, F):
+@split_cases("M,F", [(128, 1024), (1000, 1024), (37, 64), (4133, 512)],
+             # s0: one row, a partial and a full 128-row block, one row past it, several blocks, the launcher's cap F = 4096, and
+             # 33 000 rows = 258 row blocks on 256 persistent workgroups (the wrap)
+             [(1, 32), (37, 64), (128, 1024), (129, 512), (1000, 1024), (130, 4096), (33000, 256)])
+def test_ffn_fused_block(split, M, F):
     """linear1 -> ReLU -> linear2 -> + x -> LayerNorm as one kernel (hidden tile in registers) vs torch in float64,
     out of place and in place."""
     from ctrlsim_amd.pack import ffn_planes
@@ -673,16 +759,23 @@ def test_ffn_fused_block(M, F):
     assert torch.equal(Z, Y)
 
 
-@pytest.mark.parametrize("M,F", [(128, 1024), (1000, 1024), (37, 64), (4133, 512), (40000, 1024)])
-def test_outproj_layernorm_ffn_as_one_kernel(M, F):
+def _refused(rc, *outputs):
+    """The contract of an entry the bound scheme does not build: CTRLSIM_EINVAL, and the NaN-filled outputs as they were."""
+    torch.cuda.synchronize()
+    assert rc == EINVAL, rc
+    assert all(bool(torch.isnan(o).all()) for o in outputs)
+
+
+@split_cases("M,F", [(128, 1024), (1000, 1024), (37, 64), (4133, 512), (40000, 1024)], [(37, 64)])
+def test_outproj_layernorm_ffn_as_one_kernel(split, M, F):
     """The post-LN block in front of a feed-forward block fused into it (ctrlsim_ffn_fused_pre): x1 = LayerNorm0(R + O Wo^T + bo),
     y = LayerNorm(x1 + W2 relu(W1 x1 + b1) + b2) — nn.TransformerDecoderLayer's multihead_attn.out_proj + norm2 + feed-forward + norm3 /
     nn.TransformerEncoderLayer's self_attn.out_proj + norm1 + feed-forward + norm2 (modules/decoder.py:16-20, encoder.py:42-46) — against
-    torch in float64, out of place and with y aliasing the residual rows; and against the two-kernel route it replaces."""
-    from ctrlsim_amd.pack import ffn_planes_pre, ffn_planes, split3_planes
-    if _lib.lib().ctrlsim_get_option(0) != 1:
-        pytest.skip("two-fp16-plane scheme only")
-    g = torch.Generator().manual_seed(M + F + 1)
+    torch in float64, out of place and with y aliasing the residual rows.  Two-fp16-plane scheme only: under bf16x6 (OPT_SPLIT = 0) the entry
+    returns CTRLSIM_EINVAL and writes nothing (csrc/ffn_fused.hip: launch_ffn_fused_pre)."""
+    from ctrlsim_amd.pack import ffn_planes_pre
+    assert _lib.lib().ctrlsim_get_option(4) == (1 if split == "f16x3" else 0)          # OPT_SPLIT
+    g =torch.Generator().manual_seed(M + F + 1)
     O = torch.randn(M, 256, generator=g).to(DEV)
     R = (torch.randn(M, 256, generator=g) * torch.exp(0.5 * torch.randn(M, 1, generator=g))).to(DEV)
     Wo = torch.randn(256, 256, generator=g) * 0.07
@@ -695,10 +788,13 @@ def test_outproj_layernorm_ffn_as_one_kernel(M, F):
     wop, w1q, w2p = ffn_planes_pre(Wo.numpy(), W1.numpy(), W2.numpy(), 1)
     dev = lambda a: torch.from_numpy(a.view(np.int16).copy()).to(DEV)
     wod, w1d, w2d = dev(wop), dev(w1q), dev(w2p)
-    Y = torch.empty_like(R)
+    Y = torch.full_like(R, NAN)
     p = _lib.ptr
-    call = lambda Rr, Yy: _lib.check(_lib.lib().ctrlsim_ffn_fused_pre(p(O), 256, p(Rr), 256, p(wod), p(bo), p(g0), p(be0), p(w1d), p(b1), p(w2d),
-                                                                      p(b2), p(gam), p(bet), p(Yy), 256, M, F, _lib.stream_ptr()), "ffn_fused_pre")
+    raw = lambda Rr, Yy: _lib.lib().ctrlsim_ffn_fused_pre(p(O), 256, p(Rr), 256, p(wod), p(bo), p(g0), p(be0), p(w1d), p(b1), p(w2d),
+                                                          p(b2), p(gam), p(bet), p(Yy), 256, M, F, _lib.stream_ptr())
+    if split == "bf16x6":
+        return _refused(raw(R, Y), Y)
+    call = lambda Rr, Yy: _lib.check(raw(Rr, Yy), "ffn_fused_pre")
     call(R, Y)
     x1 = torch.nn.functional.layer_norm(R.double() + O.double() @ Wo.to(DEV).double().T + bo.double(), (256,), g0.double(), be0.double(), 1e-5)
     h = torch.relu(x1 @ W1.to(DEV).double().T + b1.double())
@@ -713,15 +809,15 @@ def test_outproj_layernorm_ffn_as_one_kernel(M, F):
                                             p(Y), 256, M, 3104, _lib.stream_ptr()) != 0          # beyond the LDS the bias tables fit in
 
 
-@pytest.mark.parametrize("M", [1, 129, 33000])
-def test_outproj_layernorm_ffn_with_strided_rows_and_output_over_the_attention_rows(M):
+@split_cases("M", [1, 129, 33000], [129])
+def test_outproj_layernorm_ffn_with_strided_rows_and_output_over_the_attention_rows(split, M):
     """ctrlsim_ffn_fused_pre with three different leading dimensions (attention output 320, residual 288, output 272 floats) and with the
     output written over the ATTENTION rows (the other aliasing the kernel allows): a wave reads all of its rows before its first store, the
     rows of the next row block it requests ahead are not written by anybody else.  One row, one row past a row block, many row blocks per
-    workgroup (33 000 rows = 258 row blocks on 256 persistent workgroups: the ahead-of-time requests of the last trip are clamped)."""
+    workgroup (33 000 rows = 258 row blocks on 256 persistent workgroups: the ahead-of-time requests of the last trip are clamped).
+    Under bf16x6 (OPT_SPLIT = 0): CTRLSIM_EINVAL, neither the output nor the attention rows written."""
     from ctrlsim_amd.pack import ffn_planes_pre
-    if _lib.lib().ctrlsim_get_option(0) != 1:
-        pytest.skip("two-fp16-plane scheme only")
+    assert _lib.lib().ctrlsim_get_option(4) == (1 if split == "f16x3" else 0)          # OPT_SPLIT
     F = 256
     g = torch.Generator().manual_seed(M)
     Ob = torch.randn(M, 320, generator=g).to(DEV); Rb = torch.randn(M, 288, generator=g).to(DEV)
@@ -736,8 +832,16 @@ def test_outproj_layernorm_ffn_with_strided_rows_and_output_over_the_attention_r
     ref = torch.nn.functional.layer_norm(x1 + h @ W2.to(DEV).double().T + b2.double(), (256,), gam.double(), bet.double(), 1e-5)
     p = _lib.ptr
     Yb = torch.full((M, 272), float("nan"), device=DEV)
-    run = lambda Yp, ldy: _lib.check(_lib.lib().ctrlsim_ffn_fused_pre(p(Ob), 320, p(Rb), 288, p(wod), p(bo), p(g0), p(be0), p(w1d), p(b1), p(w2d), p(b2),
-                                                                      p(gam), p(bet), Yp, ldy, M, F, _lib.stream_ptr()), "ffn_fused_pre")
+    raw = lambda Yp, ldy: _lib.lib().ctrlsim_ffn_fused_pre(p(Ob), 320, p(Rb), 288, p(wod), p(bo), p(g0), p(be0), p(w1d), p(b1), p(w2d), p(b2),
+                                                           p(gam), p(bet), Yp, ldy, M, F, _lib.stream_ptr())
+    if split == "bf16x6":
+        keep = Ob.clone()
+        _refused(raw(p(Yb), 272), Yb)
+        assert raw(p(Ob), 320) == EINVAL
+        torch.cuda.synchronize()
+        assert torch.equal(Ob, keep)
+        return
+    run = lambda Yp, ldy: _lib.check(raw(Yp, ldy), "ffn_fused_pre")
     run(p(Yb), 272)
     assert (Yb[:, :256].double() - ref).abs().max().item() < 5e-5 and torch.isnan(Yb[:, 256:]).all()
     keep = Ob[:, 256:].clone()
@@ -745,13 +849,13 @@ def test_outproj_layernorm_ffn_with_strided_rows_and_output_over_the_attention_r
     assert torch.equal(Ob[:, :256], Yb[:, :256]) and torch.equal(Ob[:, 256:], keep)
 
 
-@pytest.mark.parametrize("M", [128, 1000, 37, 4133, 40000])
-def test_outproj_layernorm_query_projection_as_one_kernel(M):
+@split_cases("M", [128, 1000, 37, 4133, 40000], [37])
+def test_outproj_layernorm_query_projection_as_one_kernel(split, M):
     """x1 = LayerNorm0(R + O Wo^T + bo), q = x1 Wq^T + bq (ctrlsim_outproj_ln_q): nn.TransformerDecoderLayer's self_attn.out_proj + norm1 and
-    the query third of multihead_attn.in_proj (modules/decoder.py:16-20) against torch in float64; x1 written over the residual rows."""
+    the query third of multihead_attn.in_proj (modules/decoder.py:16-20) against torch in float64; x1 written over the residual rows.
+    Under bf16x6 (OPT_SPLIT = 0): CTRLSIM_EINVAL, x1 and q untouched (csrc/ffn_fused.hip: launch_outproj_ln_q)."""
     from ctrlsim_amd.pack import outproj_q_planes
-    if _lib.lib().ctrlsim_get_option(0) != 1:
-        pytest.skip("two-fp16-plane scheme only")
+    assert _lib.lib().ctrlsim_get_option(4) == (1 if split == "f16x3" else 0)          # OPT_SPLIT
     g = torch.Generator().manual_seed(M + 7)
     O = torch.randn(M, 256, generator=g).to(DEV)
     R = (torch.randn(M, 256, generator=g) * torch.exp(0.5 * torch.randn(M, 1, generator=g))).to(DEV)
@@ -763,8 +867,11 @@ def test_outproj_layernorm_query_projection_as_one_kernel(M):
     wod, wqd = dev(wop), dev(wqp)
     X1 = torch.full((M, 256), float("nan"), device=DEV); Q = torch.full((M, 320), float("nan"), device=DEV)
     p = _lib.ptr
-    call = lambda Rr, Xx, Qq, ldq: _lib.check(_lib.lib().ctrlsim_outproj_ln_q(p(O), 256, p(Rr), 256, p(wod), p(bo), p(g0), p(be0), p(wqd), p(bq),
-                                                                              p(Xx), 256, p(Qq), ldq, M, _lib.stream_ptr()), "outproj_ln_q")
+    raw = lambda Rr, Xx, Qq, ldq: _lib.lib().ctrlsim_outproj_ln_q(p(O), 256, p(Rr), 256, p(wod), p(bo), p(g0), p(be0), p(wqd), p(bq),
+                                                                  p(Xx), 256, p(Qq), ldq, M, _lib.stream_ptr())
+    if split == "bf16x6":
+        return _refused(raw(R, X1, Q, 320), X1, Q)
+    call = lambda Rr, Xx, Qq, ldq: _lib.check(raw(Rr, Xx, Qq, ldq), "outproj_ln_q")
     call(R, X1, Q, 320)
     x1 = torch.nn.functional.layer_norm(R.double() + O.double() @ Wo.to(DEV).double().T + bo.double(), (256,), g0.double(), be0.double(), 1e-5)
     q = x1 @ Wq.to(DEV).double().T + bq.double()
@@ -831,3 +938,110 @@ def test_map_pool_matches_the_unfolded_front_end_in_float64(B, NP):
     scale = np.abs(ref).max(1, keepdims=True) + 1e-3
     err = np.abs(got - ref) / scale
     assert err.max() < 2e-5, (err.max(), np.unravel_index(err.argmax(), err.shape))
+
+
+# ---- beyond the fp16 range: what the three-bf16-plane scheme is selected for (tests/op_cases.py: the bound and the seeded inputs;
+# ---- profiles/ops_bf16x6_parity.md: every measured ratio).  The library's own guard pair must stay 0.
+def _guard_reset():
+    assert _lib.lib().ctrlsim_nonfinite_count(1) >= 0
+
+
+def _guard_is_zero():
+    assert _lib.lib().ctrlsim_nonfinite_count(0) == 0
+
+
+@split_cases("M,N,K,resid,ln", [], [(257, 130, 256, False, False), (129, 256, 1024, True, False), (129, 256, 256, True, True),
+                                    (33, 256, 80, False, True)])
+def test_gemm_beyond_the_fp16_range(split, gemm6_tile, M, N, K, resid, ln):
+    """Linear [+ residual] [+ LayerNorm in place over the residual] on rows of magnitude 3e4 exp(randn) (max |x| of some 1e5 to 1e6):
+    both tile shapes of the plain kernel; against float64, measured on the host's float32 evaluation."""
+    A, W, b, R, gam, bet, f64, f32 = oc.hot_gemm_case(M, N, K, resid, ln)
+    assert A.abs().max().item() > 65504.0
+    _guard_reset()
+    for tile in ((0,) if ln else (1, 2)):
+        gemm6_tile(tile)
+        Rd = R.to(DEV) if resid else None
+        out = gemm_bf16x6(A.to(DEV), W, b.to(DEV), Rd, False, ln=(gam.to(DEV), bet.to(DEV)) if ln else None, out=Rd if ln else None)
+        oc.check_hot(f"gemm{'+ln' if ln else ''} {M}x{N}x{K} resid {int(resid)} tile {tile}", out, f64, f32)
+    _guard_is_zero()
+
+
+@split_cases("M,N,K", [(257, 130, 256)], [])
+def test_hot_gemm_leaves_the_range_of_the_two_fp16_planes(split, M, N, K):
+    """The same hot rows under f16x3 (the weights are not hot and pack as usual): the activations' leading plane overflows, so the result
+    is not finite or the guard counts — the contract the automatic fallback relies on
+    (tests/test_gpu_sim_ctx.py::test_operand_split_is_a_runtime_choice_with_automatic_fallback)."""
+    A, W, b, _, _, _, _, _ = oc.hot_gemm_case(M, N, K, False, False)
+    _guard_reset()
+    out = gemm_bf16x6(A.to(DEV), W, b.to(DEV))
+    torch.cuda.synchronize()
+    count = _lib.lib().ctrlsim_nonfinite_count(1)
+    assert count > 0 or not bool(torch.isfinite(out).all())
+
+
+@split_cases("M,F", [], [(129, 512), (37, 64)])
+def test_ffn_fused_block_beyond_the_fp16_range(split, M, F):
+    """ffn_fused<0> on hot rows, out of place and in place."""
+    from ctrlsim_amd.pack import ffn_planes
+    X, W1, b1, W2, b2, gam, bet, f64, f32 = oc.hot_ffn_case(M, F)
+    assert X.abs().max().item() > 65504.0
+    w1d, w2d = (_planes16(a) for a in ffn_planes(W1.numpy(), W2.numpy()))
+    Xd, b1, b2, gam, bet = (t.to(DEV) for t in (X, b1, b2, gam, bet))
+    Y = torch.full_like(Xd, NAN)
+    p = _lib.ptr
+    _guard_reset()
+    _lib.check(_lib.lib().ctrlsim_ffn_fused(p(Xd), 256, p(w1d), p(b1), p(w2d), p(b2), p(gam), p(bet), p(Y), 256, M, F, _lib.stream_ptr()))
+    oc.check_hot(f"ffn_fused {M}x{F}", Y, f64, f32)
+    _lib.check(_lib.lib().ctrlsim_ffn_fused(p(Xd), 256, p(w1d), p(b1), p(w2d), p(b2), p(gam), p(bet), p(Xd), 256, M, F, _lib.stream_ptr()))
+    assert torch.equal(Xd, Y)
+    _guard_is_zero()
+
+
+_GAP = 1e-3                    # least relative distance of a row's two largest scores in float64: the seeds below were drawn for it
+_HOT_SEED = {"pad": 6, "causal": 3}
+
+
+@split_cases("logit_std", [], [50.0, 1e6])
+def test_attention_key_padding_beyond_the_fp16_range(split, logit_std):
+    """Key-padding attention with V rows of magnitude 1e5 and scores of standard deviation 50 (sharp) / 1e6 (one-hot softmax): the
+    in-kernel split, and pre-split images through the few-query streaming form (33 queries, a 3-key tail of the second tile)."""
+    lib, st, p = _lib.lib(), _lib.stream_ptr(), _lib.ptr
+    B, Lq, Lk = 2, 33, 67
+    Q, K, V, g = oc.hot_attn_inputs(B, Lq, Lk, logit_std, _HOT_SEED["pad"])
+    pad = torch.rand(B, Lk, generator=g) < 0.3
+    pad[:, 0] = False
+    vis = (~pad)[:, None, None, :].expand(B, 1, Lq, Lk)
+    q, k, v = oc.heads(Q), oc.heads(K), oc.heads(V)
+    assert oc.top_two_gap(q, k, vis) > _GAP                      # on the host, before the device is asked
+    f64, f32 = (oc.attn_host(q, k, v, vis, dt).transpose(1, 2).reshape(B, Lq, 256) for dt in (torch.float64, torch.float32))
+    Qd, KV, pad_d = Q.to(DEV), torch.cat([K, V], -1).to(DEV), pad.to(torch.uint8).to(DEV)
+    O = torch.full((B, Lq, 256), NAN, device=DEV); O2 = torch.full_like(O, NAN)
+    _guard_reset()
+    _lib.check(lib.ctrlsim_attention(0, p(Qd), 256, Lq * 256, p(KV), KV.data_ptr() + 1024, 512, Lk * 512, p(O), 256, Lq * 256, None,
+                                     p(pad_d), B, Lq, Lk, 24, st))
+    oc.check_hot(f"attention key padding {Lq}x{Lk} std {logit_std:g} in-kernel split", O, f64, f32)
+    nkt = (Lk + 63) // 64
+    img = _kv_images(p(KV), KV.data_ptr() + 1024, 512, Lk * 512, B, Lk, nkt)
+    _lib.check(lib.ctrlsim_attention_presplit(0, p(Qd), 256, Lq * 256, p(img), nkt, p(O2), 256, Lq * 256, None, p(pad_d), B, Lq, Lk, 24, st))
+    oc.check_hot(f"attention key padding {Lq}x{Lk} std {logit_std:g} presplit streaming", O2, f64, f32)
+    _guard_is_zero()
+
+
+@split_cases("logit_std", [], [50.0, 1e6])
+def test_attention_causal_beyond_the_fp16_range(split, logit_std):
+    """The structured causal mask (4 agents x 4 steps x 3 tokens) with V rows of magnitude 1e5 and scores of standard deviation 50 / 1e6."""
+    lib, st, p = _lib.lib(), _lib.stream_ptr(), _lib.ptr
+    B, A, T = 2, 4, 4
+    L = A * T * 3
+    Q, K, V, _ = oc.hot_attn_inputs(B, L, L, logit_std, _HOT_SEED["causal"])
+    vis = mo.causal_mask_closed_form(A, T, 3)[None, None]
+    q, k, v = oc.heads(Q), oc.heads(K), oc.heads(V)
+    assert oc.top_two_gap(q, k, vis) > _GAP
+    f64, f32 = (oc.attn_host(q, k, v, vis, dt).transpose(1, 2).reshape(B, L, 256) for dt in (torch.float64, torch.float32))
+    qkv = torch.cat([Q, K, V], -1).to(DEV)
+    O = torch.full((B, L, 256), NAN, device=DEV)
+    _guard_reset()
+    _lib.check(lib.ctrlsim_attention(1, p(qkv), 768, L * 768, qkv.data_ptr() + 1024, qkv.data_ptr() + 2048, 768, L * 768, p(O), 256,
+                                     L * 256, None, None, B, L, L, A, st))
+    oc.check_hot(f"attention causal A {A} T {T} std {logit_std:g}", O, f64, f32)
+    _guard_is_zero()
