@@ -150,6 +150,10 @@ SIGNATURES = {
     "ctrlsim_train_grads_workspace_bytes": (L, [C.POINTER(Dims), I, I, I]),
     "ctrlsim_forward_loss_grad_ffn": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P, P, P]),
     "ctrlsim_forward_loss_grad_cross": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "ctrlsim_self_attn_block_grad_workspace_bytes": (L, [I, I, I]),
+    "ctrlsim_self_attn_block_grad_chunk_contexts": (I, [I, I, I]),
+    "ctrlsim_self_attn_block_grad": (I, [P, I, P, I, P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
+    "ctrlsim_forward_loss_grad_layer": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "ctrlsim_head_ce": (I, [P, I, P, P, P, I, I, I, P, P]),
     "ctrlsim_loss_scratch_bytes": (L, [I, I, I]),
     "ctrlsim_loss_from_preds": (I, [C.POINTER(Dims), I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), P, P, P, P, P, P, P, P]),

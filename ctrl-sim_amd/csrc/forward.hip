@@ -839,6 +839,8 @@ struct FullReq {
   float* u_store = nullptr;                                 // every-token passes: receives the rows that enter the LAST decoder layer's
                                                             // feed-forward block (its norm2 output), which then runs as a kernel of its own
   float* x1_store = nullptr;                                // ... and the rows that enter its cross-attention sublayer (its norm1 output)
+  float* x0_store = nullptr;                                // ... and the rows that enter that layer (for ND == 1 the assembled tokens), copied
+                                                            // before its first kernel
   const float** mem_seen = nullptr;                         // receive the addresses of the scene encoder's output rows and their key-padding
   const unsigned char** pad_seen = nullptr;                 // bytes in the workspace: written by the scene side, only read from there on
 };
@@ -871,6 +873,9 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
     const DecLayer& Ld = m->dec[i];
     const bool last_few = !(i < d.ND - 1 || every_token);
     const bool kv_only = last_few && ctrlsim_option(OPT_LAST_KV) != 0;
+    if (i == d.ND - 1 && rq.x0_store && every_token &&
+        hipMemcpyAsync(rq.x0_store, w.X, (size_t)bt.rL * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return CTRLSIM_ELAUNCH;
     // the last layer of a rollout pass reads the queries of the A queried tokens only: keys and values of every token (two of the
     // in_proj's three column groups), queries from the gathered rows below — a twelfth of the pass's in_proj work less
     if (kv_only) CHK(gemm_kv(bt, w, Ld.skv, w.X, w.qkv[i] + DM, 3 * DM, 2 * DM, 0, w.img_dec[i], false, st));
@@ -1118,16 +1123,29 @@ bool cross_layout(const ctrlsim_dims& d, int B, int Tq, CrossLayout& o) {
   o.a = attn_grad_carve(o.dU + n, B, Tq * d.A * 3, o.M);
   return true;
 }
+// scope 3, behind that: X0 and a dX1 of its own [B*Tq*A*3, 256], then the self-attention sublayer's workspace
+struct LayerLayout { CrossLayout c; size_t X0, dX1; SelfAttnGradWs s; };
+bool layer_layout(const ctrlsim_dims& d, int B, int Tq, LayerLayout& o) {
+  if (!cross_layout(d, B, Tq, o.c)) return false;
+  const size_t rows3 = (size_t)B * Tq * d.A * 3, n = (rows3 * DM * sizeof(float) + 255) & ~size_t(255);
+  if (rows3 > (size_t)(0x7fffffffL / (3 * DM))) return false;
+  o.X0 = (o.c.a.bytes + 255) & ~size_t(255);
+  o.dX1 = o.X0 + n;
+  o.s = self_attn_grad_carve(o.dX1 + n, B, Tq * d.A * 3);
+  return true;
+}
 }  // namespace
 
 extern "C" int ctrlsim_train_grad_layout(const ctrlsim_dims* d, int has_future_states, int scope, int cap, const char** names,
                                          int64_t* offsets) {
-  static const char* const parts[12] = {".linear1.weight", ".linear1.bias", ".linear2.weight", ".linear2.bias", ".norm3.weight", ".norm3.bias",
+  static const char* const parts[18] = {".linear1.weight", ".linear1.bias", ".linear2.weight", ".linear2.bias", ".norm3.weight", ".norm3.bias",
                                         ".multihead_attn.in_proj_weight", ".multihead_attn.in_proj_bias", ".multihead_attn.out_proj.weight",
-                                        ".multihead_attn.out_proj.bias", ".norm2.weight", ".norm2.bias"};
-  static std::string store[12];
-  if (!d || scope < 0 || scope > 2 || (scope >= 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
-  const int ne = scope == 2 ? 12 : 6;
+                                        ".multihead_attn.out_proj.bias", ".norm2.weight", ".norm2.bias",
+                                        ".self_attn.in_proj_weight", ".self_attn.in_proj_bias", ".self_attn.out_proj.weight",
+                                        ".self_attn.out_proj.bias", ".norm1.weight", ".norm1.bias"};
+  static std::string store[18];
+  if (!d || scope < 0 || scope > 3 || (scope >= 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
+  const int ne = 6 * scope;
   if (scope == 0) return ctrlsim_head_grad_layout(d, has_future_states, cap, names, offsets);
   const int nh = ctrlsim_head_grad_layout(d, has_future_states, 0, nullptr, nullptr);
   if (nh < 0) return nh;
@@ -1137,7 +1155,8 @@ extern "C" int ctrlsim_train_grad_layout(const ctrlsim_dims* d, int has_future_s
   if (ctrlsim_head_grad_layout(d, has_future_states, nh + 1, names, ho.data()) != nh) return CTRLSIM_EINVAL;
   if (offsets) for (int i = 0; i < nh; ++i) offsets[i] = ho[i];
   int64_t total = ho[nh];
-  const int64_t sz[12] = {(int64_t)d->F * DM, d->F, (int64_t)DM * d->F, DM, DM, DM, 3LL * DM * DM, 3 * DM, (int64_t)DM * DM, DM, DM, DM};
+  const int64_t sz[18] = {(int64_t)d->F * DM, d->F, (int64_t)DM * d->F, DM, DM, DM, 3LL * DM * DM, 3 * DM, (int64_t)DM * DM, DM, DM, DM,
+                          3LL * DM * DM, 3 * DM, (int64_t)DM * DM, DM, DM, DM};
   const std::string pre = "decoder.transformer_decoder.layers." + std::to_string(d->ND - 1);
   for (int j = 0; j < ne; ++j) {
     if (names) { store[j] = pre + parts[j]; names[nh + j] = store[j].c_str(); }
@@ -1148,8 +1167,13 @@ extern "C" int ctrlsim_train_grad_layout(const ctrlsim_dims* d, int has_future_s
   return nh + ne;
 }
 extern "C" int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq, int scope) {
-  if (!d || B < 1 || Tq < 1 || scope < 0 || scope > 2) return CTRLSIM_EINVAL;
+  if (!d || B < 1 || Tq < 1 || scope < 0 || scope > 3) return CTRLSIM_EINVAL;
   if (scope == 0) return ctrlsim_head_grads_workspace_bytes(d, B, Tq);
+  if (scope == 3) {
+    LayerLayout Y;
+    if (d->F < 1 || !layer_layout(*d, B, Tq, Y)) return CTRLSIM_EINVAL;
+    return (int64_t)Y.s.bytes;
+  }
   if (scope == 2) {
     CrossLayout C;
     if (d->F < 1 || !cross_layout(*d, B, Tq, C)) return CTRLSIM_EINVAL;
@@ -1191,15 +1215,13 @@ extern "C" int ctrlsim_forward_loss_grad_ffn(const ctrlsim_model* m, int B, int 
 // entry with one more copy: the rows behind norm1 (X1) go to the workspace before the out-projection + norm2 overwrite them.  Mem and its
 // padding bytes are read where the scene side left them: forward_full writes w.src / w.src_pad in scene_side only, the decoder and the
 // heads read them.
-extern "C" int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
-                                               double* per_ctx, float* grads, float* dX, float* x_out, float* dU, float* u_out,
-                                               float* dX1, float* dMem, float* x1_out, float* mem_out, hipStream_t st) {
-  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads || m->d.ND < 1) return CTRLSIM_EINVAL;
-  CrossLayout C;
-  if (!cross_layout(m->d, B, Tq, C)) return CTRLSIM_EINVAL;
+namespace {
+// the _cross entry's work on a CrossLayout; x0_store: one more row copy of the forward (the _layer entry)
+int forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                            const ctrlsim_loss_cfg* cfg, float loss_action_coef, char* ws, const CrossLayout& C, double* sums, double* per_ctx,
+                            float* grads, float* dX, float* x_out, float* dU, float* u_out, float* dX1, float* dMem, float* x1_out,
+                            float* mem_out, float* x0_store, hipStream_t st) {
   const TrainLayout& L = C.t;
-  char* ws = static_cast<char*>(workspace);
   const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.g.l);
   const int A = m->d.A;
   const size_t rows3 = (size_t)B * Tq * A * 3;
@@ -1210,8 +1232,8 @@ extern "C" int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, in
   float* X1 = reinterpret_cast<float*>(ws + C.X1);
   if (!dX) dX = reinterpret_cast<float*>(ws + L.dX);
   if (!dU) dU = reinterpret_cast<float*>(ws + C.dU);
-  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.mem_seen = &Mem; rq.pad_seen = &pad;
-  CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
+  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = x0_store; rq.mem_seen = &Mem; rq.pad_seen = &pad;
+  CHK(forward_full(m, 1, &B, &A, c, Tq, ws, st, rq));
   if (!X || !Mem || !pad) return CTRLSIM_EINVAL;
   if (x_out && hipMemcpyAsync(x_out, X, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
   if (u_out && hipMemcpyAsync(u_out, U, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
@@ -1230,6 +1252,45 @@ extern "C" int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, in
   if (Ld.ckv.w != Ld.cq.w + (long)DM * DM || Ld.ckv.b != Ld.cq.b + DM) return CTRLSIM_EINVAL;
   return launch_attn_block_grad(X1, DM, Mem, DM, pad, dU, DM, Ld.cq.w, Ld.cq.b, Ld.cout.w, Ld.cout.b, Ld.n2.g, Ld.n2.b, B, Tq * A * 3, C.M,
                                 ws, C.a, grads + off[nh] + 2 * F * DM + F + 3 * DM, dX1, DM, dMem, DM, st);
+}
+}  // namespace
+extern "C" int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
+                                               double* per_ctx, float* grads, float* dX, float* x_out, float* dU, float* u_out,
+                                               float* dX1, float* dMem, float* x1_out, float* mem_out, hipStream_t st) {
+  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads || m->d.ND < 1) return CTRLSIM_EINVAL;
+  CrossLayout C;
+  if (!cross_layout(m->d, B, Tq, C)) return CTRLSIM_EINVAL;
+  return forward_loss_grad_cross(m, B, Tq, c, moving, cfg, loss_action_coef, static_cast<char*>(workspace), C, sums, per_ctx, grads, dX, x_out,
+                                 dU, u_out, dX1, dMem, x1_out, mem_out, nullptr, st);
+}
+
+// ---- training (c): ... + the last decoder layer's self-attention sublayer (csrc/self_attn_grad.hip): the whole layer.  The forward of the
+// _cross entry with one more copy: the rows that enter the layer (X0) go to the workspace before its in_proj.  The sublayer's dY is the
+// cross-attention op's dX1; its dX is dX0, the gradient at the layer's input.
+extern "C" int ctrlsim_forward_loss_grad_layer(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
+                                               double* per_ctx, float* grads, float* dX, float* x_out, float* dU, float* u_out,
+                                               float* dX1, float* dMem, float* x1_out, float* mem_out, float* dX0, float* x0_out,
+                                               hipStream_t st) {
+  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads || m->d.ND < 1) return CTRLSIM_EINVAL;
+  if (tok_variant(m->d.variant) != 0 || (m->d.variant != 0 && m->d.variant != 4)) return CTRLSIM_EINVAL;   // CtRL-Sim tokens: (t, a, k), k < 3
+  LayerLayout Y;
+  if (!layer_layout(m->d, B, Tq, Y)) return CTRLSIM_EINVAL;
+  char* ws = static_cast<char*>(workspace);
+  const size_t rows3 = (size_t)B * Tq * m->d.A * 3;
+  float* X0 = reinterpret_cast<float*>(ws + Y.X0);
+  if (!dX1) dX1 = reinterpret_cast<float*>(ws + Y.dX1);
+  CHK(forward_loss_grad_cross(m, B, Tq, c, moving, cfg, loss_action_coef, ws, Y.c, sums, per_ctx, grads, dX, x_out, dU, u_out, dX1, dMem,
+                              x1_out, mem_out, X0, st));
+  if (x0_out && hipMemcpyAsync(x0_out, X0, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+  GradHeadDesc hd[3];
+  long off[4];
+  const int nh = grad_heads(m->d, m->has_fut, hd, off);
+  const DecLayer& Ld = m->dec[m->d.ND - 1];
+  const long F = m->d.F, cross = 4L * DM * DM + 6 * DM;
+  return launch_self_attn_block_grad(X0, DM, dX1, DM, Ld.qkv.w, Ld.qkv.b, Ld.out.w, Ld.out.b, Ld.n1.g, Ld.n1.b, B, Tq, m->d.A,
+                                     m->d.variant == 4 ? 1 : 0, ws, Y.s, grads + off[nh] + 2 * F * DM + F + 3 * DM + cross, dX0, DM, st);
 }
 
 // The same sums and counts from logits in memory — compute_loss(data, preds) on the tensors of ctrlsim_forward_all (token-row order

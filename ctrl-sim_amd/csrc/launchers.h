@@ -146,6 +146,13 @@ int launch_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, c
                            int B, int Lq, int Lk, char* ws, const AttnGradWs& w, float* grads, float* dX, int lddx, float* dMem, int lddm,
                            hipStream_t st);
 
+// ---- self_attn_grad.hip: the backward of a decoder layer's self-attention sublayer under the multi-agent causal mask (contexts of 3 T A rows)
+struct SelfAttnGradWs { size_t QKV, dQKV, O, S, dS, stat, slab, part_ln, part_cs, bytes; int chunk_ctx; long nln, ncs; };
+SelfAttnGradWs self_attn_grad_carve(size_t base, int B, int L);
+int launch_self_attn_block_grad(const float* X, int ldx, const float* dY, int lddy, const float* Win, const float* bin, const float* Wo,
+                                const float* bo, const float* gamma, const float* beta, int B, int T, int A, int mask_mode, char* ws,
+                                const SelfAttnGradWs& w, float* grads, float* dX, int lddx, hipStream_t st);
+
 // ---- sim.hip
 int launch_sim_init(int S, int N, int E, const float* init_pose, const float* size, const float* edges, const unsigned char* exists, float* phys,
                     float* hist_states, unsigned char* coll, int Tmax1, float* contact_state, hipStream_t st);

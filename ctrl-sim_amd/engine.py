@@ -76,6 +76,8 @@ class HipModel:
         self._ffn = {self._ffn_layer + s: np.array(weights[self._ffn_layer + s], np.float32) for s in _pack.TRAINABLE_FFN_SUFFIXES}
         # ... and of its cross-attention sublayer (update(..., cross=True)); the out-projection weight among them is an input of .ffn#wop
         self._cross = {self._ffn_layer + s: np.array(weights[self._ffn_layer + s], np.float32) for s in _pack.TRAINABLE_CROSS_SUFFIXES}
+        # ... and of its self-attention sublayer (update(..., self_attn=True)); the out-projection weight among them is an input of .selfq#wop
+        self._self = {self._ffn_layer + s: np.array(weights[self._ffn_layer + s], np.float32) for s in _pack.TRAINABLE_SELF_SUFFIXES}
         self.split_fallback = False     # an engine of this model met non-finite values under f16x3: later split="auto" engines
                                         # (the policy surface opens one per scenario session) start on bf16x6 right away
 
@@ -85,7 +87,7 @@ class HipModel:
             raise RuntimeError(f"workspace query failed: {n}")
         return int(n)
 
-    def update(self, named_tensors, cross=False):
+    def update(self, named_tensors, cross=False, self_attn=False):
         """New fp32 values for tensors of the MLP heads (state-dict names under pack.HEAD_PREFIXES) and of the last decoder layer's
         feed-forward block (its linear1, linear2 and norm3: pack.TRAINABLE_FFN_SUFFIXES) -> torch tensor / ndarray of the tensor's
         shape: written into the packed buffer at the existing offsets, and every packed image `pack.pack` derives from them (operand
@@ -94,10 +96,13 @@ class HipModel:
         A value beyond the fp16 range of the two-plane split raises pack's FloatingPointError before anything is written.
         cross=True (the training scope "heads+ffn+cross") also takes that layer's cross-attention sublayer (multihead_attn.in_proj /
         out_proj and norm2: pack.TRAINABLE_CROSS_SUFFIXES) and re-derives pack.cross_images; without it those names are refused like
-        any other trunk tensor, so that a caller in a narrower scope cannot move them by mistake."""
+        any other trunk tensor, so that a caller in a narrower scope cannot move them by mistake.
+        self_attn=True (the training scope "heads+last_layer") likewise takes the layer's self-attention sublayer (self_attn.in_proj /
+        out_proj and norm1: pack.TRAINABLE_SELF_SUFFIXES) and re-derives pack.self_images."""
         new = {}
         for k, v in named_tensors.items():
-            master = self._heads if k in self._heads else self._cross if cross and k in self._cross else self._ffn
+            master = (self._heads if k in self._heads else self._cross if cross and k in self._cross else
+                      self._self if self_attn and k in self._self else self._ffn)
             if k not in master:
                 raise KeyError(f"{k}: update() takes the tensors of the MLP heads this model has ({', '.join(_pack.HEAD_PREFIXES)}) and "
                                f"of {self._ffn_layer}'s feed-forward block")
@@ -116,12 +121,15 @@ class HipModel:
         if any(k in self._cross and k.endswith("weight") and ".multihead_attn." in k for k in new):
             layer = {k: new.get(k, v) for k, v in self._cross.items() if k.endswith("weight") and ".multihead_attn." in k}
             images.update(_pack.cross_images(self.dims, layer, self._offset))
+        if any(k in self._self and k.endswith("weight") and ".self_attn." in k for k in new):
+            layer = {k: new.get(k, v) for k, v in self._self.items() if k.endswith("weight") and ".self_attn." in k}
+            images.update(_pack.self_images(self.dims, layer, self._offset))
         for k, v in list(new.items()) + list(images.items()):     # (stream-ordered behind the kernels already enqueued)
             v = v.reshape(-1)
             o = self._offset[k]
             self.flat[o:o + v.size].copy_(torch.from_numpy(v))
         for k, v in new.items():
-            (self._heads if k in self._heads else self._cross if k in self._cross else self._ffn)[k] = v
+            (self._heads if k in self._heads else self._cross if k in self._cross else self._self if k in self._self else self._ffn)[k] = v
 
     def __del__(self):
         try:

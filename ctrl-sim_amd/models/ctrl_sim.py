@@ -13,7 +13,9 @@ trunk: ctrlsim_forward_loss_grad gives the loss and the head gradients (csrc/hea
 (linear1, linear2, norm3): ctrlsim_forward_loss_grad_ffn (csrc/ffn_grad.hip) differentiates it too and returns `dU`, the gradient at
 that block's input; `set_trainable("heads+ffn+cross")` adds that layer's cross-attention sublayer (multihead_attn, norm2):
 ctrlsim_forward_loss_grad_cross (csrc/attn_grad.hip) starts from `dU` and returns `dX1` and `dMem`, the gradients at the layer's norm1
-output and at the scene encoder's output.  The rest of the trunk's backward pass is not built."""
+output and at the scene encoder's output; `set_trainable("heads+last_layer")` adds its self-attention sublayer (self_attn, norm1), so
+that the whole last decoder layer trains: ctrlsim_forward_loss_grad_layer (csrc/self_attn_grad.hip) starts from `dX1` and returns `dX0`,
+the gradient at the layer's input rows.  The backward through the earlier decoder layers, the encoder and the embeddings is not built."""
 from __future__ import annotations
 
 import numpy as np
@@ -309,12 +311,13 @@ class CtRLSim:
         return float(sum(np.float64(losses[k]) for k in self.loss_keys()))
 
     # ---- training, second stage (a): the heads and the last decoder layer's feed-forward block
-    SCOPES = ("heads", "heads+ffn", "heads+ffn+cross")
+    SCOPES = ("heads", "heads+ffn", "heads+ffn+cross", "heads+last_layer")
 
     def set_trainable(self, scope="heads"):
         """What training_step / configure_optimizers / optimizer_step train: "heads" (the default: the three MLP heads), "heads+ffn"
-        (the heads and linear1, linear2, norm3 of the last decoder layer) or "heads+ffn+cross" (and that layer's cross-attention:
-        multihead_attn.in_proj / out_proj and norm2).  Choose before configure_optimizers."""
+        (the heads and linear1, linear2, norm3 of the last decoder layer), "heads+ffn+cross" (and that layer's cross-attention:
+        multihead_attn.in_proj / out_proj and norm2) or "heads+last_layer" (and its self-attention: self_attn.in_proj / out_proj and
+        norm1 — the whole last decoder layer).  Choose before configure_optimizers."""
         if scope not in self.SCOPES:
             raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES}")
         self._scope = scope
@@ -323,7 +326,7 @@ class CtRLSim:
     def train_grad_layout(self, scope=None):
         """head_grad_layout for a scope (ctrlsim_train_grad_layout): "heads" gives exactly head_grad_layout's answer, "heads+ffn" appends
         the six tensors of the last decoder layer's feed-forward block, "heads+ffn+cross" the six of its cross-attention sublayer behind
-        them.  Needs no device."""
+        them, "heads+last_layer" the six of its self-attention sublayer behind those.  Needs no device."""
         import ctypes as C
         from .. import _lib
         from ..engine import _dims_struct
@@ -341,7 +344,7 @@ class CtRLSim:
     def trainable_parameters(self):
         """state-dict name -> torch.nn.Parameter of the selected scope, in layout order: head_parameters() (the same objects), then under
         "heads+ffn" the six tensors of the last decoder layer's feed-forward block, under "heads+ffn+cross" the six of its cross-attention
-        sublayer too (each created once)."""
+        sublayer too, under "heads+last_layer" the six of its self-attention sublayer as well (each created once)."""
         import torch
         params = dict(self.head_parameters())
         make = lambda names: {k: torch.nn.Parameter(torch.from_numpy(np.array(self.weights[k], np.float32)).to(self.device)) for k in names}
@@ -349,10 +352,14 @@ class CtRLSim:
             if getattr(self, "_ffn_params", None) is None:
                 self._ffn_params = make([k for k, _, _ in self.train_grad_layout("heads+ffn")[0] if k not in params])
             params.update(self._ffn_params)
-        if self._scope == "heads+ffn+cross":
+        if self._scope in self.SCOPES[2:]:
             if getattr(self, "_cross_params", None) is None:
                 self._cross_params = make([k for k, _, _ in self.train_grad_layout("heads+ffn+cross")[0] if k not in params])
             params.update(self._cross_params)
+        if self._scope == "heads+last_layer":
+            if getattr(self, "_self_params", None) is None:
+                self._self_params = make([k for k, _, _ in self.train_grad_layout("heads+last_layer")[0] if k not in params])
+            params.update(self._self_params)
         return params
 
     def train_grad_workspace_bytes(self, B, scope="heads+ffn"):
@@ -364,7 +371,7 @@ class CtRLSim:
         return int(n)
 
     def loss_and_train_grads_ctx(self, cb, moving, B, dX=False, dU=False, x_out=False, u_out=False, workspace=None, dX1=False, dMem=False,
-                                 x1_out=False, mem_out=False, scope=None):
+                                 x1_out=False, mem_out=False, scope=None, dX0=False, x0_out=False):
         """loss_and_head_grads_ctx for the scope "heads+ffn" (ctrlsim_forward_loss_grad_ffn): one teacher-forced forward + loss + the
         gradients of the heads and of the last decoder layer's feed-forward block -> (sums, {state-dict name: gradient tensor} in
         train_grad_layout("heads+ffn") order, dX, dU, x_out, u_out), each of the last four [B*T*A*3, 256] or None: the gradient at the
@@ -373,7 +380,9 @@ class CtRLSim:
         scope (default: the trainable scope, "heads+ffn" under "heads"): under "heads+ffn+cross" (ctrlsim_forward_loss_grad_cross) the
         gradients continue with the six cross-attention tensors and the tuple with (dX1, dMem, x1_out, mem_out): the gradient at the
         layer's norm1 output [B*T*A*3, 256], this layer's share of the gradient at the scene encoder's output [B*M, 256], M = (P + A + 3)
-        & ~3, and the two inputs themselves; everything the narrower scope returns is bit for bit what it returns."""
+        & ~3, and the two inputs themselves; everything the narrower scope returns is bit for bit what it returns.  Under
+        "heads+last_layer" (ctrlsim_forward_loss_grad_layer) the gradients continue with the six self-attention tensors and the tuple
+        with (dX0, x0_out): the gradient at the layer's input rows [B*T*A*3, 256] and those rows themselves."""
         import ctypes as C
         import torch
         from .. import _lib
@@ -383,9 +392,12 @@ class CtRLSim:
             scope = self._scope if self._scope != "heads" else "heads+ffn"
         if scope not in self.SCOPES[1:]:
             raise ValueError(f"loss_and_train_grads scope {scope!r}: one of {self.SCOPES[1:]}")
-        cross = scope == "heads+ffn+cross"
+        layer = scope == "heads+last_layer"
+        cross = layer or scope == "heads+ffn+cross"
         if not cross and (dX1 or dMem or x1_out or mem_out):
-            raise ValueError("dX1, dMem, x1_out and mem_out exist under the scope \"heads+ffn+cross\" only")
+            raise ValueError("dX1, dMem, x1_out and mem_out exist from the scope \"heads+ffn+cross\" on only")
+        if not layer and (dX0 or x0_out):
+            raise ValueError("dX0 and x0_out exist under the scope \"heads+last_layer\" only")
         layout, total = self.train_grad_layout(scope)
         sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
         grads = torch.empty(total, device=dev)
@@ -401,6 +413,14 @@ class CtRLSim:
             rowsm = B * ((d.P + d.A + 3) & ~3)
             dx1, x1o = buf(dX1), buf(x1_out)
             dm, mo = (torch.empty(rowsm, d.D, device=dev) if want else None for want in (dMem, mem_out))
+            if layer:
+                dx0, x0o = buf(dX0), buf(x0_out)
+                _lib.check(lib.ctrlsim_forward_loss_grad_layer(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
+                                                               ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo),
+                                                               _lib.ptr(du), _lib.ptr(uo), _lib.ptr(dx1), _lib.ptr(dm), _lib.ptr(x1o), _lib.ptr(mo),
+                                                               _lib.ptr(dx0), _lib.ptr(x0o), st), "forward_loss_grad_layer")
+                named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
+                return sums, named, dx, du, xo, uo, dx1, dm, x1o, mo, dx0, x0o
             _lib.check(lib.ctrlsim_forward_loss_grad_cross(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
                                                            ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo),
                                                            _lib.ptr(du), _lib.ptr(uo), _lib.ptr(dx1), _lib.ptr(dm), _lib.ptr(x1o), _lib.ptr(mo),
@@ -414,7 +434,7 @@ class CtRLSim:
         return sums, named, dx, du, xo, uo   # enqueued on the current stream; reading the tensors waits for it
 
     def loss_and_train_grads(self, data, dX=False, dU=False, x_out=False, u_out=False, **more):
-        """loss_and_train_grads_ctx over reference-layout windows `data` (more: dX1, dMem, x1_out, mem_out, scope)."""
+        """loss_and_train_grads_ctx over reference-layout windows `data` (more: dX1, dMem, x1_out, mem_out, dX0, x0_out, scope)."""
         cb, moving, B = self._ctx_of(data)
         return self.loss_and_train_grads_ctx(cb, moving, B, dX=dX, dU=dU, x_out=x_out, u_out=u_out, **more)
 
@@ -488,6 +508,6 @@ class CtRLSim:
             scheduler.step()
         optimizer.zero_grad(set_to_none=True)
         new = {k: p.detach().cpu().numpy() for k, p in params.items()}
-        self.hip.update(new, cross=self._scope == "heads+ffn+cross")
+        self.hip.update(new, cross=self._scope in self.SCOPES[2:], self_attn=self._scope == "heads+last_layer")
         self.weights.update({k: v.copy() for k, v in new.items()})
         return float(norm)

@@ -304,6 +304,36 @@ def cross_images(dims: Dims, w: dict, present) -> dict:
     return out
 
 
+TRAINABLE_SELF_SUFFIXES = (".self_attn.in_proj_weight", ".self_attn.in_proj_bias", ".self_attn.out_proj.weight",
+                           ".self_attn.out_proj.bias", ".norm1.weight", ".norm1.bias")
+
+
+def self_images(dims: Dims, w: dict, present) -> dict:
+    """The packed images `pack` derives from a decoder layer's self-attention weights, re-derived: `w` holds, under their state-dict
+    names, <layer>.self_attn.in_proj_weight and <layer>.self_attn.out_proj.weight.  -> {image name: flat float32 array} for every image
+    name in `present`: the operand planes of both splits of the two matrices (the query rows / the key + value rows of the last layer's
+    in_proj are row ranges of the in_proj planes), the in_proj's 32-column row blocks and .selfq#wop (the out-projection in front of
+    norm1 and the cross-attention query projection: outproj_q_planes' first image; its second comes from multihead_attn.in_proj_weight).
+    The biases and norm1 have no image but their fp32 rows.  Raises the FloatingPointError of the two-fp16-plane split when a value no
+    longer fits an image that exists."""
+    out = {}
+    sfx = ".self_attn.in_proj_weight"
+    for k in w:
+        if not k.endswith(sfx):
+            continue
+        pre = k[:-len(sfx)]
+        Win, Wo = np.asarray(w[k], np.float32), np.asarray(w[pre + ".self_attn.out_proj.weight"], np.float32)
+        for sch, suffix in PLANES_SUFFIX.items():
+            for name, v in ((k, Win), (pre + ".self_attn.out_proj.weight", Wo)):
+                if name + suffix in present:
+                    out[name + suffix] = split3_planes(v, sch).reshape(-1).view(np.float32)
+        if k + "#blk" + PLANES_SUFFIX[1] in present:
+            out[k + "#blk" + PLANES_SUFFIX[1]] = row_blocks(Win, 1).reshape(-1).view(np.float32)
+        if pre + ".selfq#wop" + PLANES_SUFFIX[1] in present:
+            out[pre + ".selfq#wop" + PLANES_SUFFIX[1]] = row_blocks(Wo, 1).reshape(-1).view(np.float32)
+    return out
+
+
 def pack(dims: Dims, w: dict):
     """-> (flat float32 ndarray, names list, offsets int64 ndarray in floats)."""
     allw = dict(w)

@@ -373,6 +373,38 @@ int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const
                                     const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
                                     float* grads, float* dX, float* x_out, float* dU, float* u_out, float* dX1, float* dMem,
                                     float* x1_out, float* mem_out, hipStream_t stream);
+/* ---- training (c): the causal self-attention sublayer's backward (csrc/self_attn_grad.hip) ----------------------------------------
+ * The op.  Forward being differentiated, per context of L = 3 T A token rows, token i = (t, a, k) = (i / 3A, (i / 3) % A, i % 3):
+ *   Q | K | V = X Win^T + bin                                           (in_proj_weight [768,256], in_proj_bias [768])
+ *   O = concat_h softmax_{visible j}(Q_h K_h^T / sqrt(32)) V_h
+ *   S = X + O Wo^T + bo,  Y = LayerNorm(S; gamma, beta)
+ * — the first sublayer of a decoder layer.  mask_mode 0 (dims.variant 0): visible(i, j) <=> t_j < t_i or (t_j == t_i and ((a_j == a_i
+ * and k_j <= k_i) or k_j == 0)); mask_mode 1 (attend_own_return_action, dims.variant 4): the t_j < t_i term only where a_j == a_i or
+ * k_j == 0.  No key-padding mask.  Masked pairs are excluded by index: their probability is exactly 0.
+ * X, dY [B*L, 256] with leading dimensions >= 256 (floats).  grads: ONE flat float32 buffer d in_proj_weight [768,256], d in_proj_bias
+ * [768], d out_proj.weight [256,256], d out_proj.bias, dgamma, dbeta [256], back to back.  dX (nullable) [B*L, 256] = dS + dQ Wq + dK Wk
+ * + dV Wv; it MAY be dY itself with lddx == lddy.  Any other overlap of an output with an input is undefined.  Argument checks and return
+ * values are ctrlsim_attn_block_grad's; any other mask_mode: CTRLSIM_EINVAL.  Nothing of a forward pass is read but X; query rows a
+ * chunk of whole contexts at a time (ctrlsim_self_attn_block_grad_chunk_contexts: <= 8192 rows where a context has no more); score tiles
+ * wholly beyond a query block's last timestep are never computed.  No float atomics, sums in fixed orders: identical bits from run to
+ * run, whatever the workspace held. */
+int64_t ctrlsim_self_attn_block_grad_workspace_bytes(int B, int T, int A);
+int ctrlsim_self_attn_block_grad_chunk_contexts(int B, int T, int A);
+int ctrlsim_self_attn_block_grad(const float* X, int ldx, const float* dY, int lddy, const float* in_proj_weight,
+                                 const float* in_proj_bias, const float* out_proj_weight, const float* out_proj_bias, const float* gamma,
+                                 const float* beta, int B, int T, int A, int mask_mode, void* workspace, float* grads, float* dX, int lddx,
+                                 hipStream_t stream);
+/* Heads + the whole LAST decoder layer.  ctrlsim_forward_loss_grad_cross with two more outputs: grads continues behind the cross-attention
+ * tensors with decoder.transformer_decoder.layers.{ND-1}.self_attn.in_proj_weight, .in_proj_bias, .out_proj.weight, .out_proj.bias,
+ * .norm1.weight, .norm1.bias (ctrlsim_train_grad_layout with scope 3; scopes 0 to 2 answer as before).  dX0 (nullable) [B*Tq*A*3, 256]:
+ * the gradient at the layer's input rows, where the next layer's backward will start; x0_out (nullable) receives those rows (for ND == 1
+ * the assembled tokens).  The forward is the _cross entry's with one more row copy; loss sums, all narrower-scope gradients, dX, dU, dX1
+ * and dMem are bit-identical to that entry's.  mask_mode follows dims.variant (0: mode 0, 4: mode 1); the baseline token layouts return
+ * CTRLSIM_EINVAL.  Workspace: ctrlsim_train_grads_workspace_bytes(dims, B, Tq, 3). */
+int ctrlsim_forward_loss_grad_layer(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                                    const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
+                                    float* grads, float* dX, float* x_out, float* dU, float* u_out, float* dX1, float* dMem,
+                                    float* x1_out, float* mem_out, float* dX0, float* x0_out, hipStream_t stream);
 /* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
  * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
  * scratch: ctrlsim_loss_scratch_bytes. */
