@@ -54,6 +54,11 @@ class LossCfg(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("supervise_moving", "local_frame_predictions", "fused", "pad_")]
 
 
+class TrainTaps(C.Structure):
+    """ctrlsim_train_taps (include/ctrlsim.h): the optional outputs of ctrlsim_forward_loss_grads, device pointers, each NULL by default."""
+    _fields_ = [(k, C.c_void_p) for k in ("dX", "x_out", "dU", "u_out", "dX1", "dMem", "x1_out", "mem_out", "dX0", "x0_out")]
+
+
 P, I, L, D, F = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_float
 U64 = C.c_uint64
 
@@ -136,10 +141,7 @@ SIGNATURES = {
     "ctrlsim_forward_all": (I, [P, I, I, C.POINTER(Ctx), P, P, P, P, P]),
     "ctrlsim_forward_loss_workspace_bytes": (L, [C.POINTER(Dims), I, I]),
     "ctrlsim_forward_loss": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), P, P, P, P, P]),
-    "ctrlsim_head_grad_layout": (I, [C.POINTER(Dims), I, I, P, P]),
-    "ctrlsim_head_grads_workspace_bytes": (L, [C.POINTER(Dims), I, I]),
     "ctrlsim_heads_loss_grad": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P]),
-    "ctrlsim_forward_loss_grad": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P]),
     "ctrlsim_ffn_block_grad_workspace_bytes": (L, [I, I]),
     "ctrlsim_ffn_block_grad_chunk_rows": (I, [I, I]),
     "ctrlsim_ffn_block_grad": (I, [P, I, P, I, P, P, P, P, P, P, I, I, P, P, P, I, P]),
@@ -148,12 +150,10 @@ SIGNATURES = {
     "ctrlsim_attn_block_grad": (I, [P, I, P, I, P, P, I, P, P, P, P, P, P, I, I, I, P, P, P, I, P, I, P]),
     "ctrlsim_train_grad_layout": (I, [C.POINTER(Dims), I, I, I, P, P]),
     "ctrlsim_train_grads_workspace_bytes": (L, [C.POINTER(Dims), I, I, I]),
-    "ctrlsim_forward_loss_grad_ffn": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P, P, P]),
-    "ctrlsim_forward_loss_grad_cross": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "ctrlsim_forward_loss_grads": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, I, P, P, P, P, C.POINTER(TrainTaps), P]),
     "ctrlsim_self_attn_block_grad_workspace_bytes": (L, [I, I, I]),
     "ctrlsim_self_attn_block_grad_chunk_contexts": (I, [I, I, I]),
     "ctrlsim_self_attn_block_grad": (I, [P, I, P, I, P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
-    "ctrlsim_forward_loss_grad_layer": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "ctrlsim_head_ce": (I, [P, I, P, P, P, I, I, I, P, P]),
     "ctrlsim_loss_scratch_bytes": (L, [I, I, I]),
     "ctrlsim_loss_from_preds": (I, [C.POINTER(Dims), I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), P, P, P, P, P, P, P, P]),

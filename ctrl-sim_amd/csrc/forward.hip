@@ -984,7 +984,9 @@ extern "C" int ctrlsim_forward_loss(const ctrlsim_model* m, int B, int Tq, const
   FullReq rq; rq.loss = &lq;
   return forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq);
 }
-// ---- training, first stage: the gradient of final_loss (models/ctrl_sim.py:207-214) through the heads (csrc/head_grad.hip)
+// ---- training: the gradient of final_loss (models/ctrl_sim.py:207-214) through the heads (csrc/head_grad.hip) and, one scope each, back
+// through the LAST decoder layer: its feed-forward block (scope >= 1, csrc/ffn_grad.hip), its cross-attention sublayer (scope >= 2,
+// csrc/attn_grad.hip) and its self-attention sublayer (scope 3, csrc/self_attn_grad.hip)
 namespace {
 struct GradHeadDesc { const char* name; int n, nsm, k, kind, sm0; };
 // the heads a model of these dims has, in weights.py order, and the float offset of each head's six tensors in `grads`
@@ -1002,17 +1004,57 @@ int grad_nmax(const ctrlsim_dims& d) {
   const int a = d.V > d.R * d.C ? d.V : d.R * d.C;
   return a > 2 * d.T ? a : 2 * d.T;
 }
-struct GradLayout { size_t base; LossWs l; HeadGradWs g; };
-bool grad_layout(const ctrlsim_dims& d, int B, int Tq, GradLayout& o) {
+// the groups behind the heads in `grads`, group g from scope g + 1 on: six tensors of decoder.transformer_decoder.layers.{ND-1}, back to
+// back in state-dict order, perF * F + fixed floats each
+struct GradPart { const char* suffix; long perF, fixed; };
+const GradPart kGroups[3][6] = {
+    {{".linear1.weight", DM, 0}, {".linear1.bias", 1, 0}, {".linear2.weight", DM, 0}, {".linear2.bias", 0, DM}, {".norm3.weight", 0, DM},
+     {".norm3.bias", 0, DM}},
+    {{".multihead_attn.in_proj_weight", 0, 3L * DM * DM}, {".multihead_attn.in_proj_bias", 0, 3 * DM},
+     {".multihead_attn.out_proj.weight", 0, (long)DM * DM}, {".multihead_attn.out_proj.bias", 0, DM}, {".norm2.weight", 0, DM},
+     {".norm2.bias", 0, DM}},
+    {{".self_attn.in_proj_weight", 0, 3L * DM * DM}, {".self_attn.in_proj_bias", 0, 3 * DM}, {".self_attn.out_proj.weight", 0, (long)DM * DM},
+     {".self_attn.out_proj.bias", 0, DM}, {".norm1.weight", 0, DM}, {".norm1.bias", 0, DM}}};
+// float offset in `grads` of group g's first tensor (= the length of scope g's buffer)
+long group_base(const ctrlsim_dims& d, bool has_fut, int g) {
+  GradHeadDesc hd[3];
+  long off[4];
+  long o = off[grad_heads(d, has_fut, hd, off)];
+  for (int k = 0; k < g; ++k)
+    for (const GradPart& p : kGroups[k]) o += p.perF * d.F + p.fixed;
+  return o;
+}
+// The workspace of a scope: the forward's own, the loss buffers, the head-gradient carve, then per scope from 1 on the rows the forward
+// stores for its op (U, X1, X0), a dY [B*Tq*A*3, 256] for that op where the caller takes no tap (dX, dU, dX1), and the op's carve
+// (cross-attention: queries a context's 3 Tq A token rows, keys its M scene rows)
+struct TrainLayout {
+  size_t rows3, bytes;                  // B*Tq*A*3 token rows; the end of the widest carved scope
+  LossWs l; HeadGradWs g;
+  size_t U, dX; FfnGradWs f;            // scope >= 1
+  size_t X1, dU; AttnGradWs a; int M;   // scope >= 2
+  size_t X0, dX1; SelfAttnGradWs s;     // scope 3
+};
+bool train_layout(const ctrlsim_dims& d, int B, int Tq, int scope, TrainLayout& o) {
+  if (scope < 0 || scope > 3 || (scope >= 1 && d.F < 1)) return false;
   const int64_t base = ctrlsim_forward_workspace_bytes(&d, B, Tq);
   if (base < 0) return false;
-  o.base = (size_t)base;
-  o.l = loss_carve(d, o.base, B, Tq);
+  o.rows3 = (size_t)B * Tq * d.A * 3;
+  if (scope >= 3 && o.rows3 > (size_t)(0x7fffffffL / (3 * DM))) return false;     // the self-attention op's Q | K | V rows: below 2^31 floats
+  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t n = up(o.rows3 * DM * sizeof(float));
+  auto rows_and_dy = [&](size_t& rows, size_t& dy) { rows = up(o.bytes); dy = rows + n; return dy + n; };
+  const int L = Tq * d.A * 3;
+  o.l = loss_carve(d, (size_t)base, B, Tq);
   o.g = head_grad_carve(o.l.bytes, (long)B * Tq * d.A, grad_nmax(d));
+  o.bytes = o.g.bytes;
+  o.M = (d.P + d.A + 3) & ~3;
+  if (scope >= 1) { o.f = ffn_grad_carve(rows_and_dy(o.U, o.dX), (long)o.rows3, d.F); o.bytes = o.f.bytes; }
+  if (scope >= 2) { o.a = attn_grad_carve(rows_and_dy(o.X1, o.dU), B, L, o.M); o.bytes = o.a.bytes; }
+  if (scope >= 3) { o.s = self_attn_grad_carve(rows_and_dy(o.X0, o.dX1), B, L); o.bytes = o.s.bytes; }
   return true;
 }
 int head_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving, const ctrlsim_loss_cfg& cfg,
-               float action_coef, const float* X, char* ws, const GradLayout& L, const double* sums, float* grads, float* dX, hipStream_t st) {
+               float action_coef, const float* X, char* ws, const TrainLayout& L, const double* sums, float* grads, float* dX, hipStream_t st) {
   const ctrlsim_dims& d = m->d;
   GradHeadDesc hd[3];
   long off[4];
@@ -1043,254 +1085,109 @@ bool grad_args_ok(const ctrlsim_model* m, int B, int Tq) {
 }
 }  // namespace
 
-extern "C" int ctrlsim_head_grad_layout(const ctrlsim_dims* d, int has_future_states, int cap, const char** names, int64_t* offsets) {
+extern "C" int ctrlsim_train_grad_layout(const ctrlsim_dims* d, int has_future_states, int scope, int cap, const char** names,
+                                         int64_t* offsets) {
   static const char* const parts[6] = {".mlp.0.weight", ".mlp.0.bias", ".mlp.1.weight", ".mlp.1.bias", ".mlp.3.weight", ".mlp.3.bias"};
-  static std::string store[18];
-  if (!d) return CTRLSIM_EINVAL;
+  static std::string store[36];        // the heads' names by kind, then the groups'
+  if (!d || scope < 0 || scope > 3 || (scope >= 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
   GradHeadDesc hd[3];
   long off[4];
-  const int nh = grad_heads(*d, has_future_states != 0, hd, off);
-  if ((names || offsets) && cap < 6 * nh) return CTRLSIM_EINVAL;
+  const int nh = grad_heads(*d, has_future_states != 0, hd, off), n = 6 * (nh + scope);
+  if ((names || offsets) && cap < n) return CTRLSIM_EINVAL;
+  auto put = [&](int i, int slot, const std::string& name, long o) {
+    if (names) { store[slot] = name; names[i] = store[slot].c_str(); }
+    if (offsets) offsets[i] = o;
+  };
   for (int i = 0; i < nh; ++i) {
     const long w = (long)hd[i].n * hd[i].nsm;
     const long sz[6] = {(long)DM * DM, DM, DM, DM, w * DM, w};
     long o = off[i];
-    for (int j = 0; j < 6; ++j) {
-      const int slot = 6 * hd[i].kind + j;
-      if (names) { store[slot] = std::string(hd[i].name) + parts[j]; names[6 * i + j] = store[slot].c_str(); }
-      if (offsets) offsets[6 * i + j] = o;
-      o += sz[j];
-    }
+    for (int j = 0; j < 6; o += sz[j], ++j) put(6 * i + j, 6 * hd[i].kind + j, std::string(hd[i].name) + parts[j], o);
   }
-  if (offsets && cap > 6 * nh) offsets[6 * nh] = off[nh];      // (room for one more: the total)
-  return 6 * nh;
+  const std::string pre = "decoder.transformer_decoder.layers." + std::to_string(d->ND - 1);
+  for (int g = 0; g < scope; ++g) {
+    long o = group_base(*d, has_future_states != 0, g);
+    for (int j = 0; j < 6; o += kGroups[g][j].perF * d->F + kGroups[g][j].fixed, ++j)
+      put(6 * (nh + g) + j, 18 + 6 * g + j, pre + kGroups[g][j].suffix, o);
+  }
+  if (offsets && cap > n) offsets[n] = group_base(*d, has_future_states != 0, scope);      // (room for one more: the total)
+  return n;
 }
-extern "C" int64_t ctrlsim_head_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq) {
-  GradLayout L;
-  if (!d || B < 1 || Tq < 1 || !grad_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
-  return (int64_t)L.g.bytes;
+extern "C" int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq, int scope) {
+  TrainLayout L;
+  if (!d || B < 1 || Tq < 1 || !train_layout(*d, B, Tq, scope, L)) return CTRLSIM_EINVAL;
+  return (int64_t)L.bytes;
 }
 extern "C" int ctrlsim_heads_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
                                        const ctrlsim_loss_cfg* cfg, float loss_action_coef, const float* X, void* workspace, double* sums,
                                        double* per_ctx, float* grads, float* dX, hipStream_t st) {
   if (!grad_args_ok(m, B, Tq) || !c || !cfg || !X || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
-  GradLayout L;
-  if (!grad_layout(m->d, B, Tq, L)) return CTRLSIM_EINVAL;
+  TrainLayout L;
+  if (!train_layout(m->d, B, Tq, 0, L)) return CTRLSIM_EINVAL;
   char* ws = static_cast<char*>(workspace);
   const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.l);
   CHK(heads_loss(m, X, B * Tq * m->d.A, reinterpret_cast<float*>(ws + L.g.H), lq, c, B, Tq, st));
   return head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L, sums, grads, dX, st);
 }
-extern "C" int ctrlsim_forward_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                         const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
-                                         double* per_ctx, float* grads, float* dX, float* x_out, hipStream_t st) {
-  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
-  GradLayout L;
-  if (!grad_layout(m->d, B, Tq, L)) return CTRLSIM_EINVAL;
-  char* ws = static_cast<char*>(workspace);
-  const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.l);
-  const int A = m->d.A;
-  float* X = nullptr;
-  FullReq rq; rq.loss = &lq; rq.x_seen = &X;
-  CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
-  if (!X) return CTRLSIM_EINVAL;
-  if (x_out && hipMemcpyAsync(x_out, X, (size_t)B * Tq * A * 3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return CTRLSIM_ELAUNCH;
-  return head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L, sums, grads, dX, st);
-}
-
-// ---- training, second stage (a): heads + the last decoder layer's feed-forward block (csrc/ffn_grad.hip)
 namespace {
-// behind the head-gradient workspace: U and a dX of its own [B*Tq*A*3, 256], then the block's workspace
-struct TrainLayout { GradLayout g; size_t U, dX; FfnGradWs f; };
-bool train_layout(const ctrlsim_dims& d, int B, int Tq, TrainLayout& o) {
-  if (!grad_layout(d, B, Tq, o.g)) return false;
-  const size_t rows3 = (size_t)B * Tq * d.A * 3, n = (rows3 * DM * sizeof(float) + 255) & ~size_t(255);
-  o.U = (o.g.g.bytes + 255) & ~size_t(255);
-  o.dX = o.U + n;
-  o.f = ffn_grad_carve(o.dX + n, (long)rows3, d.F);
-  return true;
-}
-// scope 2, behind that: X1 and a dU of its own [B*Tq*A*3, 256], then the attention sublayer's workspace (queries: a context's 3 Tq A token
-// rows; keys: its M scene rows)
-struct CrossLayout { TrainLayout t; size_t X1, dU; AttnGradWs a; int M; };
-bool cross_layout(const ctrlsim_dims& d, int B, int Tq, CrossLayout& o) {
-  if (!train_layout(d, B, Tq, o.t)) return false;
-  const size_t rows3 = (size_t)B * Tq * d.A * 3, n = (rows3 * DM * sizeof(float) + 255) & ~size_t(255);
-  o.M = (d.P + d.A + 3) & ~3;
-  o.X1 = (o.t.f.bytes + 255) & ~size_t(255);
-  o.dU = o.X1 + n;
-  o.a = attn_grad_carve(o.dU + n, B, Tq * d.A * 3, o.M);
-  return true;
-}
-// scope 3, behind that: X0 and a dX1 of its own [B*Tq*A*3, 256], then the self-attention sublayer's workspace
-struct LayerLayout { CrossLayout c; size_t X0, dX1; SelfAttnGradWs s; };
-bool layer_layout(const ctrlsim_dims& d, int B, int Tq, LayerLayout& o) {
-  if (!cross_layout(d, B, Tq, o.c)) return false;
-  const size_t rows3 = (size_t)B * Tq * d.A * 3, n = (rows3 * DM * sizeof(float) + 255) & ~size_t(255);
-  if (rows3 > (size_t)(0x7fffffffL / (3 * DM))) return false;
-  o.X0 = (o.c.a.bytes + 255) & ~size_t(255);
-  o.dX1 = o.X0 + n;
-  o.s = self_attn_grad_carve(o.dX1 + n, B, Tq * d.A * 3);
-  return true;
+// `rows` rows [., 256] into a caller's buffer, where the caller gave one
+int copy_rows(float* dst, const float* src, size_t rows, hipStream_t st) {
+  if (dst && hipMemcpyAsync(dst, src, rows * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+  return CTRLSIM_OK;
 }
 }  // namespace
-
-extern "C" int ctrlsim_train_grad_layout(const ctrlsim_dims* d, int has_future_states, int scope, int cap, const char** names,
-                                         int64_t* offsets) {
-  static const char* const parts[18] = {".linear1.weight", ".linear1.bias", ".linear2.weight", ".linear2.bias", ".norm3.weight", ".norm3.bias",
-                                        ".multihead_attn.in_proj_weight", ".multihead_attn.in_proj_bias", ".multihead_attn.out_proj.weight",
-                                        ".multihead_attn.out_proj.bias", ".norm2.weight", ".norm2.bias",
-                                        ".self_attn.in_proj_weight", ".self_attn.in_proj_bias", ".self_attn.out_proj.weight",
-                                        ".self_attn.out_proj.bias", ".norm1.weight", ".norm1.bias"};
-  static std::string store[18];
-  if (!d || scope < 0 || scope > 3 || (scope >= 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
-  const int ne = 6 * scope;
-  if (scope == 0) return ctrlsim_head_grad_layout(d, has_future_states, cap, names, offsets);
-  const int nh = ctrlsim_head_grad_layout(d, has_future_states, 0, nullptr, nullptr);
-  if (nh < 0) return nh;
-  if (!names && !offsets) return nh + ne;
-  if (cap < nh + ne) return CTRLSIM_EINVAL;
-  std::vector<int64_t> ho(nh + 1);
-  if (ctrlsim_head_grad_layout(d, has_future_states, nh + 1, names, ho.data()) != nh) return CTRLSIM_EINVAL;
-  if (offsets) for (int i = 0; i < nh; ++i) offsets[i] = ho[i];
-  int64_t total = ho[nh];
-  const int64_t sz[18] = {(int64_t)d->F * DM, d->F, (int64_t)DM * d->F, DM, DM, DM, 3LL * DM * DM, 3 * DM, (int64_t)DM * DM, DM, DM, DM,
-                          3LL * DM * DM, 3 * DM, (int64_t)DM * DM, DM, DM, DM};
-  const std::string pre = "decoder.transformer_decoder.layers." + std::to_string(d->ND - 1);
-  for (int j = 0; j < ne; ++j) {
-    if (names) { store[j] = pre + parts[j]; names[nh + j] = store[j].c_str(); }
-    if (offsets) offsets[nh + j] = total;
-    total += sz[j];
-  }
-  if (offsets && cap > nh + ne) offsets[nh + ne] = total;    // (room for one more: the total)
-  return nh + ne;
-}
-extern "C" int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq, int scope) {
-  if (!d || B < 1 || Tq < 1 || scope < 0 || scope > 3) return CTRLSIM_EINVAL;
-  if (scope == 0) return ctrlsim_head_grads_workspace_bytes(d, B, Tq);
-  if (scope == 3) {
-    LayerLayout Y;
-    if (d->F < 1 || !layer_layout(*d, B, Tq, Y)) return CTRLSIM_EINVAL;
-    return (int64_t)Y.s.bytes;
-  }
-  if (scope == 2) {
-    CrossLayout C;
-    if (d->F < 1 || !cross_layout(*d, B, Tq, C)) return CTRLSIM_EINVAL;
-    return (int64_t)C.a.bytes;
-  }
+// The teacher-forced forward, the loss, the head gradients, then the ops of the scope from the layer's output back; each op's dY is the dX
+// of the op behind it — the caller's tap, or the workspace's buffer.  Scope 0's forward is ctrlsim_forward_loss's.  From scope 1 on the
+// last decoder layer's out-projection + norm2 and its feed-forward block run as two kernels with U copied to the workspace between them
+// (FullReq::u_store); scope 2 copies the rows behind norm1 (X1) before the out-projection + norm2 overwrite them, scope 3 the rows that
+// enter the layer (X0) before its in_proj.  Mem and its padding bytes are read where the scene side left them: forward_full writes w.src /
+// w.src_pad in scene_side only, the decoder and the heads read them.
+extern "C" int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                          const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
+                                          double* per_ctx, float* grads, const ctrlsim_train_taps* taps, hipStream_t st) {
+  static const ctrlsim_train_taps none{};
+  const ctrlsim_train_taps& t = taps ? *taps : none;
+  if (scope < 0 || scope > 3 || !grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
+  if ((scope < 1 && (t.dU || t.u_out)) || (scope < 2 && (t.dX1 || t.dMem || t.x1_out || t.mem_out)) || (scope < 3 && (t.dX0 || t.x0_out)))
+    return CTRLSIM_EINVAL;                                                        // a tap of a wider scope than the call's
+  const ctrlsim_dims& d = m->d;
+  if (scope >= 1 && d.ND < 1) return CTRLSIM_EINVAL;
+  if (scope >= 3 && (tok_variant(d.variant) != 0 || (d.variant != 0 && d.variant != 4))) return CTRLSIM_EINVAL;   // CtRL-Sim tokens: (t, a, k), k < 3
+  const DecLayer* Ld = scope >= 1 ? &m->dec[d.ND - 1] : nullptr;
+  // the in_proj master [768, 256] = (Wq; Wk; Wv): the query projection's rows, then the memory projection's
+  if (scope >= 2 && (Ld->ckv.w != Ld->cq.w + (long)DM * DM || Ld->ckv.b != Ld->cq.b + DM)) return CTRLSIM_EINVAL;
   TrainLayout L;
-  if (d->F < 1 || !train_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
-  return (int64_t)L.f.bytes;
-}
-extern "C" int ctrlsim_forward_loss_grad_ffn(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                             const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
-                                             double* per_ctx, float* grads, float* dX, float* x_out, float* dU, float* u_out,
-                                             hipStream_t st) {
-  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads || m->d.ND < 1) return CTRLSIM_EINVAL;
-  TrainLayout L;
-  if (!train_layout(m->d, B, Tq, L)) return CTRLSIM_EINVAL;
+  if (!train_layout(d, B, Tq, scope, L)) return CTRLSIM_EINVAL;
   char* ws = static_cast<char*>(workspace);
-  const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.g.l);
-  const int A = m->d.A;
-  const size_t rows3 = (size_t)B * Tq * A * 3;
-  float* X = nullptr;
-  float* U = reinterpret_cast<float*>(ws + L.U);
-  if (!dX) dX = reinterpret_cast<float*>(ws + L.dX);
-  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U;
-  CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
-  if (!X) return CTRLSIM_EINVAL;
-  if (x_out && hipMemcpyAsync(x_out, X, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
-  if (u_out && hipMemcpyAsync(u_out, U, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
-  CHK(head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L.g, sums, grads, dX, st));
-  GradHeadDesc hd[3];
-  long off[4];
-  const int nh = grad_heads(m->d, m->has_fut, hd, off);
-  const DecLayer& Ld = m->dec[m->d.ND - 1];
-  return launch_ffn_block_grad(U, DM, dX, DM, Ld.lin1.w, Ld.lin1.b, Ld.lin2.w, Ld.lin2.b, Ld.n3.g, Ld.n3.b, (long)rows3, m->d.F, ws, L.f,
-                               grads + off[nh], dU, DM, st);
-}
-
-// ---- training, second stage (b): ... + the last decoder layer's cross-attention sublayer (csrc/attn_grad.hip).  The forward of the _ffn
-// entry with one more copy: the rows behind norm1 (X1) go to the workspace before the out-projection + norm2 overwrite them.  Mem and its
-// padding bytes are read where the scene side left them: forward_full writes w.src / w.src_pad in scene_side only, the decoder and the
-// heads read them.
-namespace {
-// the _cross entry's work on a CrossLayout; x0_store: one more row copy of the forward (the _layer entry)
-int forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                            const ctrlsim_loss_cfg* cfg, float loss_action_coef, char* ws, const CrossLayout& C, double* sums, double* per_ctx,
-                            float* grads, float* dX, float* x_out, float* dU, float* u_out, float* dX1, float* dMem, float* x1_out,
-                            float* mem_out, float* x0_store, hipStream_t st) {
-  const TrainLayout& L = C.t;
-  const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.g.l);
-  const int A = m->d.A;
-  const size_t rows3 = (size_t)B * Tq * A * 3;
-  float* X = nullptr;
+  auto at = [&](bool have, size_t o) { return have ? reinterpret_cast<float*>(ws + o) : nullptr; };
+  const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.l);
+  const int A = d.A;
+  float *X = nullptr, *U = at(scope >= 1, L.U), *X1 = at(scope >= 2, L.X1), *X0 = at(scope >= 3, L.X0);
+  float *dX = t.dX ? t.dX : at(scope >= 1, L.dX), *dU = t.dU ? t.dU : at(scope >= 2, L.dU), *dX1 = t.dX1 ? t.dX1 : at(scope >= 3, L.dX1);
   const float* Mem = nullptr;
   const unsigned char* pad = nullptr;
-  float* U = reinterpret_cast<float*>(ws + L.U);
-  float* X1 = reinterpret_cast<float*>(ws + C.X1);
-  if (!dX) dX = reinterpret_cast<float*>(ws + L.dX);
-  if (!dU) dU = reinterpret_cast<float*>(ws + C.dU);
-  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = x0_store; rq.mem_seen = &Mem; rq.pad_seen = &pad;
-  CHK(forward_full(m, 1, &B, &A, c, Tq, ws, st, rq));
-  if (!X || !Mem || !pad) return CTRLSIM_EINVAL;
-  if (x_out && hipMemcpyAsync(x_out, X, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
-  if (u_out && hipMemcpyAsync(u_out, U, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
-  if (x1_out && hipMemcpyAsync(x1_out, X1, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
-  if (mem_out && hipMemcpyAsync(mem_out, Mem, (size_t)B * C.M * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return CTRLSIM_ELAUNCH;
-  CHK(head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L.g, sums, grads, dX, st));
-  GradHeadDesc hd[3];
-  long off[4];
-  const int nh = grad_heads(m->d, m->has_fut, hd, off);
-  const DecLayer& Ld = m->dec[m->d.ND - 1];
-  const long F = m->d.F;
-  CHK(launch_ffn_block_grad(U, DM, dX, DM, Ld.lin1.w, Ld.lin1.b, Ld.lin2.w, Ld.lin2.b, Ld.n3.g, Ld.n3.b, (long)rows3, m->d.F, ws, L.f,
-                            grads + off[nh], dU, DM, st));
-  // the in_proj master [768, 256] = (Wq; Wk; Wv): the query projection's rows, then the memory projection's
-  if (Ld.ckv.w != Ld.cq.w + (long)DM * DM || Ld.ckv.b != Ld.cq.b + DM) return CTRLSIM_EINVAL;
-  return launch_attn_block_grad(X1, DM, Mem, DM, pad, dU, DM, Ld.cq.w, Ld.cq.b, Ld.cout.w, Ld.cout.b, Ld.n2.g, Ld.n2.b, B, Tq * A * 3, C.M,
-                                ws, C.a, grads + off[nh] + 2 * F * DM + F + 3 * DM, dX1, DM, dMem, DM, st);
-}
-}  // namespace
-extern "C" int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
-                                               double* per_ctx, float* grads, float* dX, float* x_out, float* dU, float* u_out,
-                                               float* dX1, float* dMem, float* x1_out, float* mem_out, hipStream_t st) {
-  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads || m->d.ND < 1) return CTRLSIM_EINVAL;
-  CrossLayout C;
-  if (!cross_layout(m->d, B, Tq, C)) return CTRLSIM_EINVAL;
-  return forward_loss_grad_cross(m, B, Tq, c, moving, cfg, loss_action_coef, static_cast<char*>(workspace), C, sums, per_ctx, grads, dX, x_out,
-                                 dU, u_out, dX1, dMem, x1_out, mem_out, nullptr, st);
-}
-
-// ---- training (c): ... + the last decoder layer's self-attention sublayer (csrc/self_attn_grad.hip): the whole layer.  The forward of the
-// _cross entry with one more copy: the rows that enter the layer (X0) go to the workspace before its in_proj.  The sublayer's dY is the
-// cross-attention op's dX1; its dX is dX0, the gradient at the layer's input.
-extern "C" int ctrlsim_forward_loss_grad_layer(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
-                                               double* per_ctx, float* grads, float* dX, float* x_out, float* dU, float* u_out,
-                                               float* dX1, float* dMem, float* x1_out, float* mem_out, float* dX0, float* x0_out,
-                                               hipStream_t st) {
-  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads || m->d.ND < 1) return CTRLSIM_EINVAL;
-  if (tok_variant(m->d.variant) != 0 || (m->d.variant != 0 && m->d.variant != 4)) return CTRLSIM_EINVAL;   // CtRL-Sim tokens: (t, a, k), k < 3
-  LayerLayout Y;
-  if (!layer_layout(m->d, B, Tq, Y)) return CTRLSIM_EINVAL;
-  char* ws = static_cast<char*>(workspace);
-  const size_t rows3 = (size_t)B * Tq * m->d.A * 3;
-  float* X0 = reinterpret_cast<float*>(ws + Y.X0);
-  if (!dX1) dX1 = reinterpret_cast<float*>(ws + Y.dX1);
-  CHK(forward_loss_grad_cross(m, B, Tq, c, moving, cfg, loss_action_coef, ws, Y.c, sums, per_ctx, grads, dX, x_out, dU, u_out, dX1, dMem,
-                              x1_out, mem_out, X0, st));
-  if (x0_out && hipMemcpyAsync(x0_out, X0, rows3 * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
-  GradHeadDesc hd[3];
-  long off[4];
-  const int nh = grad_heads(m->d, m->has_fut, hd, off);
-  const DecLayer& Ld = m->dec[m->d.ND - 1];
-  const long F = m->d.F, cross = 4L * DM * DM + 6 * DM;
-  return launch_self_attn_block_grad(X0, DM, dX1, DM, Ld.qkv.w, Ld.qkv.b, Ld.out.w, Ld.out.b, Ld.n1.g, Ld.n1.b, B, Tq, m->d.A,
-                                     m->d.variant == 4 ? 1 : 0, ws, Y.s, grads + off[nh] + 2 * F * DM + F + 3 * DM + cross, dX0, DM, st);
+  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = X0;
+  if (scope >= 2) { rq.mem_seen = &Mem; rq.pad_seen = &pad; }
+  CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
+  if (!X || (scope >= 2 && (!Mem || !pad))) return CTRLSIM_EINVAL;
+  CHK(copy_rows(t.x_out, X, L.rows3, st));
+  CHK(copy_rows(t.u_out, U, L.rows3, st));
+  CHK(copy_rows(t.x1_out, X1, L.rows3, st));
+  CHK(copy_rows(t.mem_out, Mem, (size_t)B * L.M, st));
+  CHK(head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L, sums, grads, dX, st));
+  auto group = [&](int g) { return grads + group_base(d, m->has_fut, g); };
+  if (scope >= 1)
+    CHK(launch_ffn_block_grad(U, DM, dX, DM, Ld->lin1.w, Ld->lin1.b, Ld->lin2.w, Ld->lin2.b, Ld->n3.g, Ld->n3.b, (long)L.rows3, d.F, ws, L.f,
+                              group(0), dU, DM, st));
+  if (scope >= 2)
+    CHK(launch_attn_block_grad(X1, DM, Mem, DM, pad, dU, DM, Ld->cq.w, Ld->cq.b, Ld->cout.w, Ld->cout.b, Ld->n2.g, Ld->n2.b, B, Tq * A * 3, L.M,
+                               ws, L.a, group(1), dX1, DM, t.dMem, DM, st));
+  if (scope >= 3) {
+    CHK(copy_rows(t.x0_out, X0, L.rows3, st));
+    CHK(launch_self_attn_block_grad(X0, DM, dX1, DM, Ld->qkv.w, Ld->qkv.b, Ld->out.w, Ld->out.b, Ld->n1.g, Ld->n1.b, B, Tq, A,
+                                    d.variant == 4 ? 1 : 0, ws, L.s, group(2), t.dX0, DM, st));
+  }
+  return CTRLSIM_OK;
 }
 
 // The same sums and counts from logits in memory — compute_loss(data, preds) on the tensors of ctrlsim_forward_all (token-row order

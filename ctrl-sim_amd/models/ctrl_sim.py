@@ -8,14 +8,14 @@ the C ABI; `forward` on reference-layout tensors is the reference's return contr
 teacher-forced), or — with `token_index` — the two-pass logits of one timestep, the slice AutoregressivePolicy reads.
 `compute_loss` / `validation_step` (models/ctrl_sim.py:48-189,217-228) score logged windows: ctrlsim_forward_loss, no logits tensor.
 `training_step` / `configure_optimizers` / `optimizer_step` (models/ctrl_sim.py:190-214,242-282) train the three MLP heads over a frozen
-trunk: ctrlsim_forward_loss_grad gives the loss and the head gradients (csrc/head_grad.hip), torch's AdamW steps the fp32 masters,
-`HipModel.update` puts them back into the packed buffer.  `set_trainable("heads+ffn")` adds the last decoder layer's feed-forward block
-(linear1, linear2, norm3): ctrlsim_forward_loss_grad_ffn (csrc/ffn_grad.hip) differentiates it too and returns `dU`, the gradient at
-that block's input; `set_trainable("heads+ffn+cross")` adds that layer's cross-attention sublayer (multihead_attn, norm2):
-ctrlsim_forward_loss_grad_cross (csrc/attn_grad.hip) starts from `dU` and returns `dX1` and `dMem`, the gradients at the layer's norm1
-output and at the scene encoder's output; `set_trainable("heads+last_layer")` adds its self-attention sublayer (self_attn, norm1), so
-that the whole last decoder layer trains: ctrlsim_forward_loss_grad_layer (csrc/self_attn_grad.hip) starts from `dX1` and returns `dX0`,
-the gradient at the layer's input rows.  The backward through the earlier decoder layers, the encoder and the embeddings is not built."""
+trunk: ctrlsim_forward_loss_grads gives the loss and, at scope 0, the head gradients (csrc/head_grad.hip), torch's AdamW steps the fp32
+masters, `HipModel.update` puts them back into the packed buffer.  `set_trainable("heads+ffn")` adds the last decoder layer's feed-forward
+block (linear1, linear2, norm3): scope 1 (csrc/ffn_grad.hip) differentiates it too and returns `dU`, the gradient at that block's input;
+`set_trainable("heads+ffn+cross")` adds that layer's cross-attention sublayer (multihead_attn, norm2): scope 2 (csrc/attn_grad.hip)
+starts from `dU` and returns `dX1` and `dMem`, the gradients at the layer's norm1 output and at the scene encoder's output;
+`set_trainable("heads+last_layer")` adds its self-attention sublayer (self_attn, norm1), so that the whole last decoder layer trains:
+scope 3 (csrc/self_attn_grad.hip) starts from `dX1` and returns `dX0`, the gradient at the layer's input rows.  The backward through the
+earlier decoder layers, the encoder and the embeddings is not built."""
 from __future__ import annotations
 
 import numpy as np
@@ -158,19 +158,9 @@ class CtRLSim:
         import ctypes as C
         import torch
         from .. import _lib
-        from ..engine import ctx_from_reference_layout
         d, dev = self.dims, self.device
-        arrs = self._arrays(data)
-        B = arrs["agent_states"].shape[0]
-        ag = data["agent"]
-        mv = ag.get("moving_agent_mask") if isinstance(ag, dict) else getattr(ag, "moving_agent_mask", None)
-        moving = None
-        if mv is not None:
-            mv = np.asarray(mv.cpu() if hasattr(mv, "cpu") else mv)
-            moving = torch.from_numpy(np.ascontiguousarray(mv != 0).astype(np.uint8)).to(dev)
         lib, st = _lib.lib(), _lib.stream_ptr()
-        cb = ctx_from_reference_layout(d, arrs, d.T, dev)
-        cb.slot_gid.copy_(torch.arange(d.A, dtype=torch.int32, device=dev).expand(B, d.A))
+        cb, moving, B = self._ctx_of(data)
         if preds is None:
             return self.loss_sums_ctx(cb, moving, B, fused=fused, per_ctx=per_ctx, row_nll=row_nll)
         sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
@@ -220,36 +210,58 @@ class CtRLSim:
                    "loss_rtg_road": "loss_rtg_road", "loss_state": "loss_state"}
 
     def head_grad_layout(self):
-        """[(state-dict name, offset in floats, shape)] of the flat gradient buffer, and its length (ctrlsim_head_grad_layout)."""
-        import ctypes as C
-        from .. import _lib
-        from ..engine import _dims_struct
-        lib = _lib.lib()
-        has_fut = int("decoder.predict_future_states.mlp.0.weight" in self.weights)
-        cd = _dims_struct(self.dims)
-        n = lib.ctrlsim_head_grad_layout(C.byref(cd), has_fut, 0, None, None)
-        names, offs = (C.c_char_p * n)(), (C.c_int64 * (n + 1))()
-        if n < 0 or lib.ctrlsim_head_grad_layout(C.byref(cd), has_fut, n + 1, names, offs) != n:
-            raise RuntimeError("head gradient layout query failed")
-        out = [(names[i].decode(), int(offs[i]), tuple(np.asarray(self.weights[names[i].decode()]).shape)) for i in range(n)]
-        return out, int(offs[n])
+        """[(state-dict name, offset in floats, shape)] of the flat gradient buffer, and its length (ctrlsim_train_grad_layout, scope 0)."""
+        return self.train_grad_layout("heads")
+
+    def _parameters(self, scope):
+        """state-dict name -> torch.nn.Parameter over the fp32 master values of a scope's tensors, in layout order (each created once, in
+        one name-keyed cache; the optimiser's state hangs on these objects)."""
+        import torch
+        cache = self.__dict__.setdefault("_params", {})
+        make = lambda k: torch.nn.Parameter(torch.from_numpy(np.array(self.weights[k], np.float32)).to(self.device))
+        return {k: cache[k] if k in cache else cache.setdefault(k, make(k)) for k, _, _ in self.train_grad_layout(scope)[0]}
 
     def head_parameters(self):
         """state-dict name -> torch.nn.Parameter over the fp32 master values of the heads this model has (created once; the
         optimiser's state hangs on these objects)."""
-        import torch
-        if getattr(self, "_head_params", None) is None:
-            self._head_params = {k: torch.nn.Parameter(torch.from_numpy(np.array(self.weights[k], np.float32)).to(self.device))
-                                 for k, _, _ in self.head_grad_layout()[0]}
-        return self._head_params
+        return self._parameters("heads")
 
     def head_grad_workspace_bytes(self, B):
+        return self.train_grad_workspace_bytes(B, "heads")
+
+    # the optional outputs of ctrlsim_forward_loss_grads in the order the result tuples list them: name -> the first scope that has it
+    _TAPS = {"dX": 0, "dU": 1, "x_out": 0, "u_out": 1, "dX1": 2, "dMem": 2, "x1_out": 2, "mem_out": 2, "dX0": 3, "x0_out": 3}
+
+    def _forward_loss_grads(self, cb, moving, B, scope, want=(), fused=True, workspace=None, X=None):
+        """The one call behind every loss_and_*_grads: forward + loss + the gradients of `scope` with the taps named in `want` ->
+        (sums, {state-dict name: gradient tensor} — views of one flat buffer in train_grad_layout(scope) order —, {tap name: tensor}).
+        X given (scope "heads" only): no forward, ctrlsim_heads_loss_grad on those decoder output rows."""
         import ctypes as C
+        import torch
         from .. import _lib
-        n = _lib.lib().ctrlsim_head_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T)
-        if n < 0:
-            raise RuntimeError(f"head gradient workspace query failed: {n}")
-        return int(n)
+        d, dev = self.dims, self.device
+        lib, st = _lib.lib(), _lib.stream_ptr()
+        layout, total = self.train_grad_layout(scope)
+        sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
+        grads = torch.empty(total, device=dev)
+        rows3, rowsm = B * d.T * d.A * 3, B * ((d.P + d.A + 3) & ~3)
+        taps = {k: torch.empty(rowsm if k in ("dMem", "mem_out") else rows3, d.D, device=dev) for k in self._TAPS if k in want}
+        cfg = self.loss_cfg(fused)
+        coef = float(self.cfg.model.get("loss_action_coef", 1.0))
+        n = self.train_grad_workspace_bytes(B, scope)
+        ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= n
+        head = (self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef)
+        if X is None:
+            ct = _lib.TrainTaps(**{k: t.data_ptr() for k, t in taps.items()})
+            _lib.check(lib.ctrlsim_forward_loss_grads(*head, self.SCOPES.index(scope), ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(),
+                                                      C.byref(ct), st), "forward_loss_grads")
+        else:
+            assert X.dtype == torch.float32 and tuple(X.shape) == (rows3, d.D)
+            _lib.check(lib.ctrlsim_heads_loss_grad(*head, _lib.ptr(X), ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(),
+                                                   _lib.ptr(taps.get("dX")), st), "heads_loss_grad")
+        named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
+        return sums, named, taps            # enqueued on the current stream; reading the tensors waits for it
 
     def loss_and_head_grads_ctx(self, cb, moving, B, fused=True, dX=False, x_out=False, X=None, workspace=None):
         """One teacher-forced forward + loss + head gradients over the first B contexts of `cb` (engine.CtxBuffers on the device:
@@ -257,33 +269,9 @@ class CtRLSim:
         {state-dict name: gradient tensor} — views of one flat buffer —, dX [B*T*A*3,256] or None, x_out likewise).  X given (decoder
         output rows, plain layout): no forward, loss and gradients from those rows (ctrlsim_heads_loss_grad).  workspace: a uint8
         device tensor of at least head_grad_workspace_bytes(B) to use instead of a fresh one."""
-        import ctypes as C
-        import torch
-        from .. import _lib
-        d, dev = self.dims, self.device
-        lib, st = _lib.lib(), _lib.stream_ptr()
-        layout, total = self.head_grad_layout()
-        sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
-        grads = torch.empty(total, device=dev)
-        rows3 = B * d.T * d.A * 3
-        dx = torch.empty(rows3, d.D, device=dev) if dX else None
-        xo = torch.empty(rows3, d.D, device=dev) if x_out and X is None else None
-        cfg = self.loss_cfg(fused)
-        coef = float(self.cfg.model.get("loss_action_coef", 1.0))
-        n = self.head_grad_workspace_bytes(B)
-        ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= n
-        if X is None:
-            _lib.check(lib.ctrlsim_forward_loss_grad(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
-                                                     ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo), st),
-                       "forward_loss_grad")
-        else:
-            assert X.dtype == torch.float32 and tuple(X.shape) == (rows3, d.D)
-            _lib.check(lib.ctrlsim_heads_loss_grad(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
-                                                   _lib.ptr(X), ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), st),
-                       "heads_loss_grad")
-        named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
-        return sums, named, dx, xo          # enqueued on the current stream; reading the tensors waits for it
+        want = [k for k, on in (("dX", dX), ("x_out", x_out and X is None)) if on]
+        sums, named, taps = self._forward_loss_grads(cb, moving, B, "heads", want, fused, workspace, X)
+        return sums, named, taps.get("dX"), taps.get("x_out")
 
     def _ctx_of(self, data):
         import torch
@@ -345,22 +333,7 @@ class CtRLSim:
         """state-dict name -> torch.nn.Parameter of the selected scope, in layout order: head_parameters() (the same objects), then under
         "heads+ffn" the six tensors of the last decoder layer's feed-forward block, under "heads+ffn+cross" the six of its cross-attention
         sublayer too, under "heads+last_layer" the six of its self-attention sublayer as well (each created once)."""
-        import torch
-        params = dict(self.head_parameters())
-        make = lambda names: {k: torch.nn.Parameter(torch.from_numpy(np.array(self.weights[k], np.float32)).to(self.device)) for k in names}
-        if self._scope != "heads":
-            if getattr(self, "_ffn_params", None) is None:
-                self._ffn_params = make([k for k, _, _ in self.train_grad_layout("heads+ffn")[0] if k not in params])
-            params.update(self._ffn_params)
-        if self._scope in self.SCOPES[2:]:
-            if getattr(self, "_cross_params", None) is None:
-                self._cross_params = make([k for k, _, _ in self.train_grad_layout("heads+ffn+cross")[0] if k not in params])
-            params.update(self._cross_params)
-        if self._scope == "heads+last_layer":
-            if getattr(self, "_self_params", None) is None:
-                self._self_params = make([k for k, _, _ in self.train_grad_layout("heads+last_layer")[0] if k not in params])
-            params.update(self._self_params)
-        return params
+        return self._parameters(self._scope)
 
     def train_grad_workspace_bytes(self, B, scope="heads+ffn"):
         import ctypes as C
@@ -372,66 +345,29 @@ class CtRLSim:
 
     def loss_and_train_grads_ctx(self, cb, moving, B, dX=False, dU=False, x_out=False, u_out=False, workspace=None, dX1=False, dMem=False,
                                  x1_out=False, mem_out=False, scope=None, dX0=False, x0_out=False):
-        """loss_and_head_grads_ctx for the scope "heads+ffn" (ctrlsim_forward_loss_grad_ffn): one teacher-forced forward + loss + the
+        """loss_and_head_grads_ctx for the scope "heads+ffn" (ctrlsim_forward_loss_grads, scope 1): one teacher-forced forward + loss + the
         gradients of the heads and of the last decoder layer's feed-forward block -> (sums, {state-dict name: gradient tensor} in
         train_grad_layout("heads+ffn") order, dX, dU, x_out, u_out), each of the last four [B*T*A*3, 256] or None: the gradient at the
         decoder output, the gradient at the block's input U, the decoder output and U itself.  The gradients are those of the function
         this call evaluated (the block applied to U as stored).
-        scope (default: the trainable scope, "heads+ffn" under "heads"): under "heads+ffn+cross" (ctrlsim_forward_loss_grad_cross) the
+        scope (default: the trainable scope, "heads+ffn" under "heads"): under "heads+ffn+cross" (scope 2) the
         gradients continue with the six cross-attention tensors and the tuple with (dX1, dMem, x1_out, mem_out): the gradient at the
         layer's norm1 output [B*T*A*3, 256], this layer's share of the gradient at the scene encoder's output [B*M, 256], M = (P + A + 3)
         & ~3, and the two inputs themselves; everything the narrower scope returns is bit for bit what it returns.  Under
-        "heads+last_layer" (ctrlsim_forward_loss_grad_layer) the gradients continue with the six self-attention tensors and the tuple
+        "heads+last_layer" (scope 3) the gradients continue with the six self-attention tensors and the tuple
         with (dX0, x0_out): the gradient at the layer's input rows [B*T*A*3, 256] and those rows themselves."""
-        import ctypes as C
-        import torch
-        from .. import _lib
-        d, dev = self.dims, self.device
-        lib, st = _lib.lib(), _lib.stream_ptr()
         if scope is None:
             scope = self._scope if self._scope != "heads" else "heads+ffn"
         if scope not in self.SCOPES[1:]:
             raise ValueError(f"loss_and_train_grads scope {scope!r}: one of {self.SCOPES[1:]}")
-        layer = scope == "heads+last_layer"
-        cross = layer or scope == "heads+ffn+cross"
-        if not cross and (dX1 or dMem or x1_out or mem_out):
+        sc = self.SCOPES.index(scope)
+        asked = dict(dX=dX, dU=dU, x_out=x_out, u_out=u_out, dX1=dX1, dMem=dMem, x1_out=x1_out, mem_out=mem_out, dX0=dX0, x0_out=x0_out)
+        if sc < 2 and (dX1 or dMem or x1_out or mem_out):
             raise ValueError("dX1, dMem, x1_out and mem_out exist from the scope \"heads+ffn+cross\" on only")
-        if not layer and (dX0 or x0_out):
+        if sc < 3 and (dX0 or x0_out):
             raise ValueError("dX0 and x0_out exist under the scope \"heads+last_layer\" only")
-        layout, total = self.train_grad_layout(scope)
-        sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
-        grads = torch.empty(total, device=dev)
-        rows3 = B * d.T * d.A * 3
-        buf = lambda want: torch.empty(rows3, d.D, device=dev) if want else None
-        dx, du, xo, uo = buf(dX), buf(dU), buf(x_out), buf(u_out)
-        cfg = self.loss_cfg(True)
-        coef = float(self.cfg.model.get("loss_action_coef", 1.0))
-        n = self.train_grad_workspace_bytes(B, scope)
-        ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= n
-        if cross:
-            rowsm = B * ((d.P + d.A + 3) & ~3)
-            dx1, x1o = buf(dX1), buf(x1_out)
-            dm, mo = (torch.empty(rowsm, d.D, device=dev) if want else None for want in (dMem, mem_out))
-            if layer:
-                dx0, x0o = buf(dX0), buf(x0_out)
-                _lib.check(lib.ctrlsim_forward_loss_grad_layer(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
-                                                               ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo),
-                                                               _lib.ptr(du), _lib.ptr(uo), _lib.ptr(dx1), _lib.ptr(dm), _lib.ptr(x1o), _lib.ptr(mo),
-                                                               _lib.ptr(dx0), _lib.ptr(x0o), st), "forward_loss_grad_layer")
-                named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
-                return sums, named, dx, du, xo, uo, dx1, dm, x1o, mo, dx0, x0o
-            _lib.check(lib.ctrlsim_forward_loss_grad_cross(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
-                                                           ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo),
-                                                           _lib.ptr(du), _lib.ptr(uo), _lib.ptr(dx1), _lib.ptr(dm), _lib.ptr(x1o), _lib.ptr(mo),
-                                                           st), "forward_loss_grad_cross")
-            named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
-            return sums, named, dx, du, xo, uo, dx1, dm, x1o, mo
-        _lib.check(lib.ctrlsim_forward_loss_grad_ffn(self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef,
-                                                     ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), _lib.ptr(dx), _lib.ptr(xo),
-                                                     _lib.ptr(du), _lib.ptr(uo), st), "forward_loss_grad_ffn")
-        named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
-        return sums, named, dx, du, xo, uo   # enqueued on the current stream; reading the tensors waits for it
+        sums, named, taps = self._forward_loss_grads(cb, moving, B, scope, [k for k, on in asked.items() if on], workspace=workspace)
+        return (sums, named) + tuple(taps.get(k) for k, first in self._TAPS.items() if first <= sc)
 
     def loss_and_train_grads(self, data, dX=False, dU=False, x_out=False, u_out=False, **more):
         """loss_and_train_grads_ctx over reference-layout windows `data` (more: dX1, dMem, x1_out, mem_out, dX0, x0_out, scope)."""
@@ -448,18 +384,11 @@ class CtRLSim:
     def training_step(self, data, batch_idx=0):
         """The reference's training_step for the heads: final_loss of the batch; `.grad` of head_parameters() is filled with its gradient
         (the trunk is frozen: it has no parameters here), `self.logged` holds what the reference logs per step, under its names."""
-        if self._scope != "heads":
-            sums, grads = self.loss_and_train_grads(data)[:2]
-        else:
-            sums, grads, _, _ = self.loss_and_head_grads(data)
-        return self._train_backward(sums, grads)
+        return self.training_step_ctx(*self._ctx_of(data))
 
     def training_step_ctx(self, cb, moving, B):
         """training_step on contexts that are already on the device (windows.build_windows)."""
-        if self._scope != "heads":
-            sums, grads = self.loss_and_train_grads_ctx(cb, moving, B)[:2]
-        else:
-            sums, grads, _, _ = self.loss_and_head_grads_ctx(cb, moving, B)
+        sums, grads, _ = self._forward_loss_grads(cb, moving, B, self._scope)
         return self._train_backward(sums, grads)
 
     @staticmethod

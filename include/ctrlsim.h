@@ -287,24 +287,18 @@ int ctrlsim_forward_loss(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ct
  * decoder output [B*Tq*A*3, 256] in the plain layout (token type k of (b, tt, a) is row ((b*Tq + tt)*A + a)*3 + k).
  * grads: ONE flat float32 buffer holding, per head in the parameter-table order (action, returns, future states; only the heads
  * the model has), mlp.0.weight [256,256], mlp.0.bias, mlp.1.weight, mlp.1.bias (the LayerNorm), mlp.3.weight [n,256], mlp.3.bias.
- * The layout query fills names[i] (state-dict names, static storage) and offsets[i] (in floats) for cap >= count entries and, if cap > count,
- * offsets[count] = the total length; it returns the count and needs no device.  dX (nullable) [B*Tq*A*3, 256]: the gradient at the decoder
+ * This is scope 0 of the layout and workspace queries below.  dX (nullable) [B*Tq*A*3, 256]: the gradient at the decoder
  * output, every row written, zeros on rows no head reads.  sums / per_ctx as for ctrlsim_forward_loss; the per-row scales divide by the
  * counts found in `sums` after this call's own reduction, on the device: hand in zeroed sums for the gradient of this batch's loss.
  * A term whose count is 0 has a NaN loss and NaN gradients, as autograd gives the reference.  Arithmetic: f32-input MFMA from the
  * fp32 master weights under either operand split of the forward; sums across workgroups go through partial slabs and a second,
- * fixed-order stage, no atomics: identical bits from run to run.  Workspace: the head-gradient workspace query (the forward-loss
- * workspace, then Z, H, dH [B*Tq*A, 256], a logits chunk of <= 8192 rows, and the partial slabs).
- * The second entry runs the teacher-forced forward first, on its own X (x_out, nullable, receives a copy); its sums are bit-identical
- * to ctrlsim_forward_loss on the same inputs. */
-int ctrlsim_head_grad_layout(const ctrlsim_dims* dims, int has_future_states, int cap, const char** names, int64_t* offsets);
-int64_t ctrlsim_head_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq);
+ * fixed-order stage, no atomics: identical bits from run to run.  Workspace: ctrlsim_train_grads_workspace_bytes(dims, B, Tq, 0) (the
+ * forward-loss workspace, then Z, H, dH [B*Tq*A, 256], a logits chunk of <= 8192 rows, and the partial slabs).
+ * ctrlsim_heads_loss_grad takes X from the caller and runs no forward; ctrlsim_forward_loss_grads (below) runs the teacher-forced
+ * forward first, on its own X. */
 int ctrlsim_heads_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
                             const ctrlsim_loss_cfg* cfg, float loss_action_coef, const float* X, void* workspace, double* sums,
                             double* per_ctx, float* grads, float* dX, hipStream_t stream);
-int ctrlsim_forward_loss_grad(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
-                              const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
-                              float* grads, float* dX, float* x_out, hipStream_t stream);
 /* ---- training, second stage (a): the feed-forward block's backward (csrc/ffn_grad.hip) -------------------------------------------
  * The op.  Forward being differentiated, per row (width 256, hidden width F, LayerNorm eps 1e-5, relu'(0) = 0):
  *   Hp = U W1^T + b1,  H = relu(Hp),  S = U + H W2^T + b2,  Y = LayerNorm(S; gamma, beta)
@@ -322,22 +316,6 @@ int ctrlsim_ffn_block_grad_chunk_rows(int rows, int F);
 int ctrlsim_ffn_block_grad(const float* U, int ldu, const float* dY, int lddy, const float* W1, const float* b1, const float* W2,
                            const float* b2, const float* gamma, const float* beta, int rows, int F, void* workspace, float* grads,
                            float* dU, int lddu, hipStream_t stream);
-/* Heads + the LAST decoder layer's feed-forward block.  ctrlsim_forward_loss_grad with two more outputs: grads continues behind the
- * head tensors with the six tensors decoder.transformer_decoder.layers.{ND-1}.linear1.weight, .linear1.bias, .linear2.weight,
- * .linear2.bias, .norm3.weight, .norm3.bias (ctrlsim_train_grad_layout with scope 1; scope 0 = exactly ctrlsim_head_grad_layout), and
- * dU (nullable) [B*Tq*A*3, 256] is the gradient at that block's input — the layer's norm2 output — where a cross-attention backward
- * will start.  u_out (nullable) receives those input rows U, x_out the decoder output.  The forward of this entry is the forward of
- * ctrlsim_forward_loss_grad except in the last decoder layer, whose cross-attention out-projection + norm2 and feed-forward block run
- * as two kernels with U copied to the workspace between them (the fused kernel never writes U).  The gradients are those of the
- * function THIS call evaluated: the block applied to U as stored, the heads applied to the decoder output as stored.  Rows of dX no
- * head reads are zero; their dU is what the block's Jacobian makes of a zero row.  A term with count 0 gives NaN gradients.
- * Accepted for the models ctrlsim_forward_loss_grad accepts.  Workspace: ctrlsim_train_grads_workspace_bytes(dims, B, Tq, 1) (the
- * head-gradient workspace, then U, a dX, the H / S / dS chunks, the slabs and partials). */
-int ctrlsim_train_grad_layout(const ctrlsim_dims* dims, int has_future_states, int scope, int cap, const char** names, int64_t* offsets);
-int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq, int scope);
-int ctrlsim_forward_loss_grad_ffn(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
-                                  const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
-                                  float* grads, float* dX, float* x_out, float* dU, float* u_out, hipStream_t stream);
 /* ---- training, second stage (b): the attention sublayer's backward (csrc/attn_grad.hip) -------------------------------------------
  * The op.  Forward being differentiated, per context of Lq query rows and Lk memory rows (width 256, 8 heads x 32, LayerNorm eps 1e-5):
  *   Q = X Wq^T + bq,  K = Mem Wk^T + bk,  V = Mem Wv^T + bv            (in_proj_weight [768,256] = Wq; Wk; Wv, in_proj_bias [768])
@@ -360,19 +338,6 @@ int ctrlsim_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, 
                             const float* in_proj_weight, const float* in_proj_bias, const float* out_proj_weight,
                             const float* out_proj_bias, const float* gamma, const float* beta, int B, int Lq, int Lk, void* workspace,
                             float* grads, float* dX, int lddx, float* dMem, int lddm, hipStream_t stream);
-/* Heads + the LAST decoder layer's feed-forward block + its cross-attention sublayer.  ctrlsim_forward_loss_grad_ffn with four more
- * outputs: grads continues behind the feed-forward tensors with decoder.transformer_decoder.layers.{ND-1}.multihead_attn.in_proj_weight,
- * .in_proj_bias, .out_proj.weight, .out_proj.bias, .norm2.weight, .norm2.bias (ctrlsim_train_grad_layout with scope 2; scopes 0 and 1
- * answer as before).  dX1 (nullable) [B*Tq*A*3, 256]: the gradient at the layer's norm1 output, where the self-attention backward will
- * start; dMem (nullable) [B*M, 256], M = (P + A + 3) & ~3 scene rows per context: this layer's contribution to the gradient at the
- * scene encoder's output.  x1_out / mem_out (nullable) receive the norm1 output rows and the encoder output the backward read.  The
- * forward is the _ffn entry's with one more row copy; loss sums, head and feed-forward gradients, dX and dU are bit-identical to that
- * entry's.  The gradients are those of the sublayer applied to X1 and Mem as stored.  Workspace:
- * ctrlsim_train_grads_workspace_bytes(dims, B, Tq, 2). */
-int ctrlsim_forward_loss_grad_cross(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
-                                    const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
-                                    float* grads, float* dX, float* x_out, float* dU, float* u_out, float* dX1, float* dMem,
-                                    float* x1_out, float* mem_out, hipStream_t stream);
 /* ---- training (c): the causal self-attention sublayer's backward (csrc/self_attn_grad.hip) ----------------------------------------
  * The op.  Forward being differentiated, per context of L = 3 T A token rows, token i = (t, a, k) = (i / 3A, (i / 3) % A, i % 3):
  *   Q | K | V = X Win^T + bin                                           (in_proj_weight [768,256], in_proj_bias [768])
@@ -394,17 +359,42 @@ int ctrlsim_self_attn_block_grad(const float* X, int ldx, const float* dY, int l
                                  const float* in_proj_bias, const float* out_proj_weight, const float* out_proj_bias, const float* gamma,
                                  const float* beta, int B, int T, int A, int mask_mode, void* workspace, float* grads, float* dX, int lddx,
                                  hipStream_t stream);
-/* Heads + the whole LAST decoder layer.  ctrlsim_forward_loss_grad_cross with two more outputs: grads continues behind the cross-attention
- * tensors with decoder.transformer_decoder.layers.{ND-1}.self_attn.in_proj_weight, .in_proj_bias, .out_proj.weight, .out_proj.bias,
- * .norm1.weight, .norm1.bias (ctrlsim_train_grad_layout with scope 3; scopes 0 to 2 answer as before).  dX0 (nullable) [B*Tq*A*3, 256]:
- * the gradient at the layer's input rows, where the next layer's backward will start; x0_out (nullable) receives those rows (for ND == 1
- * the assembled tokens).  The forward is the _cross entry's with one more row copy; loss sums, all narrower-scope gradients, dX, dU, dX1
- * and dMem are bit-identical to that entry's.  mask_mode follows dims.variant (0: mode 0, 4: mode 1); the baseline token layouts return
- * CTRLSIM_EINVAL.  Workspace: ctrlsim_train_grads_workspace_bytes(dims, B, Tq, 3). */
-int ctrlsim_forward_loss_grad_layer(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
-                                    const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
-                                    float* grads, float* dX, float* x_out, float* dU, float* u_out, float* dX1, float* dMem,
-                                    float* x1_out, float* mem_out, float* dX0, float* x0_out, hipStream_t stream);
+/* ---- training: forward, loss, then the gradients of the first `scope` groups behind the heads ---------------------------------------
+ * ctrlsim_forward_loss_grads runs the teacher-forced forward on its own X, the loss (sums bit-identical to ctrlsim_forward_loss on the
+ * same inputs) and the head gradients as described for ctrlsim_heads_loss_grad, then the three ops above on the LAST decoder layer
+ * from its output back, as far as `scope` says; each op's dY is the dX of the op behind it.  grads: ONE flat float32 buffer, the head
+ * tensors and then, per scope from 1 on, six tensors of decoder.transformer_decoder.layers.{ND-1}:
+ *   scope | group added to grads             | taps added       | forward, against the scope before      | models accepted   | workspace
+ *   0     | the heads' tensors               | dX, x_out        | ctrlsim_forward_loss's                 | that entry's      | head-gradient carve
+ *   1     | .linear1, .linear2 (weight,      | dU, u_out        | out-projection + norm2 and the feed-   | + ND >= 1, F >= 1 | + U, a dX, the
+ *         | bias), .norm3                    |                  | forward block as two kernels, U copied |                   | feed-forward op's
+ *   2     | .multihead_attn in_proj_weight,  | dX1, dMem,       | + one row copy: X1, the norm1 output   | as scope 1        | + X1, a dU, the
+ *         | in_proj_bias, out_proj, .norm2   | x1_out, mem_out  |                                        |                   | attention op's
+ *   3     | .self_attn (the same), .norm1    | dX0, x0_out      | + one row copy: X0, before the layer's | + dims.variant 0  | + X0, a dX1, the self-
+ *         |                                  |                  | first kernel                           | or 4 (mask_mode)  | attention op's
+ * The gradient taps, [B*Tq*A*3, 256] each: dX at the decoder output; dU at the feed-forward block's input, the layer's norm2 output; dX1
+ * at the layer's norm1 output; dX0 at the layer's input rows (for ND == 1 the assembled tokens).  dMem [B*M, 256], M = (P + A + 3) & ~3
+ * scene rows per context: this layer's contribution to the gradient at the scene encoder's output.  x_out, u_out, x1_out, x0_out and
+ * mem_out receive the rows those gradients belong to, as the backward read them.  A non-null tap of a wider scope than the call's, a scope
+ * outside 0..3 or a model the scope does not accept: CTRLSIM_EINVAL, nothing launched.  taps == NULL: no tap.  Whatever a narrower scope
+ * returns, a wider one returns bit for bit.  The gradients are those of the function THIS call evaluated: each op applied to its input
+ * rows as stored.  Rows of dX no head reads are zero; their dU is what the block's Jacobian makes of a zero row.  A term with count 0
+ * gives NaN gradients.
+ * The layout query fills names[i] (state-dict names, static storage: valid until the next layout query) and offsets[i] (in floats) for
+ * cap >= count entries and, if cap > count, offsets[count] = the total length; it returns the count and needs no device.  Workspace:
+ * ctrlsim_train_grads_workspace_bytes(dims, B, Tq, scope); the dX / dU / dX1 of its own is the next op's dY where the caller takes no
+ * such tap.  Scope 3 also refuses B*Tq*A*3 * 768 >= 2^31. */
+typedef struct ctrlsim_train_taps {          /* every member nullable */
+  float *dX, *x_out;                         /* scope >= 0 */
+  float *dU, *u_out;                         /* scope >= 1 */
+  float *dX1, *dMem, *x1_out, *mem_out;      /* scope >= 2 */
+  float *dX0, *x0_out;                       /* scope 3    */
+} ctrlsim_train_taps;
+int ctrlsim_train_grad_layout(const ctrlsim_dims* dims, int has_future_states, int scope, int cap, const char** names, int64_t* offsets);
+int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq, int scope);
+int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
+                               double* per_ctx, float* grads, const ctrlsim_train_taps* taps /* nullable */, hipStream_t stream);
 /* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
  * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
  * scratch: ctrlsim_loss_scratch_bytes. */

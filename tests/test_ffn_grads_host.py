@@ -1,6 +1,6 @@
 """CPU tests of the feed-forward-block gradient path's host side and of its checker:
   * tests/ffn_grad_ref.py (float64 autograd restatement of the block) against central finite differences;
-  * ctrlsim_train_grad_layout against ctrlsim_head_grad_layout (scope 0) and the parameter table (scope 1);
+  * ctrlsim_train_grad_layout against CtRLSim.head_grad_layout (scope 0) and the parameter table (scope 1);
   * pack.ffn_images against pack.pack, bit for bit;
   * the AdamW parameter groups with the new names;
   * the checker's handling of ReLU kinks (ffn_grad_ref.resolve_kinks)."""
@@ -53,7 +53,7 @@ def test_restatement_matches_central_differences():
 
 @pytest.mark.parametrize("case", [0, 4, 7])
 def test_training_layout_extends_the_head_layout(case):
-    """ctrlsim_train_grad_layout (needs the library, not a device): scope 0 is ctrlsim_head_grad_layout name by name and offset by
+    """ctrlsim_train_grad_layout (needs the library, not a device): scope 0 is CtRLSim.head_grad_layout name by name and offset by
     offset; scope 1 appends the last decoder layer's six tensors, back to back, with the parameter table's shapes."""
     cfg = loss_ref.case_cfg(case)
     d = spec.Dims(cfg)

@@ -1,4 +1,4 @@
-"""GPU tests of the attention sublayer's backward (csrc/attn_grad.hip: ctrlsim_attn_block_grad) and of ctrlsim_forward_loss_grad_cross
+"""GPU tests of the attention sublayer's backward (csrc/attn_grad.hip: ctrlsim_attn_block_grad) and of ctrlsim_forward_loss_grads at scope 2
 (heads + the last decoder layer's feed-forward block + its cross-attention sublayer), under both operand splits of the forward where a
 forward is involved.
 
@@ -223,8 +223,8 @@ def _key_pad(cfg, d, inp):
 @pytest.mark.parametrize("split", SPLITS)
 @pytest.mark.parametrize("case", MODEL_CASES)
 def test_forward_loss_grad_cross_through_the_model(case, split):
-    """ctrlsim_forward_loss_grad_cross on fixture cases 0, 1 (tiny) and 7 (full dims, B = 2): loss sums, head and feed-forward gradients,
-    dX and dU bit-identical to ctrlsim_forward_loss_grad_ffn; the six new tensors, dX1 and dMem against the float64 sublayer applied to
+    """ctrlsim_forward_loss_grads at scope 2 on fixture cases 0, 1 (tiny) and 7 (full dims, B = 2): loss sums, head and feed-forward gradients,
+    dX and dU bit-identical to scope 1; the six new tensors, dX1 and dMem against the float64 sublayer applied to
     the returned X1 / Mem with the returned dU as dY."""
     lib = _lib.lib()
     cfg, d, w, inp = _model_case(case)

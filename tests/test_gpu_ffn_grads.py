@@ -1,4 +1,4 @@
-"""GPU tests of the feed-forward block's backward (csrc/ffn_grad.hip: ctrlsim_ffn_block_grad), of ctrlsim_forward_loss_grad_ffn (heads +
+"""GPU tests of the feed-forward block's backward (csrc/ffn_grad.hip: ctrlsim_ffn_block_grad), of ctrlsim_forward_loss_grads at scope 1 (heads +
 the last decoder layer's feed-forward block), of HipModel.update for the block's tensors and of the training loop in scope "heads+ffn",
 under both operand splits of the forward where a forward is involved.
 
@@ -233,7 +233,7 @@ def _model_case(case):
 @pytest.mark.parametrize("split", SPLITS)
 @pytest.mark.parametrize("case", MODEL_CASES)
 def test_forward_loss_grad_ffn_through_the_model(case, split):
-    """ctrlsim_forward_loss_grad_ffn on fixture cases 0, 1 (tiny) and 7 (full dims, B = 2): the loss against float64 heads on the
+    """ctrlsim_forward_loss_grads at scope 1 on fixture cases 0, 1 (tiny) and 7 (full dims, B = 2): the loss against float64 heads on the
     returned decoder output and against the reference's recorded loss; head gradients and dX against float64 autograd of the heads on
     that output; the block's six tensors and dU against the float64 block applied to the returned U with the returned dX as dY (the
     ReLU's side at float32-zero hidden elements as ffn_grad_ref.resolve_kinks reads it off the device's db1); the

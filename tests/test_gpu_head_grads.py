@@ -1,4 +1,4 @@
-"""GPU tests of the head gradients of the open-loop loss (csrc/head_grad.hip; ctrlsim_heads_loss_grad, ctrlsim_forward_loss_grad),
+"""GPU tests of the head gradients of the open-loop loss (csrc/head_grad.hip; ctrlsim_heads_loss_grad, ctrlsim_forward_loss_grads at scope 0),
 of HipModel.update and of the head training loop, under both operand splits of the forward.
 
 ACCURACY BOUND (profiles/head_grad_parity.md holds the measured ratios).  For every gradient tensor T, relative to max |T_f64|:
@@ -121,7 +121,7 @@ def _model_case(case):
 @pytest.mark.parametrize("split", SPLITS)
 @pytest.mark.parametrize("case", MODEL_CASES)
 def test_forward_loss_grad_through_the_model(case, split):
-    """ctrlsim_forward_loss_grad on the fixture cases: sums bit-equal to ctrlsim_forward_loss; gradients against float64 autograd of the
+    """ctrlsim_forward_loss_grads at scope 0 on the fixture cases: sums bit-equal to ctrlsim_forward_loss; gradients against float64 autograd of the
     heads applied to x_out; the reference's own recorded values on the fixture's sampled rows."""
     lib = _lib.lib()
     cfg, d, w, inp = _model_case(case)

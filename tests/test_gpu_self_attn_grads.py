@@ -1,5 +1,5 @@
 """GPU tests of the causal self-attention sublayer's backward (csrc/self_attn_grad.hip: ctrlsim_self_attn_block_grad) and of
-ctrlsim_forward_loss_grad_layer (heads + the whole last decoder layer), under both operand splits of the forward where a forward is
+ctrlsim_forward_loss_grads at scope 3 (heads + the whole last decoder layer), under both operand splits of the forward where a forward is
 involved.
 
 ACCURACY BOUND (profiles/self_attn_grad_parity.md holds every measured ratio).  The form of tests/test_gpu_attn_grads.py: for every
@@ -278,7 +278,7 @@ def _layer_call(model, cb, moving, B, **kw):
 @pytest.mark.parametrize("split", SPLITS)
 @pytest.mark.parametrize("case", MODEL_CASES)
 def test_forward_loss_grad_layer_through_the_model(case, split):
-    """ctrlsim_forward_loss_grad_layer on fixture cases 0, 1 (tiny) and 7 (full dims, B = 2): everything the scope "heads+ffn+cross"
+    """ctrlsim_forward_loss_grads at scope 3 on fixture cases 0, 1 (tiny) and 7 (full dims, B = 2): everything the scope "heads+ffn+cross"
     returns bit-identical; the six new tensors and dX0 against the float64 sublayer applied to the returned X0 with the returned dX1 as
     dY; the six tensors against the reference's recorded gradients (tests/golden/self_grads.npz: its trunk, its float32).  Measured
     (profiles/self_attn_grad_parity.md): ratios at most 5.79 (case 7, bf16x6); deviation from the recorded gradients at most 4.5e-5 of a
@@ -369,6 +369,36 @@ def test_scopes_before_this_one_answer_as_before():
     assert model.train_grad_workspace_bytes(2, "heads+last_layer") > model.train_grad_workspace_bytes(2, "heads+ffn+cross")
     with pytest.raises(ValueError):
         model.loss_and_train_grads_ctx(None, None, 1, dX0=True, scope="heads+ffn+cross")
+
+
+def test_the_entry_refuses_a_tap_of_a_wider_scope_and_needs_no_taps():
+    """The raw ctrlsim_forward_loss_grads call on case 0: scope 1 with taps.dX0 set, scope 4 and scope -1 return CTRLSIM_EINVAL and
+    launch nothing (zeroed sums, a NaN-poisoned grads buffer and the tap keep their bits); taps = NULL at scope 3 gives the sums and
+    gradients of the call with every tap, bit for bit."""
+    import ctypes as C
+    lib, st = _lib.lib(), _lib.stream_ptr()
+    cfg, d, w, inp = _model_case(0)
+    model = CtRLSim(cfg, w, device=DEV)
+    cb, moving, B = model._ctx_of(_data(inp))
+    lc = model.loss_cfg(True)
+    coef = float(cfg.model.get("loss_action_coef", 1.0))
+    ws = torch.empty(model.train_grad_workspace_bytes(B, "heads+last_layer"), dtype=torch.uint8, device=DEV)
+    sums = torch.zeros(5, 2, dtype=torch.float64, device=DEV)
+    grads = torch.full((model.train_grad_layout("heads+last_layer")[1],), float("nan"), device=DEV)
+    dX0 = torch.full((B * d.T * d.A * 3, 256), 7.0, device=DEV)
+
+    def call(scope, taps):
+        return lib.ctrlsim_forward_loss_grads(model.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(lc), coef, scope,
+                                              ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), taps, st)
+
+    assert call(1, C.byref(_lib.TrainTaps(dX0=dX0.data_ptr()))) == -22          # CTRLSIM_EINVAL
+    assert call(4, None) == -22 and call(-1, None) == -22
+    torch.cuda.synchronize()
+    assert not sums.any() and torch.isnan(grads).all() and (dX0 == 7.0).all()
+    assert call(3, None) == 0
+    r3 = _layer_call(model, cb, moving, B)
+    assert np.array_equal(_bits(sums), _bits(r3[0]))
+    assert np.array_equal(_bits(grads), _bits(torch.cat([g.reshape(-1) for g in r3[1].values()])))
 
 
 # ---- 3. HipModel.update

@@ -198,7 +198,7 @@ def test_param_groups_and_schedule_match_reference(fixture):
 
 @pytest.mark.parametrize("case", [0, 4, 7])
 def test_gradient_layout_follows_parameter_table(case):
-    """ctrlsim_head_grad_layout: the head tensors in weights.param_table order, back to back (needs the library, not a device)."""
+    """ctrlsim_train_grad_layout at scope 0: the head tensors in weights.param_table order, back to back (needs the library, not a device)."""
     cfg = loss_ref.case_cfg(case)
     d = spec.Dims(cfg)
     w = loss_ref.case_weights(case, d)
