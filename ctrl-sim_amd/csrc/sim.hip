@@ -177,7 +177,9 @@ extern "C" void ctrlsim_sim_timing(unsigned long long* out, int reset) {
 #define SIMT(k)
 #endif
 #define GRID 16               // broad-phase grid of the vehicle x road-edge tests (GRID x GRID cells, a 64-bit vehicle mask each)
-// shared by init and step: corners/AABBs into LDS, flags, history row
+// shared by init and step: corners/AABBs into LDS, flags, history row.  all_placed is a template argument, not a run-time one: the
+// step's instance is the code it was before the init row needed its own rule (and a run-time flag cost both kernels 8 bytes of scratch)
+template <bool all_placed = false>
 __device__ void collide_and_record(int s, int N, int E, const float* __restrict__ size, const float* __restrict__ edges,
                                    const unsigned char* __restrict__ exists, float* __restrict__ hist_states,
                                    unsigned char* __restrict__ coll, int t_row, int Tmax1, float (*corner)[8],
@@ -239,7 +241,9 @@ __device__ void collide_and_record(int s, int N, int E, const float* __restrict_
   __shared__ unsigned live_lo, live_hi;                        // existing vehicles (the ones the grid bins)
   for (int c = tid; c < GRID * GRID; c += blockDim.x) { cell_lo[c] = 0u; cell_hi[c] = 0u; }
   if (tid < 64) {                                              // wave 0: bounding box of the existing vehicles
-    const bool live = tid < N && exists[(size_t)s * N + tid];
+    // all_placed (init): nobody has been moved to the parking spot yet — a vehicle that does not exist stands at its start pose
+    // and meets road edges there like any other (Scenario::Step tests every object), so it is binned too
+    const bool live = tid < N && (all_placed || exists[(size_t)s * N + tid]);
     float m0 = live ? box[tid][0] : 3.402823466e+38f, m1 = live ? box[tid][1] : 3.402823466e+38f;
     float m2 = live ? box[tid][2] : -3.402823466e+38f, m3 = live ? box[tid][3] : -3.402823466e+38f;
 #pragma unroll
@@ -259,7 +263,7 @@ __device__ void collide_and_record(int s, int N, int E, const float* __restrict_
     const float ihx = (float)GRID / fmaxf(gbox[2] - gx0, 1e-3f), ihy = (float)GRID / fmaxf(gbox[3] - gy0, 1e-3f);
     auto cellx = [&](float x) { return min(GRID - 1, max(0, (int)floorf((x - gx0) * ihx))); };
     auto celly = [&](float y) { return min(GRID - 1, max(0, (int)floorf((y - gy0) * ihy))); };
-    if (tid < N && exists[(size_t)s * N + tid]) {
+    if (tid < N && (all_placed || exists[(size_t)s * N + tid])) {
       const int x0 = cellx(box[tid][0]), x1 = cellx(box[tid][2]), y0 = celly(box[tid][1]), y1 = celly(box[tid][3]);
       for (int y = y0; y <= y1; ++y)
         for (int x = x0; x <= x1; ++x) {
@@ -1078,8 +1082,8 @@ __global__ __launch_bounds__(256) void sim_init_kernel(int N, int E, const float
     }
     tail[2] = 1.f;                                       // m_newContacts
   }
-  collide_and_record(s, N, E, size, edges, exists, hist_states, coll, 0, Tmax1, corner, box, flag_veh, flag_edge, px, py,
-                     hd, sp);
+  collide_and_record<true>(s, N, E, size, edges, exists, hist_states, coll, 0, Tmax1, corner, box, flag_veh, flag_edge, px, py,
+                           hd, sp);
 }
 
 // One rollout step t -> t+1.  Actions: token ids [S,N] (int32, action vocabulary index) or, if act_f64 != nullptr,
