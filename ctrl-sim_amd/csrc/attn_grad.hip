@@ -335,7 +335,7 @@ AttnGradWs attn_grad_carve(size_t base, int B, int Lq, int Lk) {
 int launch_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, const unsigned char* key_pad, const float* dY, int lddy,
                            const float* Win, const float* bin, const float* Wo, const float* bo, const float* gamma, const float* beta,
                            int B, int Lq, int Lk, char* ws, const AttnGradWs& w, float* grads, float* dX, int lddx, float* dMem, int lddm,
-                           hipStream_t st) {
+                           int accumulate_dmem, hipStream_t st) {
   (void)beta;                                          // the backward of a LayerNorm does not read its bias
   if (!X || !Mem || !dY || !Win || !bin || !Wo || !bo || !gamma || !ws || !grads || B < 1 || Lq < 1 || Lk < 1 ||
       (long)B * Lq > 0x7fffffffL / DM || (long)B * Lk > 0x7fffffffL / (2 * DM) || ldx < DM || ldm < DM || lddy < DM || (dX && lddx < DM) ||
@@ -394,15 +394,25 @@ int launch_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, c
     hipLaunchKernelGGL(fg_colsum_kernel, dim3(2, ncb), dim3(256), 0, st, dKVc, 2L * DM, nk, 2 * DM, pck + nck * 2 * DM);
     nck += ncb;
   }
-  // dMem = dK Wk + dV Wv
+  // dMem (+)= dK Wk + dV Wv: each element has one owner, which with accumulate_dmem adds its sum to what dMem holds (a padded key's
+  // row adds an exact +0)
   if (dMem)
-    FG_CHK(hg_gemm_t<true, false, HG_EPI_PLAIN>(HgGemm{dKV, 2 * DM, 1, Win + wsz, DM, 1, dMem, lddm, 0, nullptr, rowsk, DM, 2 * DM, 2 * DM, 0}, st));
+    FG_CHK(hg_gemm_t<true, false, HG_EPI_PLAIN>(HgGemm{dKV, 2 * DM, 1, Win + wsz, DM, 1, dMem, lddm, 0, nullptr, rowsk, DM, 2 * DM, 2 * DM,
+                                                       accumulate_dmem ? 1 : 0}, st));
   if (nln > w.nln || ncq > w.ncq || nck > w.nck) return CTRLSIM_EINVAL;
   float* const col3[3] = {gg, gbe, gbo};               // the LayerNorm backward's partial rows are [3][256]: (dY xhat, dY, dS)
   for (int q = 0; q < 3; ++q)
     hipLaunchKernelGGL(fg_colreduce_kernel, dim3(DM / 16), dim3(256), 0, st, pln + q * DM, (int)nln, 3L * DM, DM, col3[q]);
   hipLaunchKernelGGL(fg_colreduce_kernel, dim3(DM / 16), dim3(256), 0, st, pcq, (int)ncq, (long)DM, DM, gbin);
   hipLaunchKernelGGL(fg_colreduce_kernel, dim3(2 * DM / 16), dim3(256), 0, st, pck, (int)nck, 2L * DM, 2 * DM, gbin + DM);
+  return ctrlsim_launch_status();
+}
+
+// Step 2 alone, for decoder_layer_grad.hip's recompute of the sublayer's output: O [nc Lq, 256] and the statistics [nc Lq, 8] of the nc
+// contexts from c0 on (Q, O and the statistics chunk-local, K | V and key_pad of all contexts)
+int launch_attn_fwd_stats(const float* Q, const float* KV, const unsigned char* key_pad, float* O, float* smax, float* slog, int nc, int Lq,
+                          int Lk, int c0, hipStream_t st) {
+  hipLaunchKernelGGL(ag_fwd_kernel, dim3((Lq + 127) / 128, NHEAD, nc), dim3(256), 0, st, Q, KV, key_pad, O, smax, slog, Lq, Lk, c0);
   return ctrlsim_launch_status();
 }
 
@@ -422,5 +432,5 @@ extern "C" int ctrlsim_attn_block_grad(const float* X, int ldx, const float* Mem
   if (B < 1 || Lq < 1 || Lk < 1 || !beta || !workspace || (long)B * Lq > 0x7fffffffL / DM || (long)B * Lk > 0x7fffffffL / (2 * DM))
     return CTRLSIM_EINVAL;
   return launch_attn_block_grad(X, ldx, Mem, ldm, key_pad, dY, lddy, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, gamma, beta,
-                                B, Lq, Lk, static_cast<char*>(workspace), attn_grad_carve(0, B, Lq, Lk), grads, dX, lddx, dMem, lddm, stream);
+                                B, Lq, Lk, static_cast<char*>(workspace), attn_grad_carve(0, B, Lq, Lk), grads, dX, lddx, dMem, lddm, 0, stream);
 }

@@ -29,7 +29,7 @@ NO_PK = "-Xclang -target-feature -Xclang -packed-fp32-ops"
 COMMON = "-fno-slp-vectorize"
 SRCS = {"gemm": "", "attention": "", "sim": "-ffp-contract=off", "context": "-ffp-contract=off", "embed": NO_PK,
         "map_encoder": "", "sample": "", "metrics": "-ffp-contract=off", "rewards": "-ffp-contract=off", "replay": "-ffp-contract=off",
-        "dataset": "-ffp-contract=off", "window": "-ffp-contract=off", "head_grad": NO_PK, "ffn_grad": NO_PK, "attn_grad": NO_PK, "self_attn_grad": NO_PK, "forward": "", "dispatch": "", "api": ""}
+        "dataset": "-ffp-contract=off", "window": "-ffp-contract=off", "head_grad": NO_PK, "ffn_grad": NO_PK, "attn_grad": NO_PK, "self_attn_grad": NO_PK, "decoder_layer_grad": NO_PK, "forward": "", "dispatch": "", "api": ""}
 OUT = os.path.join(HERE, "libctrlsim_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # CTRLSIM_VARIANT=<name> (tools only): a complete second library built with CTRLSIM_EXTRA_DEFS into its own object directory,

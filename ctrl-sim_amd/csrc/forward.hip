@@ -841,6 +841,7 @@ struct FullReq {
   float* x1_store = nullptr;                                // ... and the rows that enter its cross-attention sublayer (its norm1 output)
   float* x0_store = nullptr;                                // ... and the rows that enter that layer (for ND == 1 the assembled tokens), copied
                                                             // before its first kernel
+  float* const* x0_layers = nullptr;                        // every-token passes: x0_layers[i] (nullable) receives the rows that enter layer i
   const float** mem_seen = nullptr;                         // receive the addresses of the scene encoder's output rows and their key-padding
   const unsigned char** pad_seen = nullptr;                 // bytes in the workspace: written by the scene side, only read from there on
 };
@@ -875,6 +876,9 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
     const bool kv_only = last_few && ctrlsim_option(OPT_LAST_KV) != 0;
     if (i == d.ND - 1 && rq.x0_store && every_token &&
         hipMemcpyAsync(rq.x0_store, w.X, (size_t)bt.rL * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return CTRLSIM_ELAUNCH;
+    if (rq.x0_layers && rq.x0_layers[i] && every_token &&
+        hipMemcpyAsync(rq.x0_layers[i], w.X, (size_t)bt.rL * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
       return CTRLSIM_ELAUNCH;
     // the last layer of a rollout pass reads the queries of the A queried tokens only: keys and values of every token (two of the
     // in_proj's three column groups), queries from the gathered rows below — a twelfth of the pass's in_proj work less
@@ -1142,11 +1146,12 @@ int copy_rows(float* dst, const float* src, size_t rows, hipStream_t st) {
 // (FullReq::u_store); scope 2 copies the rows behind norm1 (X1) before the out-projection + norm2 overwrite them, scope 3 the rows that
 // enter the layer (X0) before its in_proj.  Mem and its padding bytes are read where the scene side left them: forward_full writes w.src /
 // w.src_pad in scene_side only, the decoder and the heads read them.
-extern "C" int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                          const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
-                                          double* per_ctx, float* grads, const ctrlsim_train_taps* taps, hipStream_t st) {
-  static const ctrlsim_train_taps none{};
-  const ctrlsim_train_taps& t = taps ? *taps : none;
+// x0_layers / mem_seen / pad_seen (the all-layers entry below): the per-layer row stores of the forward, and where Mem and its padding
+// bytes lie in the workspace; the public entry passes none.
+namespace {
+int loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving, const ctrlsim_loss_cfg* cfg,
+               float loss_action_coef, int scope, void* workspace, double* sums, double* per_ctx, float* grads, const ctrlsim_train_taps& t,
+               float* const* x0_layers, const float** mem_seen, const unsigned char** pad_seen, hipStream_t st) {
   if (scope < 0 || scope > 3 || !grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
   if ((scope < 1 && (t.dU || t.u_out)) || (scope < 2 && (t.dX1 || t.dMem || t.x1_out || t.mem_out)) || (scope < 3 && (t.dX0 || t.x0_out)))
     return CTRLSIM_EINVAL;                                                        // a tap of a wider scope than the call's
@@ -1166,10 +1171,12 @@ extern "C" int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq,
   float *dX = t.dX ? t.dX : at(scope >= 1, L.dX), *dU = t.dU ? t.dU : at(scope >= 2, L.dU), *dX1 = t.dX1 ? t.dX1 : at(scope >= 3, L.dX1);
   const float* Mem = nullptr;
   const unsigned char* pad = nullptr;
-  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = X0;
+  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = X0; rq.x0_layers = x0_layers;
   if (scope >= 2) { rq.mem_seen = &Mem; rq.pad_seen = &pad; }
   CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
   if (!X || (scope >= 2 && (!Mem || !pad))) return CTRLSIM_EINVAL;
+  if (mem_seen) *mem_seen = Mem;
+  if (pad_seen) *pad_seen = pad;
   CHK(copy_rows(t.x_out, X, L.rows3, st));
   CHK(copy_rows(t.u_out, U, L.rows3, st));
   CHK(copy_rows(t.x1_out, X1, L.rows3, st));
@@ -1181,11 +1188,111 @@ extern "C" int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq,
                               group(0), dU, DM, st));
   if (scope >= 2)
     CHK(launch_attn_block_grad(X1, DM, Mem, DM, pad, dU, DM, Ld->cq.w, Ld->cq.b, Ld->cout.w, Ld->cout.b, Ld->n2.g, Ld->n2.b, B, Tq * A * 3, L.M,
-                               ws, L.a, group(1), dX1, DM, t.dMem, DM, st));
+                               ws, L.a, group(1), dX1, DM, t.dMem, DM, 0, st));
   if (scope >= 3) {
     CHK(copy_rows(t.x0_out, X0, L.rows3, st));
     CHK(launch_self_attn_block_grad(X0, DM, dX1, DM, Ld->qkv.w, Ld->qkv.b, Ld->out.w, Ld->out.b, Ld->n1.g, Ld->n1.b, B, Tq, A,
                                     d.variant == 4 ? 1 : 0, ws, L.s, group(2), t.dX0, DM, st));
+  }
+  return CTRLSIM_OK;
+}
+// the 18 tensors of a decoder layer behind scope 3's buffer, in the layer op's order: kGroups, group by group
+const GradPart* layer_part(int j) { return &kGroups[j / 6][j % 6]; }
+long layer_floats(const ctrlsim_dims& d) {
+  long o = 0;
+  for (int j = 0; j < 18; ++j) o += layer_part(j)->perF * d.F + layer_part(j)->fixed;
+  return o;
+}
+// The workspace of the all-layers entry: scope 3's, then the ND-1 row buffers X0_l, one dX0 buffer (a layer's dX0 overwrites its dY
+// where the caller takes neither as a tap) and the layer op's carve
+struct DecoderLayout { TrainLayout t; size_t X0[CTRLSIM_MAX_DECODER_LAYERS], dX0, bytes; DecLayerGradWs w; };
+bool decoder_layout(const ctrlsim_dims& d, int B, int Tq, DecoderLayout& o) {
+  if (d.ND < 1 || d.ND > CTRLSIM_MAX_DECODER_LAYERS || !train_layout(d, B, Tq, 3, o.t)) return false;
+  const size_t n = (o.t.rows3 * DM * sizeof(float) + 255) & ~size_t(255);
+  size_t off = (o.t.bytes + 255) & ~size_t(255);
+  for (int l = 0; l < d.ND - 1; ++l, off += n) o.X0[l] = off;
+  o.dX0 = off; off += n;
+  o.bytes = off;
+  if (d.ND > 1) {
+    if (!decoder_layer_grad_dims_ok(B, Tq, d.A, o.t.M, d.F)) return false;
+    o.w = decoder_layer_grad_carve(off, B, Tq, d.A, o.t.M, d.F);
+    o.bytes = o.w.bytes;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                          const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
+                                          double* per_ctx, float* grads, const ctrlsim_train_taps* taps, hipStream_t st) {
+  static const ctrlsim_train_taps none{};
+  return loss_grads(m, B, Tq, c, moving, cfg, loss_action_coef, scope, workspace, sums, per_ctx, grads, taps ? *taps : none, nullptr, nullptr,
+                    nullptr, st);
+}
+
+// ---- training (d): every decoder layer.  Scope 3 with the rows that enter each earlier layer copied by the forward, then the layer op
+// (csrc/decoder_layer_grad.hip) for l = ND-2 .. 0 on those rows: dY = the dX0 of layer l + 1, dMem accumulated onto the last layer's.
+extern "C" int ctrlsim_decoder_grad_layout(const ctrlsim_dims* d, int has_future_states, int cap, const char** names, int64_t* offsets) {
+  static std::string store[18 * (CTRLSIM_MAX_DECODER_LAYERS - 1)];
+  if (!d || d->ND < 1 || d->ND > CTRLSIM_MAX_DECODER_LAYERS || d->F < 1) return CTRLSIM_EINVAL;
+  const int n3 = ctrlsim_train_grad_layout(d, has_future_states, 3, 0, nullptr, nullptr);
+  if (n3 < 0) return n3;
+  const int n = n3 + 18 * (d->ND - 1);
+  if ((names || offsets) && cap < n) return CTRLSIM_EINVAL;
+  if (names || offsets) ctrlsim_train_grad_layout(d, has_future_states, 3, n3, names, offsets);
+  long o = group_base(*d, has_future_states != 0, 3);
+  int i = n3;
+  for (int l = d->ND - 2; l >= 0; --l) {
+    const std::string pre = "decoder.transformer_decoder.layers." + std::to_string(l);
+    for (int j = 0; j < 18; o += layer_part(j)->perF * d->F + layer_part(j)->fixed, ++j, ++i) {
+      if (names) { store[i - n3] = pre + layer_part(j)->suffix; names[i] = store[i - n3].c_str(); }
+      if (offsets) offsets[i] = o;
+    }
+  }
+  if (offsets && cap > n) offsets[n] = o;              // (room for one more: the total)
+  return n;
+}
+extern "C" int64_t ctrlsim_decoder_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq) {
+  DecoderLayout L;
+  if (!d || B < 1 || Tq < 1 || !decoder_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
+  return (int64_t)L.bytes;
+}
+extern "C" int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                                  const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
+                                                  double* per_ctx, float* grads, const ctrlsim_decoder_taps* taps, hipStream_t st) {
+  static const ctrlsim_decoder_taps none{};
+  const ctrlsim_decoder_taps& t = taps ? *taps : none;
+  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
+  const ctrlsim_dims& d = m->d;
+  DecoderLayout L;
+  if (!decoder_layout(d, B, Tq, L)) return CTRLSIM_EINVAL;
+  if (tok_variant(d.variant) != 0 || (d.variant != 0 && d.variant != 4)) return CTRLSIM_EINVAL;      // (scope 3's own refusal, before anything runs)
+  for (int l = d.ND; l < CTRLSIM_MAX_DECODER_LAYERS; ++l)
+    if (t.x0_out[l] || t.dX0[l]) return CTRLSIM_EINVAL;
+  for (int l = 0; l < d.ND - 1; ++l)
+    if (m->dec[l].ckv.w != m->dec[l].cq.w + (long)DM * DM || m->dec[l].ckv.b != m->dec[l].cq.b + DM) return CTRLSIM_EINVAL;
+  char* ws = static_cast<char*>(workspace);
+  auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
+  const int last = d.ND - 1;
+  float* x0[CTRLSIM_MAX_DECODER_LAYERS] = {};
+  for (int l = 0; l < last; ++l) x0[l] = f(L.X0[l]);
+  ctrlsim_train_taps t3{};
+  t3.dX = t.dX; t3.x_out = t.x_out; t3.dMem = t.dMem; t3.mem_out = t.mem_out; t3.x0_out = t.x0_out[last];
+  t3.dX0 = t.dX0[last] ? t.dX0[last] : last > 0 ? f(L.dX0) : nullptr;
+  const float* Mem = nullptr;
+  const unsigned char* pad = nullptr;
+  CHK(loss_grads(m, B, Tq, c, moving, cfg, loss_action_coef, 3, workspace, sums, per_ctx, grads, t3, last > 0 ? x0 : nullptr, &Mem, &pad, st));
+  const float* dY = t3.dX0;
+  float* g = grads + group_base(d, m->has_fut, 3);
+  for (int l = last - 1; l >= 0; --l, g += layer_floats(d)) {
+    const DecLayer& Ld = m->dec[l];
+    const float* tn[18] = {Ld.lin1.w, Ld.lin1.b, Ld.lin2.w, Ld.lin2.b, Ld.n3.g, Ld.n3.b, Ld.cq.w, Ld.cq.b, Ld.cout.w, Ld.cout.b, Ld.n2.g, Ld.n2.b,
+                           Ld.qkv.w, Ld.qkv.b, Ld.out.w, Ld.out.b, Ld.n1.g, Ld.n1.b};
+    CHK(copy_rows(t.x0_out[l], x0[l], L.t.rows3, st));
+    float* dX0 = t.dX0[l] ? t.dX0[l] : l > 0 ? f(L.dX0) : nullptr;       // (layer 0's, untapped, is nobody's dY)
+    CHK(launch_decoder_layer_grad(x0[l], DM, Mem, DM, pad, dY, DM, tn, B, Tq, d.A, L.t.M, d.F, d.variant == 4 ? 1 : 0, ws, L.w, g, dX0, DM, t.dMem,
+                                  DM, 1, nullptr, nullptr, st));
+    dY = dX0;
   }
   return CTRLSIM_OK;
 }

@@ -144,7 +144,9 @@ AttnGradWs attn_grad_carve(size_t base, int B, int Lq, int Lk);
 int launch_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, const unsigned char* key_pad, const float* dY, int lddy,
                            const float* Win, const float* bin, const float* Wo, const float* bo, const float* gamma, const float* beta,
                            int B, int Lq, int Lk, char* ws, const AttnGradWs& w, float* grads, float* dX, int lddx, float* dMem, int lddm,
-                           hipStream_t st);
+                           int accumulate_dmem, hipStream_t st);     // accumulate_dmem: dMem += this call's, instead of =
+int launch_attn_fwd_stats(const float* Q, const float* KV, const unsigned char* key_pad, float* O, float* smax, float* slog, int nc, int Lq,
+                          int Lk, int c0, hipStream_t st);
 
 // ---- self_attn_grad.hip: the backward of a decoder layer's self-attention sublayer under the multi-agent causal mask (contexts of 3 T A rows)
 struct SelfAttnGradWs { size_t QKV, dQKV, O, S, dS, stat, slab, part_ln, part_cs, bytes; int chunk_ctx; long nln, ncs; };
@@ -152,6 +154,16 @@ SelfAttnGradWs self_attn_grad_carve(size_t base, int B, int L);
 int launch_self_attn_block_grad(const float* X, int ldx, const float* dY, int lddy, const float* Win, const float* bin, const float* Wo,
                                 const float* bo, const float* gamma, const float* beta, int B, int T, int A, int mask_mode, char* ws,
                                 const SelfAttnGradWs& w, float* grads, float* dX, int lddx, hipStream_t st);
+int launch_self_attn_fwd_stats(const float* QKV, float* O, float* smax, float* slog, int nc, int L, int A, int mask_mode, hipStream_t st);
+
+// ---- decoder_layer_grad.hip: a whole decoder layer's backward from the rows that enter it (X1 and U recomputed, then the three ops above)
+struct DecLayerGradWs { size_t X1, U, dU, dX1, bytes; FfnGradWs f; AttnGradWs a; SelfAttnGradWs s; };
+bool decoder_layer_grad_dims_ok(int B, int T, int A, int Lk, int F);
+DecLayerGradWs decoder_layer_grad_carve(size_t base, int B, int T, int A, int Lk, int F);
+int launch_decoder_layer_grad(const float* X0, int ldx, const float* Mem, int ldm, const unsigned char* key_pad, const float* dY, int lddy,
+                              const float* const* tensors, int B, int T, int A, int Lk, int F, int mask_mode, char* ws,
+                              const DecLayerGradWs& w, float* grads, float* dX0, int lddx0, float* dMem, int lddm, int accumulate_dmem,
+                              float* x1_out, float* u_out, hipStream_t st);
 
 // ---- sim.hip
 int launch_sim_init(int S, int N, int E, const float* init_pose, const float* size, const float* edges, const unsigned char* exists, float* phys,

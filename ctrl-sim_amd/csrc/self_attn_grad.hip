@@ -431,6 +431,12 @@ int launch_self_attn_block_grad(const float* X, int ldx, const float* dY, int ld
   return ctrlsim_launch_status();
 }
 
+// Step 2 alone, for decoder_layer_grad.hip's recompute of the sublayer's output: O [nc L, 256] and the statistics [nc L, 8] of nc contexts
+int launch_self_attn_fwd_stats(const float* QKV, float* O, float* smax, float* slog, int nc, int L, int A, int mask_mode, hipStream_t st) {
+  hipLaunchKernelGGL(sa_fwd_kernel, dim3((L + 127) / 128, NHEAD, nc), dim3(256), 0, st, QKV, O, smax, slog, L, A, mask_mode);
+  return ctrlsim_launch_status();
+}
+
 // ---- the op as a C ABI entry (include/ctrlsim.h)
 namespace {
 bool sa_dims_ok(int B, int T, int A) {

@@ -78,6 +78,10 @@ class HipModel:
         self._cross = {self._ffn_layer + s: np.array(weights[self._ffn_layer + s], np.float32) for s in _pack.TRAINABLE_CROSS_SUFFIXES}
         # ... and of its self-attention sublayer (update(..., self_attn=True)); the out-projection weight among them is an input of .selfq#wop
         self._self = {self._ffn_layer + s: np.array(weights[self._ffn_layer + s], np.float32) for s in _pack.TRAINABLE_SELF_SUFFIXES}
+        # ... and of the same 18 tensors of every earlier decoder layer (update(..., decoder=True))
+        sfx = _pack.TRAINABLE_FFN_SUFFIXES + _pack.TRAINABLE_CROSS_SUFFIXES + _pack.TRAINABLE_SELF_SUFFIXES
+        self._early = {f"decoder.transformer_decoder.layers.{l}{x}": np.array(weights[f"decoder.transformer_decoder.layers.{l}{x}"], np.float32)
+                       for l in range(self.dims.ND - 1) for x in sfx}
         self.split_fallback = False     # an engine of this model met non-finite values under f16x3: later split="auto" engines
                                         # (the policy surface opens one per scenario session) start on bf16x6 right away
 
@@ -87,7 +91,7 @@ class HipModel:
             raise RuntimeError(f"workspace query failed: {n}")
         return int(n)
 
-    def update(self, named_tensors, cross=False, self_attn=False):
+    def update(self, named_tensors, cross=False, self_attn=False, decoder=False):
         """New fp32 values for tensors of the MLP heads (state-dict names under pack.HEAD_PREFIXES) and of the last decoder layer's
         feed-forward block (its linear1, linear2 and norm3: pack.TRAINABLE_FFN_SUFFIXES) -> torch tensor / ndarray of the tensor's
         shape: written into the packed buffer at the existing offsets, and every packed image `pack.pack` derives from them (operand
@@ -98,11 +102,17 @@ class HipModel:
         out_proj and norm2: pack.TRAINABLE_CROSS_SUFFIXES) and re-derives pack.cross_images; without it those names are refused like
         any other trunk tensor, so that a caller in a narrower scope cannot move them by mistake.
         self_attn=True (the training scope "heads+last_layer") likewise takes the layer's self-attention sublayer (self_attn.in_proj /
-        out_proj and norm1: pack.TRAINABLE_SELF_SUFFIXES) and re-derives pack.self_images."""
+        out_proj and norm1: pack.TRAINABLE_SELF_SUFFIXES) and re-derives pack.self_images.
+        decoder=True (the training scope "heads+decoder") takes all of that and the same 18 tensors of EVERY earlier decoder layer, and
+        re-derives pack.ffn_images, pack.cross_images and pack.self_images of each layer it is given tensors of — every image the fused
+        kernels of the earlier layers read."""
+        if decoder:
+            cross = self_attn = True
+        early = self._early if decoder else {}
         new = {}
         for k, v in named_tensors.items():
             master = (self._heads if k in self._heads else self._cross if cross and k in self._cross else
-                      self._self if self_attn and k in self._self else self._ffn)
+                      self._self if self_attn and k in self._self else early if k in early else self._ffn)
             if k not in master:
                 raise KeyError(f"{k}: update() takes the tensors of the MLP heads this model has ({', '.join(_pack.HEAD_PREFIXES)}) and "
                                f"of {self._ffn_layer}'s feed-forward block")
@@ -124,12 +134,18 @@ class HipModel:
         if any(k in self._self and k.endswith("weight") and ".self_attn." in k for k in new):
             layer = {k: new.get(k, v) for k, v in self._self.items() if k.endswith("weight") and ".self_attn." in k}
             images.update(_pack.self_images(self.dims, layer, self._offset))
+        for pre in sorted({".".join(k.split(".")[:4]) for k in new if k in early}):      # decoder.transformer_decoder.layers.{l}
+            layer = {k: new.get(k, v) for k, v in early.items() if k.startswith(pre + ".") and k.endswith("weight") and ".norm" not in k}
+            images.update(_pack.ffn_images(self.dims, layer, self._offset))
+            images.update(_pack.cross_images(self.dims, layer, self._offset))
+            images.update(_pack.self_images(self.dims, layer, self._offset))
         for k, v in list(new.items()) + list(images.items()):     # (stream-ordered behind the kernels already enqueued)
             v = v.reshape(-1)
             o = self._offset[k]
             self.flat[o:o + v.size].copy_(torch.from_numpy(v))
         for k, v in new.items():
-            (self._heads if k in self._heads else self._cross if k in self._cross else self._self if k in self._self else self._ffn)[k] = v
+            (self._heads if k in self._heads else self._cross if k in self._cross else self._self if k in self._self else
+             early if k in early else self._ffn)[k] = v
 
     def __del__(self):
         try:

@@ -14,8 +14,11 @@ block (linear1, linear2, norm3): scope 1 (csrc/ffn_grad.hip) differentiates it t
 `set_trainable("heads+ffn+cross")` adds that layer's cross-attention sublayer (multihead_attn, norm2): scope 2 (csrc/attn_grad.hip)
 starts from `dU` and returns `dX1` and `dMem`, the gradients at the layer's norm1 output and at the scene encoder's output;
 `set_trainable("heads+last_layer")` adds its self-attention sublayer (self_attn, norm1), so that the whole last decoder layer trains:
-scope 3 (csrc/self_attn_grad.hip) starts from `dX1` and returns `dX0`, the gradient at the layer's input rows.  The backward through the
-earlier decoder layers, the encoder and the embeddings is not built."""
+scope 3 (csrc/self_attn_grad.hip) starts from `dX1` and returns `dX0`, the gradient at the layer's input rows.
+`set_trainable("heads+decoder")` (CtRLSim.DECODER_SCOPE) trains every decoder layer: ctrlsim_forward_loss_grads_decoder does what scope 3
+does and then, for each earlier layer from the last but one down, recomputes the layer's inside from the rows that entered it and runs the
+three backward ops (csrc/decoder_layer_grad.hip); it returns `dX0` of every layer and `dMem` summed over all of them, the gradients the
+encoder's and the embeddings' backward — not built — would start from."""
 from __future__ import annotations
 
 import numpy as np
@@ -252,7 +255,19 @@ class CtRLSim:
         ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
         assert ws.dtype == torch.uint8 and ws.numel() >= n
         head = (self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef)
-        if X is None:
+        if scope == self.DECODER_SCOPE:
+            assert X is None
+            taps = {k: torch.empty(rowsm if k in ("dMem", "mem_out") else rows3, d.D, device=dev) for k in ("dX", "x_out", "dMem", "mem_out")
+                    if k in want}
+            ct = _lib.DecoderTaps(**{k: t.data_ptr() for k, t in taps.items()})
+            for k in ("dX0", "x0_out"):
+                if k in want:
+                    taps[k] = [torch.empty(rows3, d.D, device=dev) for _ in range(d.ND)]
+                    for l, t in enumerate(taps[k]):
+                        getattr(ct, k)[l] = t.data_ptr()
+            _lib.check(lib.ctrlsim_forward_loss_grads_decoder(*head, ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), C.byref(ct), st),
+                       "forward_loss_grads_decoder")
+        elif X is None:
             ct = _lib.TrainTaps(**{k: t.data_ptr() for k, t in taps.items()})
             _lib.check(lib.ctrlsim_forward_loss_grads(*head, self.SCOPES.index(scope), ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(),
                                                       C.byref(ct), st), "forward_loss_grads")
@@ -300,31 +315,42 @@ class CtRLSim:
 
     # ---- training, second stage (a): the heads and the last decoder layer's feed-forward block
     SCOPES = ("heads", "heads+ffn", "heads+ffn+cross", "heads+last_layer")
+    # training (d): the heads and EVERY decoder layer (ctrlsim_forward_loss_grads_decoder); accepted wherever a scope name is taken
+    DECODER_SCOPE = "heads+decoder"
 
     def set_trainable(self, scope="heads"):
         """What training_step / configure_optimizers / optimizer_step train: "heads" (the default: the three MLP heads), "heads+ffn"
         (the heads and linear1, linear2, norm3 of the last decoder layer), "heads+ffn+cross" (and that layer's cross-attention:
         multihead_attn.in_proj / out_proj and norm2) or "heads+last_layer" (and its self-attention: self_attn.in_proj / out_proj and
-        norm1 — the whole last decoder layer).  Choose before configure_optimizers."""
-        if scope not in self.SCOPES:
-            raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES}")
+        norm1 — the whole last decoder layer) or "heads+decoder" (and the 18 tensors of every earlier decoder layer).  Choose before
+        configure_optimizers."""
+        if scope not in self.SCOPES + (self.DECODER_SCOPE,):
+            raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES + (self.DECODER_SCOPE,)}")
         self._scope = scope
         return self
 
     def train_grad_layout(self, scope=None):
         """head_grad_layout for a scope (ctrlsim_train_grad_layout): "heads" gives exactly head_grad_layout's answer, "heads+ffn" appends
         the six tensors of the last decoder layer's feed-forward block, "heads+ffn+cross" the six of its cross-attention sublayer behind
-        them, "heads+last_layer" the six of its self-attention sublayer behind those.  Needs no device."""
+        them, "heads+last_layer" the six of its self-attention sublayer behind those; "heads+decoder" (ctrlsim_decoder_grad_layout)
+        behind those, for the layers ND-2 down to 0, each layer's 18 tensors in the same group order.  Needs no device."""
         import ctypes as C
         from .. import _lib
         from ..engine import _dims_struct
         lib = _lib.lib()
-        sc = self.SCOPES.index(self._scope if scope is None else scope)
+        scope = self._scope if scope is None else scope
         has_fut = int("decoder.predict_future_states.mlp.0.weight" in self.weights)
         cd = _dims_struct(self.dims)
-        n = lib.ctrlsim_train_grad_layout(C.byref(cd), has_fut, sc, 0, None, None)
+        if scope == self.DECODER_SCOPE:
+            query = lambda cap, names, offs: lib.ctrlsim_decoder_grad_layout(C.byref(cd), has_fut, cap, names, offs)
+        else:
+            if scope not in self.SCOPES:
+                raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES + (self.DECODER_SCOPE,)}")
+            sc = self.SCOPES.index(scope)
+            query = lambda cap, names, offs: lib.ctrlsim_train_grad_layout(C.byref(cd), has_fut, sc, cap, names, offs)
+        n = query(0, None, None)
         names, offs = (C.c_char_p * max(n, 1))(), (C.c_int64 * (max(n, 0) + 1))()
-        if n < 0 or lib.ctrlsim_train_grad_layout(C.byref(cd), has_fut, sc, n + 1, names, offs) != n:
+        if n < 0 or query(n + 1, names, offs) != n:
             raise RuntimeError("training gradient layout query failed")
         out = [(names[i].decode(), int(offs[i]), tuple(np.asarray(self.weights[names[i].decode()]).shape)) for i in range(n)]
         return out, int(offs[n])
@@ -332,13 +358,17 @@ class CtRLSim:
     def trainable_parameters(self):
         """state-dict name -> torch.nn.Parameter of the selected scope, in layout order: head_parameters() (the same objects), then under
         "heads+ffn" the six tensors of the last decoder layer's feed-forward block, under "heads+ffn+cross" the six of its cross-attention
-        sublayer too, under "heads+last_layer" the six of its self-attention sublayer as well (each created once)."""
+        sublayer too, under "heads+last_layer" the six of its self-attention sublayer as well, under "heads+decoder" the 18 tensors of
+        every earlier decoder layer too (each created once)."""
         return self._parameters(self._scope)
 
     def train_grad_workspace_bytes(self, B, scope="heads+ffn"):
         import ctypes as C
         from .. import _lib
-        n = _lib.lib().ctrlsim_train_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T, self.SCOPES.index(scope))
+        if scope == self.DECODER_SCOPE:
+            n = _lib.lib().ctrlsim_decoder_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T)
+        else:
+            n = _lib.lib().ctrlsim_train_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T, self.SCOPES.index(scope))
         if n < 0:
             raise RuntimeError(f"training gradient workspace query failed: {n}")
         return int(n)
@@ -355,9 +385,20 @@ class CtRLSim:
         layer's norm1 output [B*T*A*3, 256], this layer's share of the gradient at the scene encoder's output [B*M, 256], M = (P + A + 3)
         & ~3, and the two inputs themselves; everything the narrower scope returns is bit for bit what it returns.  Under
         "heads+last_layer" (scope 3) the gradients continue with the six self-attention tensors and the tuple
-        with (dX0, x0_out): the gradient at the layer's input rows [B*T*A*3, 256] and those rows themselves."""
+        with (dX0, x0_out): the gradient at the layer's input rows [B*T*A*3, 256] and those rows themselves.
+        Under "heads+decoder" (ctrlsim_forward_loss_grads_decoder) the gradients continue with the 18 tensors of each earlier layer and
+        the tuple is (sums, gradients, dX, x_out, dMem, mem_out, dX0, x0_out): dMem summed over all ND layers; dX0 and x0_out LISTS of ND
+        tensors, entry l the gradient at the rows that enter layer l and those rows (dX0[0]: the gradient at the assembled tokens).  The
+        intermediate taps of the last layer (dU, u_out, dX1, x1_out) do not exist in that scope."""
         if scope is None:
             scope = self._scope if self._scope != "heads" else "heads+ffn"
+        if scope == self.DECODER_SCOPE:
+            if dU or u_out or dX1 or x1_out:
+                raise ValueError("dU, u_out, dX1 and x1_out do not exist under the scope \"heads+decoder\"")
+            order = ("dX", "x_out", "dMem", "mem_out", "dX0", "x0_out")
+            asked = dict(dX=dX, x_out=x_out, dMem=dMem, mem_out=mem_out, dX0=dX0, x0_out=x0_out)
+            sums, named, taps = self._forward_loss_grads(cb, moving, B, scope, [k for k in order if asked[k]], workspace=workspace)
+            return (sums, named) + tuple(taps.get(k) for k in order)
         if scope not in self.SCOPES[1:]:
             raise ValueError(f"loss_and_train_grads scope {scope!r}: one of {self.SCOPES[1:]}")
         sc = self.SCOPES.index(scope)
@@ -437,6 +478,9 @@ class CtRLSim:
             scheduler.step()
         optimizer.zero_grad(set_to_none=True)
         new = {k: p.detach().cpu().numpy() for k, p in params.items()}
-        self.hip.update(new, cross=self._scope in self.SCOPES[2:], self_attn=self._scope == "heads+last_layer")
+        if self._scope == self.DECODER_SCOPE:
+            self.hip.update(new, decoder=True)
+        else:
+            self.hip.update(new, cross=self._scope in self.SCOPES[2:], self_attn=self._scope == "heads+last_layer")
         self.weights.update({k: v.copy() for k, v in new.items()})
         return float(norm)

@@ -395,6 +395,52 @@ int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int
 int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
                                const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
                                double* per_ctx, float* grads, const ctrlsim_train_taps* taps /* nullable */, hipStream_t stream);
+/* ---- training (d): one whole decoder layer's backward by recompute (csrc/decoder_layer_grad.hip) ---------------------------------------
+ * The op.  Forward being differentiated, per context of L = 3 T A token rows and Lk memory rows: the three sublayers above in a row,
+ *   X1 = the self-attention sublayer of X0 (norm1),  U = the cross-attention sublayer of X1 and Mem (norm2),  Y = the feed-forward block
+ *   of U (norm3)
+ * — torch.nn.TransformerDecoderLayer, post-LN, relu.  X0, dY [B*L, 256], Mem [B*Lk, 256] with leading dimensions >= 256 (floats); key_pad
+ * [B, Lk] bytes or NULL; mask_mode as the self-attention op's.  tensors: a HOST array of the layer's 18 fp32 master tensors (device
+ * pointers), grads: ONE flat float32 buffer of their gradients, both in the order a training scope appends them: the six feed-forward
+ * tensors (linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm3.weight, norm3.bias), the six of the cross-attention
+ * (multihead_attn.in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, norm2.weight, norm2.bias), the six of the self-attention
+ * (self_attn.*, norm1.*), each group in state-dict order, back to back.  dX0 (nullable) [B*L, 256]: the gradient at X0; it MAY be dY
+ * itself with lddx0 == lddy.  dMem (nullable) [B*Lk, 256]: the gradient at Mem; with accumulate_dmem != 0 every element's one owner
+ * adds this call's value to what dMem holds (a fixed order: deterministic), otherwise it overwrites.  Rows of padded keys: exactly 0
+ * without the flag, left as they are with it.  x1_out, u_out (nullable) [B*L, 256] dense: X1 and U as the backward read them.
+ * Nothing of a forward pass is read but X0, Mem and key_pad: X1 and U are recomputed on the f32-input MFMA from the fp32 masters, then
+ * the three ops run on (U, dY), (X1, Mem, dU) and (X0, dX1) and recompute their own sublayer's inside.  The gradient is that of the layer
+ * function evaluated this way on X0 as given; the result equals, bit for bit, the three public ops called by hand on x1_out and u_out.
+ * A null pointer other than key_pad, dX0, dMem, x1_out, u_out, a leading dimension below 256, B, T, A, Lk or F < 1, another mask_mode,
+ * B*L*768 >= 2^31 or B*Lk*512 >= 2^31: CTRLSIM_EINVAL, nothing launched.  No float atomics, sums in fixed orders: identical bits from
+ * run to run, whatever the workspace held. */
+int64_t ctrlsim_decoder_layer_grad_workspace_bytes(int B, int T, int A, int Lk, int F);
+int ctrlsim_decoder_layer_grad(const float* X0, int ldx, const float* Mem, int ldm, const uint8_t* key_pad, const float* dY, int lddy,
+                               const float* const* tensors /* 18 fp32 masters */, int B, int T, int A, int Lk, int F, int mask_mode,
+                               void* workspace, float* grads, float* dX0, int lddx0, float* dMem, int lddm, int accumulate_dmem,
+                               float* x1_out, float* u_out, hipStream_t stream);
+/* ---- training (d): forward, loss, then the gradients of the heads and of EVERY decoder layer -------------------------------------------
+ * ctrlsim_forward_loss_grads_decoder does everything scope 3 of ctrlsim_forward_loss_grads does — the same launches, with one more row
+ * copy per earlier layer: the rows that enter layer l (X0_l), before that layer's first kernel; layers 0 .. ND-2 keep their fused
+ * forward — and then, for l = ND-2 .. 0, the layer op above on (X0_l, Mem, dY = dX0 of layer l + 1) with accumulate_dmem = 1.
+ * grads: scope 3's buffer, unchanged, as a prefix; then for l = ND-2 .. 0 the 18 tensors of decoder.transformer_decoder.layers.{l} in
+ * the layer op's order (ctrlsim_decoder_grad_layout: names, offsets and the total, as ctrlsim_train_grad_layout).
+ * Taps, each nullable: x0_out[l] / dX0[l], l < ND: the rows that enter layer l and the gradient there ([B*Tq*A*3, 256]; dX0[0] is the
+ * gradient at the assembled token rows); dMem [B*M, 256]: the gradient at the scene encoder's output, the sum over all ND layers — the
+ * last layer's contribution first, then descending l; mem_out, dX, x_out as scope 3's.  On the same inputs the loss sums, the scope-3
+ * prefix of grads, dX and dX0[ND-1] are bit for bit scope 3's; for ND == 1 the entry IS scope 3.  A model scope 3 refuses, ND >
+ * CTRLSIM_MAX_DECODER_LAYERS or a tap of a layer >= ND: CTRLSIM_EINVAL, nothing launched.  Workspace:
+ * ctrlsim_decoder_grads_workspace_bytes(dims, B, Tq): scope 3's, ND-1 row buffers, a dX0 pair, the layer op's. */
+#define CTRLSIM_MAX_DECODER_LAYERS 8
+typedef struct ctrlsim_decoder_taps {        /* every member nullable */
+  float *x0_out[CTRLSIM_MAX_DECODER_LAYERS], *dX0[CTRLSIM_MAX_DECODER_LAYERS];
+  float *dMem, *mem_out, *dX, *x_out;
+} ctrlsim_decoder_taps;
+int ctrlsim_decoder_grad_layout(const ctrlsim_dims* dims, int has_future_states, int cap, const char** names, int64_t* offsets);
+int64_t ctrlsim_decoder_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq);
+int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                                       const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
+                                       float* grads, const ctrlsim_decoder_taps* taps /* nullable */, hipStream_t stream);
 /* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
  * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
  * scratch: ctrlsim_loss_scratch_bytes. */

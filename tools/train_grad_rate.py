@@ -4,10 +4,12 @@ sublayer, 3: + its self-attention sublayer) on the same batch of B full-size win
 taps it adds (dX; dU; dX1, dMem; dX0 and x0_out), as the per-scope tools this one replaces did.  Device events around `reps` calls per
 measurement, all routes warmed and ALTERNATING in one process, three rounds; prints one JSON line per round, then the medians, the
 differences between neighbouring scopes and the workspace bytes.  Recorded in profiles/train_grad_rate.md, not gated.
+Scope 4 is "heads+decoder" (ctrlsim_forward_loss_grads_decoder: scope 3, then every earlier decoder layer by recompute), with the taps
+dX, dMem and dX0 / x0_out of every layer; its difference to scope 3, divided by ND - 1, is the added time per earlier layer.
 `trace SCOPE`: `reps` calls at that scope only, nothing timed — the run to put under a kernel trace (the difference of two scopes'
 per-kernel tables is what the wider one's backward adds).
 
-    python tools/train_grad_rate.py [B=64] [reps=10] [scope=3 | trace SCOPE]
+    python tools/train_grad_rate.py [B=64] [reps=10] [scope=4 | trace SCOPE]
 """
 import ctypes as C
 import json
@@ -26,14 +28,14 @@ from ctrlsim_amd.models import CtRLSim  # noqa: E402
 from ctrlsim_amd.engine import ctx_from_reference_layout  # noqa: E402
 import synth_inputs  # noqa: E402
 
-TAPS = (("dX",), ("dU",), ("dX1", "dMem"), ("dX0", "x0_out"))          # added per scope
+TAPS = (("dX",), ("dU",), ("dX1", "dMem"), ("dX0", "x0_out"))          # added per scope 0..3
 
 
 def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
     trace = len(sys.argv) > 3 and sys.argv[3] == "trace"
-    top = int(sys.argv[4 if trace else 3]) if len(sys.argv) > (4 if trace else 3) else 3
+    top = int(sys.argv[4 if trace else 3]) if len(sys.argv) > (4 if trace else 3) else 4
     cfg = spec.make_cfg()
     d = spec.Dims(cfg)
     dev = "cuda:0"
@@ -43,20 +45,30 @@ def main():
     inp = {k: np.concatenate([v] * ((B + len(v) - 1) // len(v)))[:B] for k, v in base.items()}
     cb = ctx_from_reference_layout(d, inp, d.T, dev)
     sizes = {"forward_loss": int(lib.ctrlsim_forward_loss_workspace_bytes(C.byref(model.hip.cdims), B, d.T))}
-    sizes.update({f"scope{s}": model.train_grad_workspace_bytes(B, model.SCOPES[s]) for s in range(top + 1)})
+    names = model.SCOPES + (model.DECODER_SCOPE,)
+    sizes.update({f"scope{s}": model.train_grad_workspace_bytes(B, names[s]) for s in range(top + 1)})
     ws = torch.empty(max(sizes.values()), dtype=torch.uint8, device=dev)
     sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
     lc = model.loss_cfg(True)
-    grads = torch.empty(model.train_grad_layout(model.SCOPES[top])[1], device=dev)
+    grads = torch.empty(model.train_grad_layout(names[top])[1], device=dev)
     rows3, rowsm = B * d.T * d.A * 3, B * ((d.P + d.A + 3) & ~3)
     bufs = {k: torch.empty(rowsm if k == "dMem" else rows3, d.D, device=dev) for ks in TAPS[:top + 1] for k in ks}
-    taps = [_lib.TrainTaps(**{k: bufs[k].data_ptr() for ks in TAPS[:s + 1] for k in ks}) for s in range(top + 1)]
+    taps = [_lib.TrainTaps(**{k: bufs[k].data_ptr() for ks in TAPS[:s + 1] for k in ks}) for s in range(min(top, 3) + 1)]
+    if top == 4:
+        layer_bufs = [torch.empty(rows3, d.D, device=dev) for _ in range(2 * (d.ND - 1))]
+        dtaps = _lib.DecoderTaps(dX=bufs["dX"].data_ptr(), dMem=bufs["dMem"].data_ptr())
+        for l in range(d.ND):
+            dtaps.dX0[l] = (bufs["dX0"] if l == d.ND - 1 else layer_bufs[2 * l]).data_ptr()
+            dtaps.x0_out[l] = (bufs["x0_out"] if l == d.ND - 1 else layer_bufs[2 * l + 1]).data_ptr()
     h, ctx = model.hip.handle, C.byref(cb.struct)
 
     def loss_only():
         _lib.check(lib.ctrlsim_forward_loss(h, B, d.T, ctx, None, C.byref(lc), ws.data_ptr(), sums.data_ptr(), None, None, st))
 
     def loss_grads(s):
+        if s == 4:
+            return lambda: _lib.check(lib.ctrlsim_forward_loss_grads_decoder(h, B, d.T, ctx, None, C.byref(lc), 1.0, ws.data_ptr(), sums.data_ptr(),
+                                                                             None, grads.data_ptr(), C.byref(dtaps), st))
         return lambda: _lib.check(lib.ctrlsim_forward_loss_grads(h, B, d.T, ctx, None, C.byref(lc), 1.0, s, ws.data_ptr(), sums.data_ptr(),
                                                                  None, grads.data_ptr(), C.byref(taps[s]), st))
 
@@ -88,9 +100,12 @@ def main():
         rows.append(row)
         print(json.dumps(row))
     med = {name: float(np.median([r[name] for r in rows])) for name, _ in routes}
-    names = [name for name, _ in routes]
-    print(json.dumps({"B": B, "token_rows": rows3, "memory_rows": rowsm, "medians_ms": med, "workspace_bytes": sizes,
-                      "added_ms": {f"{b[:-3]}_over_{a[:-3]}": med[b] - med[a] for a, b in zip(names, names[1:])}}))
+    order = [name for name, _ in routes]
+    out = {"B": B, "token_rows": rows3, "memory_rows": rowsm, "medians_ms": med, "workspace_bytes": sizes,
+           "added_ms": {f"{b[:-3]}_over_{a[:-3]}": med[b] - med[a] for a, b in zip(order, order[1:])}}
+    if top == 4 and d.ND > 1:
+        out["added_ms_per_earlier_layer"] = (med["scope4_ms"] - med["scope3_ms"]) / (d.ND - 1)
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
