@@ -11,8 +11,9 @@
 //
 // THE RECOMPUTE, per chunk of whole contexts (the ops' chunks: <= 8192 rows where a context has no more), in the ops' own arithmetic
 // (f32-input MFMA from the fp32 masters) and their own workspace carves, which the backward then overwrites:
-//   self:   Q | K | V = X0 Win^T + bin (hg_gemm.h);  O (sa_fwd_kernel);  X1 = LayerNorm(X0 + O Wo^T + bo)    dl_proj_ln_kernel
-//   cross:  K | V = Mem (Wk; Wv)^T + (bk; bv) once;  Q = X1 Wq^T + bq;  O (ag_fwd_kernel);  U = LayerNorm(X1 + O Wo^T + bo)
+//   self:   Q | K | V = X0 Win^T + bin;  O           (launch_self_attn_chunk_fwd);  X1 = LayerNorm(X0 + O Wo^T + bo)    dl_proj_ln_kernel
+//   cross:  K | V of Mem once;  Q = X1 Wq^T + bq;  O  (launch_attn_chunk_fwd);       U  = LayerNorm(X1 + O Wo^T + bo)
+// — steps 1 and 2 of the ops' own chunk loops, by the ops' own launchers (ag_tile.h's ag_fwd_kernel under either mask).
 // dl_proj_ln_kernel: the out-projection, the residual and the LayerNorm in one kernel — a workgroup owns 32 whole rows, a wave 64 of
 // their 256 columns in two accumulator tiles; the rows never leave the registers between the product and the norm, the row sums are
 // shuffles within a wave and one fixed-order add of the four waves' partials.  No atomics anywhere; nothing is read but the arguments;
@@ -114,10 +115,9 @@ int copy_out(float* dst, const float* src, size_t rows, hipStream_t st) {
 
 }  // namespace
 
-// B * 3TA * 768 (the self-attention op's Q | K | V rows) and B * Lk * 512 (the cross-attention op's K | V rows) below 2^31 floats
+// what the two attention ops accept, for contexts of 3 T A rows
 bool decoder_layer_grad_dims_ok(int B, int T, int A, int Lk, int F) {
-  return B >= 1 && T >= 1 && A >= 1 && Lk >= 1 && F >= 1 && 3L * T * A <= 0x7fffffffL / (3 * DM) &&
-         (long)B * 3 * T * A <= 0x7fffffffL / (3 * DM) && (long)B * Lk <= 0x7fffffffL / (2 * DM);
+  return F >= 1 && Lk >= 1 && self_attn_grad_dims_ok(B, T, A) && attn_grad_dims_ok(B, 3 * T * A, Lk);
 }
 
 // Workspace behind `base`: X1, U and the two gradients between the ops (dU, dX1) [B 3TA, 256], then the three ops' carves on top of
@@ -149,42 +149,31 @@ int launch_decoder_layer_grad(const float* X0, int ldx, const float* Mem, int ld
   const float* const* cw = tn + 6;      // multihead_attn: in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias; norm2.weight, .bias
   const float* const* sw = tn + 12;     // self_attn: the same; norm1.weight, norm1.bias
   const int L = 3 * T * A;
-  const long wsz = (long)DM * DM, rows = (long)B * L;
+  const long rows = (long)B * L;
   auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
   float *X1 = f(w.X1), *U = f(w.U), *dU = f(w.dU), *dX1 = f(w.dX1);
-  // ---- X1: the self-attention sublayer's output, in the self-attention op's chunk buffers
-  {
-    float *QKV = f(w.s.QKV), *O = f(w.s.O), *smax = f(w.s.stat), *slog = smax + (long)w.s.chunk_ctx * L * NHEAD;
-    for (int c0 = 0; c0 < B; c0 += w.s.chunk_ctx) {
-      const int nc = B - c0 < w.s.chunk_ctx ? B - c0 : w.s.chunk_ctx, nr = nc * L;
-      const long r0 = (long)c0 * L;
-      const float* Xc = X0 + r0 * ldx;
-      FG_CHK(hg_gemm_t<true, true, HG_EPI_PLAIN>(HgGemm{Xc, ldx, 1, sw[0], 1, DM, QKV, 3 * DM, 0, sw[1], nr, 3 * DM, DM, DM, 0}, st));
-      FG_CHK(launch_self_attn_fwd_stats(QKV, O, smax, slog, nc, L, A, mask_mode, st));
-      FG_CHK(proj_ln(O, sw[2], sw[3], Xc, ldx, sw[4], sw[5], X1 + r0 * DM, DM, nr, st));
-    }
+  // ---- X1: the self-attention sublayer's output, through the self-attention op's chunk buffers
+  for (int c0 = 0; c0 < B; c0 += w.s.chunk_ctx) {
+    const int nc = B - c0 < w.s.chunk_ctx ? B - c0 : w.s.chunk_ctx;
+    const long r0 = (long)c0 * L;
+    FG_CHK(launch_self_attn_chunk_fwd(X0, ldx, sw[0], sw[1], B, L, A, mask_mode, c0, ws, w.s, st));
+    FG_CHK(proj_ln(f(w.s.O), sw[2], sw[3], X0 + r0 * ldx, ldx, sw[4], sw[5], X1 + r0 * DM, DM, nc * L, st));
   }
-  // ---- U: the cross-attention sublayer's output, in the cross-attention op's buffers
-  {
-    float *KV = f(w.a.KV), *Q = f(w.a.Q), *O = f(w.a.O), *smax = f(w.a.stat), *slog = smax + (long)w.a.chunk_ctx * L * NHEAD;
-    FG_CHK(hg_gemm_t<true, true, HG_EPI_PLAIN>(HgGemm{Mem, ldm, 1, cw[0] + wsz, 1, DM, KV, 2 * DM, 0, cw[1] + DM, B * Lk, 2 * DM, DM, DM, 0}, st));
-    for (int c0 = 0; c0 < B; c0 += w.a.chunk_ctx) {
-      const int nc = B - c0 < w.a.chunk_ctx ? B - c0 : w.a.chunk_ctx, nr = nc * L;
-      const long r0 = (long)c0 * L;
-      const float* Xc = X1 + r0 * DM;
-      FG_CHK(hg_gemm_t<true, true, HG_EPI_PLAIN>(HgGemm{Xc, DM, 1, cw[0], 1, DM, Q, DM, 0, cw[1], nr, DM, DM, DM, 0}, st));
-      FG_CHK(launch_attn_fwd_stats(Q, KV, key_pad, O, smax, slog, nc, L, Lk, c0, st));
-      FG_CHK(proj_ln(O, cw[2], cw[3], Xc, DM, cw[4], cw[5], U + r0 * DM, DM, nr, st));
-    }
+  // ---- U: the cross-attention sublayer's output, through the cross-attention op's buffers
+  for (int c0 = 0; c0 < B; c0 += w.a.chunk_ctx) {
+    const int nc = B - c0 < w.a.chunk_ctx ? B - c0 : w.a.chunk_ctx;
+    const long r0 = (long)c0 * L;
+    FG_CHK(launch_attn_chunk_fwd(X1, DM, Mem, ldm, key_pad, cw[0], cw[1], B, L, Lk, c0, ws, w.a, st));
+    FG_CHK(proj_ln(f(w.a.O), cw[2], cw[3], X1 + r0 * DM, DM, cw[4], cw[5], U + r0 * DM, DM, nc * L, st));
   }
   FG_CHK(copy_out(x1_out, X1, (size_t)rows, st));
   FG_CHK(copy_out(u_out, U, (size_t)rows, st));
   // ---- the three ops, from the layer's output back; each op's dY is the dX of the op behind it
-  const long gF = 2L * DM * F + F + 3 * DM, gA = 4 * wsz + 6 * DM;
+  const long gF = 2L * DM * F + F + 3 * DM;
   FG_CHK(launch_ffn_block_grad(U, DM, dY, lddy, fw[0], fw[1], fw[2], fw[3], fw[4], fw[5], rows, F, ws, w.f, grads, dU, DM, st));
   FG_CHK(launch_attn_block_grad(X1, DM, Mem, ldm, key_pad, dU, DM, cw[0], cw[1], cw[2], cw[3], cw[4], cw[5], B, L, Lk, ws, w.a, grads + gF,
                                 dX1, DM, dMem, lddm, accumulate_dmem, st));
-  return launch_self_attn_block_grad(X0, ldx, dX1, DM, sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], B, T, A, mask_mode, ws, w.s, grads + gF + gA,
+  return launch_self_attn_block_grad(X0, ldx, dX1, DM, sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], B, T, A, mask_mode, ws, w.s, grads + gF + AG_NGRADS,
                                      dX0, lddx0, st);
 }
 

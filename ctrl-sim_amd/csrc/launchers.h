@@ -145,8 +145,10 @@ int launch_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, c
                            const float* Win, const float* bin, const float* Wo, const float* bo, const float* gamma, const float* beta,
                            int B, int Lq, int Lk, char* ws, const AttnGradWs& w, float* grads, float* dX, int lddx, float* dMem, int lddm,
                            int accumulate_dmem, hipStream_t st);     // accumulate_dmem: dMem += this call's, instead of =
-int launch_attn_fwd_stats(const float* Q, const float* KV, const unsigned char* key_pad, float* O, float* smax, float* slog, int nc, int Lq,
-                          int Lk, int c0, hipStream_t st);
+bool attn_grad_dims_ok(int B, int Lq, int Lk);
+// steps 1 and 2 of the chunk of contexts from c0 on, into the op's chunk buffers (K | V of all contexts before the first chunk's)
+int launch_attn_chunk_fwd(const float* X, int ldx, const float* Mem, int ldm, const unsigned char* key_pad, const float* Win, const float* bin,
+                          int B, int Lq, int Lk, int c0, char* ws, const AttnGradWs& w, hipStream_t st);
 
 // ---- self_attn_grad.hip: the backward of a decoder layer's self-attention sublayer under the multi-agent causal mask (contexts of 3 T A rows)
 struct SelfAttnGradWs { size_t QKV, dQKV, O, S, dS, stat, slab, part_ln, part_cs, bytes; int chunk_ctx; long nln, ncs; };
@@ -154,7 +156,9 @@ SelfAttnGradWs self_attn_grad_carve(size_t base, int B, int L);
 int launch_self_attn_block_grad(const float* X, int ldx, const float* dY, int lddy, const float* Win, const float* bin, const float* Wo,
                                 const float* bo, const float* gamma, const float* beta, int B, int T, int A, int mask_mode, char* ws,
                                 const SelfAttnGradWs& w, float* grads, float* dX, int lddx, hipStream_t st);
-int launch_self_attn_fwd_stats(const float* QKV, float* O, float* smax, float* slog, int nc, int L, int A, int mask_mode, hipStream_t st);
+bool self_attn_grad_dims_ok(int B, int T, int A);
+int launch_self_attn_chunk_fwd(const float* X, int ldx, const float* Win, const float* bin, int B, int L, int A, int mask_mode, int c0, char* ws,
+                               const SelfAttnGradWs& w, hipStream_t st);     // steps 1 and 2 of the chunk of contexts from c0 on
 
 // ---- decoder_layer_grad.hip: a whole decoder layer's backward from the rows that enter it (X1 and U recomputed, then the three ops above)
 struct DecLayerGradWs { size_t X1, U, dU, dX1, bytes; FfnGradWs f; AttnGradWs a; SelfAttnGradWs s; };
