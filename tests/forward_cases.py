@@ -15,6 +15,7 @@ token.  tests/test_forward_paths_host.py proves the equality with the truncated,
 LAYOUT.  A class (B_k, A_k) with A_k < d.A holds contexts of A_k - 1 live agents in the leading A_k slots of the reference layout: the last
 slot is a padded one, the representative of all padded slots (csrc/forward.hip: Shape).  A_k == d.A is the plain layout; its contexts have
 d.A - 1 live agents.  Logits rows come class after class, context after context, regular slot after regular slot."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -135,17 +136,24 @@ def oracle_context(tw, wtag, d, key, inp, dtype=torch.float32):
     return _ORACLE[ck]
 
 
-def _forward(tw, x, d, dtype):
+@contextlib.contextmanager
+def widened(dtype):
+    """model_oracle casts its inputs with .float(); in float64 the same plain-torch code runs with those casts widened (oracle/gen_golden.py
+    makes the float64 logits of tests/golden/model_trained.npz the same way).  float32: nothing changes."""
     if dtype == torch.float32:
-        return mo.forward(tw, x, d)
-    # model_oracle casts its inputs with .float(); in float64 the same plain-torch code runs with those casts widened (oracle/gen_golden.py
-    # makes the float64 logits of tests/golden/model_trained.npz the same way)
+        yield
+        return
     orig = torch.Tensor.float
     torch.Tensor.float = lambda self, *a, **k: self.double()
     try:
-        return mo.forward(tw, x, d)
+        yield
     finally:
         torch.Tensor.float = orig
+
+
+def _forward(tw, x, d, dtype):
+    with widened(dtype):
+        return mo.forward(tw, x, d)
 
 
 def oracle_logits(tw, wtag, recipe, dtype=torch.float32):
