@@ -1,7 +1,8 @@
-// The attention backward's core, stated once for the two ops that use it (attn_grad.hip under a key-padding mask, self_attn_grad.hip
-// under the multi-agent causal mask; decoder_layer_grad.hip drives both): the head-tile helpers, the three kernels as templates over a
-// MASK POLICY, and the host steps the two launchers share.  Internal linkage, like hg_gemm.h: one set of instantiations per including
-// file — ag_fwd_kernel / ag_dq_kernel / ag_dkv_kernel<AgPadMask> in attn_grad.hip, <SaCausalMask> in self_attn_grad.hip.
+// The attention backward's core, stated once for the ops that use it (attn_grad.hip and scene_attn_grad.hip under a key-padding mask,
+// self_attn_grad.hip under the multi-agent causal mask; decoder_layer_grad.hip and encoder_layer_grad.hip drive them): the head-tile
+// helpers, the three kernels as templates over a MASK POLICY, and the host steps the launchers share.  Internal linkage, like hg_gemm.h:
+// one set of instantiations per including file — ag_fwd_kernel / ag_dq_kernel / ag_dkv_kernel<AgPadMask> (ag_pad_mask.h) in attn_grad.hip
+// and scene_attn_grad.hip, <SaCausalMask> in self_attn_grad.hip.
 //
 // THE CORE.  One wave = a 32 x 32 tile of scores.  ag_fwd / ag_dq: a workgroup = 128 queries of one (context, head), the query on the
 // lane (S^T = K Q^T as attention.hip), so that max, sum, delta and the statistics are lane-local and the score registers are the B

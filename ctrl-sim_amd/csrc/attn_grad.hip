@@ -23,41 +23,17 @@
 // statistics of 2, recomputed here; the bk slice of the bias gradient is computed like the others (it is zero in exact arithmetic).
 //
 // THE ATTENTION CORE is ag_tile.h's (ag_fwd_kernel, ag_dq_kernel, ag_dkv_kernel: one wave = a 32 x 32 tile of scores, a key tile has one
-// owner) under AgPadMask below: every tile of a context is visited, a padded key and a key at or beyond Lk are excluded by index —
+// owner) under AgPadMask (ag_pad_mask.h): every tile of a context is visited, a padded key and a key at or beyond Lk are excluded by index —
 // their P is exactly 0, so their dK, dV and dMem rows are exactly 0.
 //
 // SUMS OVER ROWS as ffn_grad.hip (fg_reduce.h): slabs of 1024 rows added in slab order in float64, chunks in stream order; column sums
 // through partials and one fixed-order float64 reduction.  Identical bits from run to run, whatever the workspace held.
-#include "ag_tile.h"
+#include "ag_pad_mask.h"
 #include "../../include/ctrlsim.h"
 
 #define AG_KVROWS 8192           // memory rows per pass of dWk | dWv
 
 namespace {
-
-// The key-padding mask as ag_tile.h's policy.  pad [contexts of the launch, Lk] or null.  Under the query's lane (ag_fwd, ag_dq) a
-// masked key is a -inf beside the staged tile, 0 otherwise, ADDED to the score in ag_fwd (s + 0: a row maximum of -0 is stored as +0);
-// under the key's lane (ag_dkv) it is the lane's own flag.
-struct AgPadMask {
-  const unsigned char* pad;
-  bool kvalid;
-  static constexpr bool REVERSE = false;
-  struct KeyTile { float bias[64]; };
-  struct QueryTile {};
-  __device__ void set_query(int b, int, int Lk) { if (pad) pad += (long)b * Lk; }
-  __device__ void set_key(int b, int, int key, int Lk) { kvalid = key < Lk && !(pad && pad[(long)b * Lk + key]); }
-  __device__ int key_end(int, int, int Lk) const { return Lk; }
-  __device__ int first_query(int) const { return 0; }
-  __device__ bool beyond(int, int) const { return false; }
-  __device__ int band(int) const { return AG_NO_BAND; }
-  __device__ void stage_keys(KeyTile& t, int k0, int Lk, int tid) const {
-    if (tid < 64) t.bias[tid] = (k0 + tid < Lk && !(pad && pad[k0 + tid])) ? 0.f : -__builtin_inff();
-  }
-  __device__ void stage_queries(QueryTile&, int, int) const {}
-  __device__ float score(const KeyTile& t, float s, int jj) const { return s + t.bias[jj]; }
-  __device__ bool key_visible(const KeyTile& t, int jj) const { return t.bias[jj] == 0.f; }
-  __device__ bool query_visible(const QueryTile&, int) const { return kvalid; }
-};
 
 // the core's operands for the contexts from c0 on: Q, O, dO, dQ and the statistics are chunk-local, K | V, dK | dV and key_pad are not
 AgOperands operands(char* ws, const AttnGradWs& w, int c0, int Lq, int Lk) {
@@ -66,7 +42,6 @@ AgOperands operands(char* ws, const AttnGradWs& w, int c0, int Lq, int Lk) {
   float *KV = f(w.KV) + k0, *dKV = f(w.dKV) + k0, *smax = f(w.stat);
   return AgOperands{f(w.Q), KV, f(w.S), f(w.O), f(w.dQ), dKV, smax, smax + nstat, smax + 2 * nstat, DM, 2 * DM, Lq, Lk};
 }
-AgPadMask pad_mask(const unsigned char* key_pad, int c0, int Lk) { return AgPadMask{key_pad ? key_pad + (long)c0 * Lk : nullptr, false}; }
 
 }  // namespace
 
@@ -114,7 +89,7 @@ int launch_attn_chunk_fwd(const float* X, int ldx, const float* Mem, int ldm, co
     FG_CHK(hg_gemm_t<true, true, HG_EPI_PLAIN>(HgGemm{Mem, ldm, 1, Win + (long)DM * DM, 1, DM, KV, 2 * DM, 0, bin + DM, B * Lk, 2 * DM, DM, DM, 0}, st));
   FG_CHK(hg_gemm_t<true, true, HG_EPI_PLAIN>(HgGemm{X + (long)c0 * Lq * ldx, ldx, 1, Win, 1, DM, Q, DM, 0, bin, nc * Lq, DM, DM, DM, 0}, st));
   hipLaunchKernelGGL(ag_fwd_kernel<AgPadMask>, dim3((Lq + 127) / 128, NHEAD, nc), dim3(256), 0, st,
-                     operands(ws, w, c0, Lq, Lk), pad_mask(key_pad, c0, Lk));
+                     operands(ws, w, c0, Lq, Lk), ag_pad_mask(key_pad, c0, Lk));
   return ctrlsim_launch_status();
 }
 
@@ -145,8 +120,8 @@ int launch_attn_block_grad(const float* X, int ldx, const float* Mem, int ldm, c
     FG_CHK(ag_out_proj_bwd(Xc, ldx, dY + r0 * lddy, lddy, O, Wo, bo, gamma, S, dS, slab, g.Wo, nr, acc, pln, nln, st));
     // 7. delta, dQ      8. dK | dV of these contexts
     const AgOperands a = operands(ws, w, c0, Lq, Lk);
-    hipLaunchKernelGGL(ag_dq_kernel<AgPadMask>, dim3((Lq + 127) / 128, NHEAD, nc), dim3(256), 0, st, a, pad_mask(key_pad, c0, Lk));
-    hipLaunchKernelGGL(ag_dkv_kernel<AgPadMask>, dim3((Lk + 63) / 64, NHEAD, nc), dim3(256), 0, st, a, pad_mask(key_pad, c0, Lk));
+    hipLaunchKernelGGL(ag_dq_kernel<AgPadMask>, dim3((Lq + 127) / 128, NHEAD, nc), dim3(256), 0, st, a, ag_pad_mask(key_pad, c0, Lk));
+    hipLaunchKernelGGL(ag_dkv_kernel<AgPadMask>, dim3((Lk + 63) / 64, NHEAD, nc), dim3(256), 0, st, a, ag_pad_mask(key_pad, c0, Lk));
     // 9. dWq (+)= dQ^T X      10. dbq partials      11. dX = dS + dQ Wq
     FG_CHK(hg_gemm_t<false, false, HG_EPI_PLAIN>(HgGemm{dQ, 1, DM, Xc, ldx, 1, slab, DM, wsz, nullptr, DM, DM, nr, FG_KS, 0}, st));
     hipLaunchKernelGGL(fg_slab_add_kernel, dim3(nadd), dim3(256), 0, st, slab, nslab, wsz, g.Win, acc);

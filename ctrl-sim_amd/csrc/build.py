@@ -29,7 +29,8 @@ NO_PK = "-Xclang -target-feature -Xclang -packed-fp32-ops"
 COMMON = "-fno-slp-vectorize"
 SRCS = {"gemm": "", "attention": "", "sim": "-ffp-contract=off", "context": "-ffp-contract=off", "embed": NO_PK,
         "map_encoder": "", "sample": "", "metrics": "-ffp-contract=off", "rewards": "-ffp-contract=off", "replay": "-ffp-contract=off",
-        "dataset": "-ffp-contract=off", "window": "-ffp-contract=off", "head_grad": NO_PK, "ffn_grad": NO_PK, "attn_grad": NO_PK, "self_attn_grad": NO_PK, "decoder_layer_grad": NO_PK, "forward": "", "dispatch": "", "api": ""}
+        "dataset": "-ffp-contract=off", "window": "-ffp-contract=off", "head_grad": NO_PK, "ffn_grad": NO_PK, "attn_grad": NO_PK, "self_attn_grad": NO_PK, "decoder_layer_grad": NO_PK,
+        "scene_attn_grad": NO_PK, "encoder_layer_grad": NO_PK, "forward": "", "dispatch": "", "api": ""}
 OUT = os.path.join(HERE, "libctrlsim_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # CTRLSIM_VARIANT=<name> (tools only): a complete second library built with CTRLSIM_EXTRA_DEFS into its own object directory,
@@ -61,7 +62,7 @@ def compile_cmd(name, extra, obj):
 
 
 # objects without device code: an EMPTY disassembly is expected there and nowhere else (loss.hip's kernels exist in the two-plane build only)
-HOST_ONLY = ("dispatch", "api", "loss_s0")
+HOST_ONLY = ("dispatch", "api", "loss_s0", "encoder_layer_grad")
 
 
 def _llvm_tool(name):
@@ -126,7 +127,7 @@ def isa_guard(obj):
 
 
 def build(force=False, verbose=False):
-    deps = [os.path.join(HERE, h) for h in ("common.h", "split.h", "classes.h", "launchers.h", "split_launchers.inc", "hg_gemm.h", "fg_reduce.h", "ag_tile.h")]
+    deps = [os.path.join(HERE, h) for h in ("common.h", "split.h", "classes.h", "launchers.h", "split_launchers.inc", "hg_gemm.h", "fg_reduce.h", "ag_tile.h", "ag_pad_mask.h")]
     deps.append(os.path.join(HERE, "..", "..", "include", "ctrlsim.h"))
     objs = []
     procs = []

@@ -102,18 +102,19 @@ __global__ __launch_bounds__(256) void dl_proj_ln_kernel(const float* __restrict
   }
 }
 
-int proj_ln(const float* O, const float* Wo, const float* bo, const float* R, long ldr, const float* gamma, const float* beta, float* Y,
-            long ldy, int rows, hipStream_t st) {
-  hipLaunchKernelGGL(dl_proj_ln_kernel, dim3((rows + 31) / 32), dim3(256), 0, st, O, Wo, bo, R, ldr, gamma, beta, Y, ldy, rows);
-  return ctrlsim_launch_status();
-}
-
 int copy_out(float* dst, const float* src, size_t rows, hipStream_t st) {
   if (dst && hipMemcpyAsync(dst, src, rows * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
   return CTRLSIM_OK;
 }
 
 }  // namespace
+
+// dl_proj_ln_kernel for `rows` rows (launchers.h: encoder_layer_grad.hip's recompute calls it too)
+int launch_proj_ln(const float* O, const float* Wo, const float* bo, const float* R, long ldr, const float* gamma, const float* beta, float* Y,
+                   long ldy, int rows, hipStream_t st) {
+  hipLaunchKernelGGL(dl_proj_ln_kernel, dim3((rows + 31) / 32), dim3(256), 0, st, O, Wo, bo, R, ldr, gamma, beta, Y, ldy, rows);
+  return ctrlsim_launch_status();
+}
 
 // what the two attention ops accept, for contexts of 3 T A rows
 bool decoder_layer_grad_dims_ok(int B, int T, int A, int Lk, int F) {
@@ -157,14 +158,14 @@ int launch_decoder_layer_grad(const float* X0, int ldx, const float* Mem, int ld
     const int nc = B - c0 < w.s.chunk_ctx ? B - c0 : w.s.chunk_ctx;
     const long r0 = (long)c0 * L;
     FG_CHK(launch_self_attn_chunk_fwd(X0, ldx, sw[0], sw[1], B, L, A, mask_mode, c0, ws, w.s, st));
-    FG_CHK(proj_ln(f(w.s.O), sw[2], sw[3], X0 + r0 * ldx, ldx, sw[4], sw[5], X1 + r0 * DM, DM, nc * L, st));
+    FG_CHK(launch_proj_ln(f(w.s.O), sw[2], sw[3], X0 + r0 * ldx, ldx, sw[4], sw[5], X1 + r0 * DM, DM, nc * L, st));
   }
   // ---- U: the cross-attention sublayer's output, through the cross-attention op's buffers
   for (int c0 = 0; c0 < B; c0 += w.a.chunk_ctx) {
     const int nc = B - c0 < w.a.chunk_ctx ? B - c0 : w.a.chunk_ctx;
     const long r0 = (long)c0 * L;
     FG_CHK(launch_attn_chunk_fwd(X1, DM, Mem, ldm, key_pad, cw[0], cw[1], B, L, Lk, c0, ws, w.a, st));
-    FG_CHK(proj_ln(f(w.a.O), cw[2], cw[3], X1 + r0 * DM, DM, cw[4], cw[5], U + r0 * DM, DM, nc * L, st));
+    FG_CHK(launch_proj_ln(f(w.a.O), cw[2], cw[3], X1 + r0 * DM, DM, cw[4], cw[5], U + r0 * DM, DM, nc * L, st));
   }
   FG_CHK(copy_out(x1_out, X1, (size_t)rows, st));
   FG_CHK(copy_out(u_out, U, (size_t)rows, st));

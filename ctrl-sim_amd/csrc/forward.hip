@@ -603,7 +603,8 @@ int map_inputs(const ctrlsim_model* m, const Batch& bt, const Ws& w, hipStream_t
 }
 
 // map encoder + scene encoder + per-layer memory K/V (everything that only depends on the frame of the context)
-int scene_side(const ctrlsim_model* m, const Batch& bt, const Ws& w, float* dbg_seg_emb, hipStream_t st) {
+// e0_layers (the training entry of the encoder scope): e0_layers[i] (nullable) receives the scene rows that enter encoder layer i
+int scene_side(const ctrlsim_model* m, const Batch& bt, const Ws& w, float* dbg_seg_emb, hipStream_t st, float* const* e0_layers = nullptr) {
   const ctrlsim_dims& d = m->d;
   const int rM = (int)bt.rM, rP = (int)bt.rP;
   // ---- map encoder (map_encoder.py:34-53): rows of `src` 0..P-1 per context
@@ -641,6 +642,9 @@ int scene_side(const ctrlsim_model* m, const Batch& bt, const Ws& w, float* dbg_
   const bool mem_tails_done = d.ND + 1 <= 8;
   for (int i = 0; i < d.NE; ++i) {
     const EncLayer& Le = m->enc[i];
+    if (e0_layers && e0_layers[i] &&
+        hipMemcpyAsync(e0_layers[i], w.src, (size_t)rM * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return CTRLSIM_ELAUNCH;
     CHK(gemm_kv(bt, w, Le.qkv, w.src, w.eqkv, 3 * DM, 3 * DM, DM, w.img_enc, true, st, true));
     CHK(attention(bt, w, AttnCall{0, Q_SCENE, w.eqkv, 3 * DM, w.eqkv + DM, w.eqkv + 2 * DM, 3 * DM, w.img_enc, true, w.eatt, 0, 0, 0},
                   st));
@@ -842,6 +846,7 @@ struct FullReq {
   float* x0_store = nullptr;                                // ... and the rows that enter that layer (for ND == 1 the assembled tokens), copied
                                                             // before its first kernel
   float* const* x0_layers = nullptr;                        // every-token passes: x0_layers[i] (nullable) receives the rows that enter layer i
+  float* const* e0_layers = nullptr;                        // e0_layers[i] (nullable) receives the scene rows that enter ENCODER layer i
   const float** mem_seen = nullptr;                         // receive the addresses of the scene encoder's output rows and their key-padding
   const unsigned char** pad_seen = nullptr;                 // bytes in the workspace: written by the scene side, only read from there on
 };
@@ -866,7 +871,7 @@ int forward_full(const ctrlsim_model* m, int n, const int* Bk, const int* Ak, co
   // ---- token embeddings (encoder.py:95-153)
   CHK(embed_inputs(m, bt, w, Tq, true, st));
   CHK(assemble_tokens(m, bt, w, Tq, false, st));
-  CHK(scene_side(m, bt, w, rq.dbg_seg_emb, st));
+  CHK(scene_side(m, bt, w, rq.dbg_seg_emb, st, rq.e0_layers));
   const bool use_tbl = d.variant == 0 && presplit() && ctrlsim_option(OPT_ATTN_TBL) != 0;   // (own-return mask: in-kernel masks, like the baselines)
   if (use_tbl) CHK(build_mask_tables(bt, w, Tq, st));
   // ---- decoder (decoder.py:52): layers 0..ND-2 on all tokens
@@ -1147,11 +1152,12 @@ int copy_rows(float* dst, const float* src, size_t rows, hipStream_t st) {
 // enter the layer (X0) before its in_proj.  Mem and its padding bytes are read where the scene side left them: forward_full writes w.src /
 // w.src_pad in scene_side only, the decoder and the heads read them.
 // x0_layers / mem_seen / pad_seen (the all-layers entry below): the per-layer row stores of the forward, and where Mem and its padding
-// bytes lie in the workspace; the public entry passes none.
+// bytes lie in the workspace; the public entry passes none.  e0_layers (the encoder entry): the scene side's per-layer row stores.
 namespace {
 int loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving, const ctrlsim_loss_cfg* cfg,
                float loss_action_coef, int scope, void* workspace, double* sums, double* per_ctx, float* grads, const ctrlsim_train_taps& t,
-               float* const* x0_layers, const float** mem_seen, const unsigned char** pad_seen, hipStream_t st) {
+               float* const* x0_layers, const float** mem_seen, const unsigned char** pad_seen, hipStream_t st,
+               float* const* e0_layers = nullptr) {
   if (scope < 0 || scope > 3 || !grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
   if ((scope < 1 && (t.dU || t.u_out)) || (scope < 2 && (t.dX1 || t.dMem || t.x1_out || t.mem_out)) || (scope < 3 && (t.dX0 || t.x0_out)))
     return CTRLSIM_EINVAL;                                                        // a tap of a wider scope than the call's
@@ -1171,7 +1177,7 @@ int loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, cons
   float *dX = t.dX ? t.dX : at(scope >= 1, L.dX), *dU = t.dU ? t.dU : at(scope >= 2, L.dU), *dX1 = t.dX1 ? t.dX1 : at(scope >= 3, L.dX1);
   const float* Mem = nullptr;
   const unsigned char* pad = nullptr;
-  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = X0; rq.x0_layers = x0_layers;
+  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = X0; rq.x0_layers = x0_layers; rq.e0_layers = e0_layers;
   if (scope >= 2) { rq.mem_seen = &Mem; rq.pad_seen = &pad; }
   CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
   if (!X || (scope >= 2 && (!Mem || !pad))) return CTRLSIM_EINVAL;
@@ -1257,20 +1263,26 @@ extern "C" int64_t ctrlsim_decoder_grads_workspace_bytes(const ctrlsim_dims* d, 
   if (!d || B < 1 || Tq < 1 || !decoder_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
   return (int64_t)L.bytes;
 }
-extern "C" int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                                  const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
-                                                  double* per_ctx, float* grads, const ctrlsim_decoder_taps* taps, hipStream_t st) {
-  static const ctrlsim_decoder_taps none{};
-  const ctrlsim_decoder_taps& t = taps ? *taps : none;
-  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
+namespace {
+// what the decoder entry refuses, before anything runs
+bool decoder_grads_ok(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const ctrlsim_loss_cfg* cfg, const void* workspace,
+                      const double* sums, const float* grads, const ctrlsim_decoder_taps& t, DecoderLayout& L) {
+  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return false;
   const ctrlsim_dims& d = m->d;
-  DecoderLayout L;
-  if (!decoder_layout(d, B, Tq, L)) return CTRLSIM_EINVAL;
-  if (tok_variant(d.variant) != 0 || (d.variant != 0 && d.variant != 4)) return CTRLSIM_EINVAL;      // (scope 3's own refusal, before anything runs)
+  if (!decoder_layout(d, B, Tq, L)) return false;
+  if (tok_variant(d.variant) != 0 || (d.variant != 0 && d.variant != 4)) return false;      // (scope 3's own refusal, before anything runs)
   for (int l = d.ND; l < CTRLSIM_MAX_DECODER_LAYERS; ++l)
-    if (t.x0_out[l] || t.dX0[l]) return CTRLSIM_EINVAL;
+    if (t.x0_out[l] || t.dX0[l]) return false;
   for (int l = 0; l < d.ND - 1; ++l)
-    if (m->dec[l].ckv.w != m->dec[l].cq.w + (long)DM * DM || m->dec[l].ckv.b != m->dec[l].cq.b + DM) return CTRLSIM_EINVAL;
+    if (m->dec[l].ckv.w != m->dec[l].cq.w + (long)DM * DM || m->dec[l].ckv.b != m->dec[l].cq.b + DM) return false;
+  return true;
+}
+// The decoder entry behind its checks.  e0_layers / pad_seen (the encoder entry below): the scene side's per-layer row stores, and where
+// the scene rows' key-padding bytes lie in the workspace; the public decoder entry passes none.
+int decoder_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving, const ctrlsim_loss_cfg* cfg,
+                  float loss_action_coef, void* workspace, double* sums, double* per_ctx, float* grads, const ctrlsim_decoder_taps& t,
+                  const DecoderLayout& L, float* const* e0_layers, const unsigned char** pad_seen, hipStream_t st) {
+  const ctrlsim_dims& d = m->d;
   char* ws = static_cast<char*>(workspace);
   auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
   const int last = d.ND - 1;
@@ -1281,7 +1293,9 @@ extern "C" int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B,
   t3.dX0 = t.dX0[last] ? t.dX0[last] : last > 0 ? f(L.dX0) : nullptr;
   const float* Mem = nullptr;
   const unsigned char* pad = nullptr;
-  CHK(loss_grads(m, B, Tq, c, moving, cfg, loss_action_coef, 3, workspace, sums, per_ctx, grads, t3, last > 0 ? x0 : nullptr, &Mem, &pad, st));
+  CHK(loss_grads(m, B, Tq, c, moving, cfg, loss_action_coef, 3, workspace, sums, per_ctx, grads, t3, last > 0 ? x0 : nullptr, &Mem, &pad, st,
+                 e0_layers));
+  if (pad_seen) *pad_seen = pad;
   const float* dY = t3.dX0;
   float* g = grads + group_base(d, m->has_fut, 3);
   for (int l = last - 1; l >= 0; --l, g += layer_floats(d)) {
@@ -1293,6 +1307,109 @@ extern "C" int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B,
     CHK(launch_decoder_layer_grad(x0[l], DM, Mem, DM, pad, dY, DM, tn, B, Tq, d.A, L.t.M, d.F, d.variant == 4 ? 1 : 0, ws, L.w, g, dX0, DM, t.dMem,
                                   DM, 1, nullptr, nullptr, st));
     dY = dX0;
+  }
+  return CTRLSIM_OK;
+}
+}  // namespace
+extern "C" int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                                  const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
+                                                  double* per_ctx, float* grads, const ctrlsim_decoder_taps* taps, hipStream_t st) {
+  static const ctrlsim_decoder_taps none{};
+  const ctrlsim_decoder_taps& t = taps ? *taps : none;
+  DecoderLayout L;
+  if (!decoder_grads_ok(m, B, Tq, c, cfg, workspace, sums, grads, t, L)) return CTRLSIM_EINVAL;
+  return decoder_grads(m, B, Tq, c, moving, cfg, loss_action_coef, workspace, sums, per_ctx, grads, t, L, nullptr, nullptr, st);
+}
+
+// ---- training (e): every scene-encoder layer.  The decoder entry with the scene rows that enter each encoder layer copied by the
+// forward, then the layer op (csrc/encoder_layer_grad.hip) for l = NE-1 .. 0 on those rows: dY = dMem, then the dE0 of layer l + 1.
+namespace {
+const GradPart kEncParts[12] = {
+    {".linear1.weight", DM, 0}, {".linear1.bias", 1, 0}, {".linear2.weight", DM, 0}, {".linear2.bias", 0, DM}, {".norm2.weight", 0, DM},
+    {".norm2.bias", 0, DM}, {".self_attn.in_proj_weight", 0, 3L * DM * DM}, {".self_attn.in_proj_bias", 0, 3 * DM},
+    {".self_attn.out_proj.weight", 0, (long)DM * DM}, {".self_attn.out_proj.bias", 0, DM}, {".norm1.weight", 0, DM}, {".norm1.bias", 0, DM}};
+// the length of the decoder entry's buffer: scope 3's, then ND-1 layers of 18 tensors
+long decoder_grads_floats(const ctrlsim_dims& d, bool has_fut) { return group_base(d, has_fut, 3) + (d.ND - 1) * layer_floats(d); }
+long enc_layer_floats(const ctrlsim_dims& d) {
+  long o = 0;
+  for (const GradPart& p : kEncParts) o += p.perF * d.F + p.fixed;
+  return o;
+}
+// The workspace of the encoder entry: the decoder entry's, then the NE row buffers E0_l, a dMem (where the caller takes no tap), one dE0
+// buffer (a layer's dE0 overwrites its dY where the caller takes neither as a tap) and the layer op's carve
+struct EncoderLayout { DecoderLayout dl; size_t E0[CTRLSIM_MAX_ENCODER_LAYERS], dMem, dE0, bytes; int M; EncLayerGradWs w; };
+bool encoder_layout(const ctrlsim_dims& d, int B, int Tq, EncoderLayout& o) {
+  if (d.NE < 0 || d.NE > CTRLSIM_MAX_ENCODER_LAYERS || !decoder_layout(d, B, Tq, o.dl)) return false;
+  o.M = o.dl.t.M;
+  o.bytes = o.dl.bytes;
+  if (d.NE == 0) return true;
+  if (!encoder_layer_grad_dims_ok(B, o.M, d.F)) return false;
+  const size_t n = ((size_t)B * o.M * DM * sizeof(float) + 255) & ~size_t(255);
+  size_t off = (o.dl.bytes + 255) & ~size_t(255);
+  for (int l = 0; l < d.NE; ++l, off += n) o.E0[l] = off;
+  o.dMem = off; off += n;
+  o.dE0 = off; off += n;
+  o.w = encoder_layer_grad_carve(off, B, o.M, d.F);
+  o.bytes = o.w.bytes;
+  return true;
+}
+}  // namespace
+extern "C" int ctrlsim_encoder_grad_layout(const ctrlsim_dims* d, int has_future_states, int cap, const char** names, int64_t* offsets) {
+  static std::string store[12 * CTRLSIM_MAX_ENCODER_LAYERS];
+  if (!d || d->NE < 0 || d->NE > CTRLSIM_MAX_ENCODER_LAYERS) return CTRLSIM_EINVAL;
+  const int nd = ctrlsim_decoder_grad_layout(d, has_future_states, 0, nullptr, nullptr);
+  if (nd < 0) return nd;
+  const int n = nd + 12 * d->NE;
+  if ((names || offsets) && cap < n) return CTRLSIM_EINVAL;
+  if (names || offsets) ctrlsim_decoder_grad_layout(d, has_future_states, nd, names, offsets);
+  long o = decoder_grads_floats(*d, has_future_states != 0);
+  int i = nd;
+  for (int l = d->NE - 1; l >= 0; --l) {
+    const std::string pre = "encoder.transformer_encoder.layers." + std::to_string(l);
+    for (int j = 0; j < 12; o += kEncParts[j].perF * d->F + kEncParts[j].fixed, ++j, ++i) {
+      if (names) { store[i - nd] = pre + kEncParts[j].suffix; names[i] = store[i - nd].c_str(); }
+      if (offsets) offsets[i] = o;
+    }
+  }
+  if (offsets && cap > n) offsets[n] = o;              // (room for one more: the total)
+  return n;
+}
+extern "C" int64_t ctrlsim_encoder_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq) {
+  EncoderLayout L;
+  if (!d || B < 1 || Tq < 1 || !encoder_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
+  return (int64_t)L.bytes;
+}
+extern "C" int ctrlsim_forward_loss_grads_encoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                                  const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
+                                                  double* per_ctx, float* grads, const ctrlsim_encoder_taps* taps, hipStream_t st) {
+  static const ctrlsim_encoder_taps none{};
+  const ctrlsim_encoder_taps& t = taps ? *taps : none;
+  if (!m) return CTRLSIM_EINVAL;
+  const ctrlsim_dims& d = m->d;
+  EncoderLayout L;
+  if (!decoder_grads_ok(m, B, Tq, c, cfg, workspace, sums, grads, t.dec, L.dl) || !encoder_layout(d, B, Tq, L)) return CTRLSIM_EINVAL;
+  for (int l = d.NE; l < CTRLSIM_MAX_ENCODER_LAYERS; ++l)
+    if (t.e0_out[l] || t.dE0[l]) return CTRLSIM_EINVAL;
+  if (d.NE == 0) return decoder_grads(m, B, Tq, c, moving, cfg, loss_action_coef, workspace, sums, per_ctx, grads, t.dec, L.dl, nullptr, nullptr, st);
+  char* ws = static_cast<char*>(workspace);
+  auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
+  float* e0[CTRLSIM_MAX_ENCODER_LAYERS] = {};
+  for (int l = 0; l < d.NE; ++l) e0[l] = f(L.E0[l]);
+  ctrlsim_decoder_taps td = t.dec;
+  if (!td.dMem) td.dMem = f(L.dMem);
+  const unsigned char* pad = nullptr;
+  CHK(decoder_grads(m, B, Tq, c, moving, cfg, loss_action_coef, workspace, sums, per_ctx, grads, td, L.dl, e0, &pad, st));
+  if (!pad) return CTRLSIM_EINVAL;
+  const float* dY = td.dMem;
+  float* g = grads + decoder_grads_floats(d, m->has_fut);
+  const size_t rowsM = (size_t)B * L.M;
+  for (int l = d.NE - 1; l >= 0; --l, g += enc_layer_floats(d)) {
+    const EncLayer& Le = m->enc[l];
+    const float* tn[12] = {Le.lin1.w, Le.lin1.b, Le.lin2.w, Le.lin2.b, Le.n2.g, Le.n2.b, Le.qkv.w, Le.qkv.b, Le.out.w, Le.out.b, Le.n1.g, Le.n1.b};
+    CHK(copy_rows(t.e0_out[l], e0[l], rowsM, st));
+    float* dE0 = t.dE0[l] ? t.dE0[l] : l > 0 ? f(L.dE0) : nullptr;       // (layer 0's, untapped, is nobody's dY)
+    CHK(launch_encoder_layer_grad(e0[l], DM, pad, dY, DM, tn, B, L.M, d.F, ws, L.w, g, dE0, DM, nullptr, st));
+    dY = dE0;
   }
   return CTRLSIM_OK;
 }

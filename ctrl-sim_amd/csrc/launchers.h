@@ -168,6 +168,26 @@ int launch_decoder_layer_grad(const float* X0, int ldx, const float* Mem, int ld
                               const float* const* tensors, int B, int T, int A, int Lk, int F, int mask_mode, char* ws,
                               const DecLayerGradWs& w, float* grads, float* dX0, int lddx0, float* dMem, int lddm, int accumulate_dmem,
                               float* x1_out, float* u_out, hipStream_t st);
+// Y = LayerNorm(R + O Wo^T + bo; gamma, beta) for `rows` rows (dl_proj_ln_kernel): O [rows, 256] dense, R / Y with leading dimensions
+int launch_proj_ln(const float* O, const float* Wo, const float* bo, const float* R, long ldr, const float* gamma, const float* beta, float* Y,
+                   long ldy, int rows, hipStream_t st);
+
+// ---- scene_attn_grad.hip: the backward of a scene-encoder layer's self-attention sublayer — one source, key-padding mask; the
+// workspace is self_attn_grad.hip's carve (self_attn_grad_carve(base, B, L))
+bool scene_attn_grad_dims_ok(int B, int L);
+int launch_scene_attn_block_grad(const float* X, int ldx, const unsigned char* key_pad, const float* dY, int lddy, const float* Win,
+                                 const float* bin, const float* Wo, const float* bo, const float* gamma, const float* beta, int B, int L,
+                                 char* ws, const SelfAttnGradWs& w, float* grads, float* dX, int lddx, hipStream_t st);
+int launch_scene_attn_chunk_fwd(const float* X, int ldx, const unsigned char* key_pad, const float* Win, const float* bin, int B, int L, int c0,
+                                char* ws, const SelfAttnGradWs& w, hipStream_t st);     // steps 1 and 2 of the chunk of contexts from c0 on
+
+// ---- encoder_layer_grad.hip: a whole scene-encoder layer's backward from the rows that enter it (U recomputed, then the two ops)
+struct EncLayerGradWs { size_t U, dU, bytes; FfnGradWs f; SelfAttnGradWs s; };
+bool encoder_layer_grad_dims_ok(int B, int L, int F);
+EncLayerGradWs encoder_layer_grad_carve(size_t base, int B, int L, int F);
+int launch_encoder_layer_grad(const float* X0, int ldx, const unsigned char* key_pad, const float* dY, int lddy, const float* const* tensors,
+                              int B, int L, int F, char* ws, const EncLayerGradWs& w, float* grads, float* dX0, int lddx0, float* u_out,
+                              hipStream_t st);
 
 // ---- sim.hip
 int launch_sim_init(int S, int N, int E, const float* init_pose, const float* size, const float* edges, const unsigned char* exists, float* phys,

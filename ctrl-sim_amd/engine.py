@@ -82,6 +82,9 @@ class HipModel:
         sfx = _pack.TRAINABLE_FFN_SUFFIXES + _pack.TRAINABLE_CROSS_SUFFIXES + _pack.TRAINABLE_SELF_SUFFIXES
         self._early = {f"decoder.transformer_decoder.layers.{l}{x}": np.array(weights[f"decoder.transformer_decoder.layers.{l}{x}"], np.float32)
                        for l in range(self.dims.ND - 1) for x in sfx}
+        # ... and of the 12 tensors of every scene-encoder layer (update(..., encoder=True))
+        self._enc = {f"encoder.transformer_encoder.layers.{l}{x}": np.array(weights[f"encoder.transformer_encoder.layers.{l}{x}"], np.float32)
+                     for l in range(self.dims.NE) for x in _pack.TRAINABLE_ENCODER_SUFFIXES}
         self.split_fallback = False     # an engine of this model met non-finite values under f16x3: later split="auto" engines
                                         # (the policy surface opens one per scenario session) start on bf16x6 right away
 
@@ -91,7 +94,7 @@ class HipModel:
             raise RuntimeError(f"workspace query failed: {n}")
         return int(n)
 
-    def update(self, named_tensors, cross=False, self_attn=False, decoder=False):
+    def update(self, named_tensors, cross=False, self_attn=False, decoder=False, encoder=False):
         """New fp32 values for tensors of the MLP heads (state-dict names under pack.HEAD_PREFIXES) and of the last decoder layer's
         feed-forward block (its linear1, linear2 and norm3: pack.TRAINABLE_FFN_SUFFIXES) -> torch tensor / ndarray of the tensor's
         shape: written into the packed buffer at the existing offsets, and every packed image `pack.pack` derives from them (operand
@@ -105,10 +108,16 @@ class HipModel:
         out_proj and norm1: pack.TRAINABLE_SELF_SUFFIXES) and re-derives pack.self_images.
         decoder=True (the training scope "heads+decoder") takes all of that and the same 18 tensors of EVERY earlier decoder layer, and
         re-derives pack.ffn_images, pack.cross_images and pack.self_images of each layer it is given tensors of — every image the fused
-        kernels of the earlier layers read."""
+        kernels of the earlier layers read.
+        encoder=True (the training scope "heads+decoder+encoder") implies decoder=True and also takes the 12 tensors of every scene-encoder
+        layer (pack.TRAINABLE_ENCODER_SUFFIXES), re-deriving pack.encoder_images of each layer it is given tensors of."""
+        if encoder:
+            decoder = True
         if decoder:
             cross = self_attn = True
         early = self._early if decoder else {}
+        if encoder:
+            early = {**early, **self._enc}
         new = {}
         for k, v in named_tensors.items():
             master = (self._heads if k in self._heads else self._cross if cross and k in self._cross else
@@ -134,8 +143,11 @@ class HipModel:
         if any(k in self._self and k.endswith("weight") and ".self_attn." in k for k in new):
             layer = {k: new.get(k, v) for k, v in self._self.items() if k.endswith("weight") and ".self_attn." in k}
             images.update(_pack.self_images(self.dims, layer, self._offset))
-        for pre in sorted({".".join(k.split(".")[:4]) for k in new if k in early}):      # decoder.transformer_decoder.layers.{l}
+        for pre in sorted({".".join(k.split(".")[:4]) for k in new if k in early}):      # decoder.transformer_decoder.layers.{l} / encoder...
             layer = {k: new.get(k, v) for k, v in early.items() if k.startswith(pre + ".") and k.endswith("weight") and ".norm" not in k}
+            if pre.startswith("encoder."):
+                images.update(_pack.encoder_images(self.dims, layer, self._offset))
+                continue
             images.update(_pack.ffn_images(self.dims, layer, self._offset))
             images.update(_pack.cross_images(self.dims, layer, self._offset))
             images.update(_pack.self_images(self.dims, layer, self._offset))
@@ -145,7 +157,7 @@ class HipModel:
             self.flat[o:o + v.size].copy_(torch.from_numpy(v))
         for k, v in new.items():
             (self._heads if k in self._heads else self._cross if k in self._cross else self._self if k in self._self else
-             early if k in early else self._ffn)[k] = v
+             self._enc if k in self._enc else self._early if k in self._early else self._ffn)[k] = v
 
     def __del__(self):
         try:

@@ -18,7 +18,11 @@ scope 3 (csrc/self_attn_grad.hip) starts from `dX1` and returns `dX0`, the gradi
 `set_trainable("heads+decoder")` (CtRLSim.DECODER_SCOPE) trains every decoder layer: ctrlsim_forward_loss_grads_decoder does what scope 3
 does and then, for each earlier layer from the last but one down, recomputes the layer's inside from the rows that entered it and runs the
 three backward ops (csrc/decoder_layer_grad.hip); it returns `dX0` of every layer and `dMem` summed over all of them, the gradients the
-encoder's and the embeddings' backward — not built — would start from."""
+encoder's and the embeddings' backward start from.
+`set_trainable("heads+decoder+encoder")` (CtRLSim.ENCODER_SCOPE) also trains every scene-encoder layer: ctrlsim_forward_loss_grads_encoder
+does what the decoder entry does and then, from `dMem` back, recomputes each encoder layer's inside from the scene rows that entered it and
+runs the two backward ops (csrc/encoder_layer_grad.hip); it returns `dE0` of every encoder layer — `dE0[0]` is the gradient at the rows
+[polylines || initial states], where the map encoder's and the embeddings' backward — not built — would start."""
 from __future__ import annotations
 
 import numpy as np
@@ -255,7 +259,7 @@ class CtRLSim:
         ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
         assert ws.dtype == torch.uint8 and ws.numel() >= n
         head = (self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef)
-        if scope == self.DECODER_SCOPE:
+        if scope in (self.DECODER_SCOPE, self.ENCODER_SCOPE):
             assert X is None
             taps = {k: torch.empty(rowsm if k in ("dMem", "mem_out") else rows3, d.D, device=dev) for k in ("dX", "x_out", "dMem", "mem_out")
                     if k in want}
@@ -265,8 +269,18 @@ class CtRLSim:
                     taps[k] = [torch.empty(rows3, d.D, device=dev) for _ in range(d.ND)]
                     for l, t in enumerate(taps[k]):
                         getattr(ct, k)[l] = t.data_ptr()
-            _lib.check(lib.ctrlsim_forward_loss_grads_decoder(*head, ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), C.byref(ct), st),
-                       "forward_loss_grads_decoder")
+            if scope == self.ENCODER_SCOPE:
+                et = _lib.EncoderTaps(dec=ct)
+                for k in ("dE0", "e0_out"):
+                    if k in want:
+                        taps[k] = [torch.empty(rowsm, d.D, device=dev) for _ in range(d.NE)]
+                        for l, t in enumerate(taps[k]):
+                            getattr(et, k)[l] = t.data_ptr()
+                _lib.check(lib.ctrlsim_forward_loss_grads_encoder(*head, ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), C.byref(et),
+                                                                  st), "forward_loss_grads_encoder")
+            else:
+                _lib.check(lib.ctrlsim_forward_loss_grads_decoder(*head, ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), C.byref(ct),
+                                                                  st), "forward_loss_grads_decoder")
         elif X is None:
             ct = _lib.TrainTaps(**{k: t.data_ptr() for k, t in taps.items()})
             _lib.check(lib.ctrlsim_forward_loss_grads(*head, self.SCOPES.index(scope), ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(),
@@ -317,15 +331,17 @@ class CtRLSim:
     SCOPES = ("heads", "heads+ffn", "heads+ffn+cross", "heads+last_layer")
     # training (d): the heads and EVERY decoder layer (ctrlsim_forward_loss_grads_decoder); accepted wherever a scope name is taken
     DECODER_SCOPE = "heads+decoder"
+    # training (e): and EVERY scene-encoder layer (ctrlsim_forward_loss_grads_encoder); accepted wherever a scope name is taken
+    ENCODER_SCOPE = "heads+decoder+encoder"
 
     def set_trainable(self, scope="heads"):
         """What training_step / configure_optimizers / optimizer_step train: "heads" (the default: the three MLP heads), "heads+ffn"
         (the heads and linear1, linear2, norm3 of the last decoder layer), "heads+ffn+cross" (and that layer's cross-attention:
         multihead_attn.in_proj / out_proj and norm2) or "heads+last_layer" (and its self-attention: self_attn.in_proj / out_proj and
-        norm1 — the whole last decoder layer) or "heads+decoder" (and the 18 tensors of every earlier decoder layer).  Choose before
-        configure_optimizers."""
-        if scope not in self.SCOPES + (self.DECODER_SCOPE,):
-            raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES + (self.DECODER_SCOPE,)}")
+        norm1 — the whole last decoder layer) or "heads+decoder" (and the 18 tensors of every earlier decoder layer) or
+        "heads+decoder+encoder" (and the 12 tensors of every scene-encoder layer).  Choose before configure_optimizers."""
+        if scope not in self.SCOPES + (self.DECODER_SCOPE, self.ENCODER_SCOPE):
+            raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES + (self.DECODER_SCOPE, self.ENCODER_SCOPE)}")
         self._scope = scope
         return self
 
@@ -333,7 +349,9 @@ class CtRLSim:
         """head_grad_layout for a scope (ctrlsim_train_grad_layout): "heads" gives exactly head_grad_layout's answer, "heads+ffn" appends
         the six tensors of the last decoder layer's feed-forward block, "heads+ffn+cross" the six of its cross-attention sublayer behind
         them, "heads+last_layer" the six of its self-attention sublayer behind those; "heads+decoder" (ctrlsim_decoder_grad_layout)
-        behind those, for the layers ND-2 down to 0, each layer's 18 tensors in the same group order.  Needs no device."""
+        behind those, for the layers ND-2 down to 0, each layer's 18 tensors in the same group order; "heads+decoder+encoder"
+        (ctrlsim_encoder_grad_layout) behind those, for the encoder layers NE-1 down to 0, each layer's 12 tensors (the feed-forward
+        six, then the attention six).  Needs no device."""
         import ctypes as C
         from .. import _lib
         from ..engine import _dims_struct
@@ -343,9 +361,11 @@ class CtRLSim:
         cd = _dims_struct(self.dims)
         if scope == self.DECODER_SCOPE:
             query = lambda cap, names, offs: lib.ctrlsim_decoder_grad_layout(C.byref(cd), has_fut, cap, names, offs)
+        elif scope == self.ENCODER_SCOPE:
+            query = lambda cap, names, offs: lib.ctrlsim_encoder_grad_layout(C.byref(cd), has_fut, cap, names, offs)
         else:
             if scope not in self.SCOPES:
-                raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES + (self.DECODER_SCOPE,)}")
+                raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES + (self.DECODER_SCOPE, self.ENCODER_SCOPE)}")
             sc = self.SCOPES.index(scope)
             query = lambda cap, names, offs: lib.ctrlsim_train_grad_layout(C.byref(cd), has_fut, sc, cap, names, offs)
         n = query(0, None, None)
@@ -359,7 +379,8 @@ class CtRLSim:
         """state-dict name -> torch.nn.Parameter of the selected scope, in layout order: head_parameters() (the same objects), then under
         "heads+ffn" the six tensors of the last decoder layer's feed-forward block, under "heads+ffn+cross" the six of its cross-attention
         sublayer too, under "heads+last_layer" the six of its self-attention sublayer as well, under "heads+decoder" the 18 tensors of
-        every earlier decoder layer too (each created once)."""
+        every earlier decoder layer too, under "heads+decoder+encoder" the 12 tensors of every scene-encoder layer as well (each created
+        once)."""
         return self._parameters(self._scope)
 
     def train_grad_workspace_bytes(self, B, scope="heads+ffn"):
@@ -367,6 +388,8 @@ class CtRLSim:
         from .. import _lib
         if scope == self.DECODER_SCOPE:
             n = _lib.lib().ctrlsim_decoder_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T)
+        elif scope == self.ENCODER_SCOPE:
+            n = _lib.lib().ctrlsim_encoder_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T)
         else:
             n = _lib.lib().ctrlsim_train_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T, self.SCOPES.index(scope))
         if n < 0:
@@ -374,7 +397,7 @@ class CtRLSim:
         return int(n)
 
     def loss_and_train_grads_ctx(self, cb, moving, B, dX=False, dU=False, x_out=False, u_out=False, workspace=None, dX1=False, dMem=False,
-                                 x1_out=False, mem_out=False, scope=None, dX0=False, x0_out=False):
+                                 x1_out=False, mem_out=False, scope=None, dX0=False, x0_out=False, dE0=False, e0_out=False):
         """loss_and_head_grads_ctx for the scope "heads+ffn" (ctrlsim_forward_loss_grads, scope 1): one teacher-forced forward + loss + the
         gradients of the heads and of the last decoder layer's feed-forward block -> (sums, {state-dict name: gradient tensor} in
         train_grad_layout("heads+ffn") order, dX, dU, x_out, u_out), each of the last four [B*T*A*3, 256] or None: the gradient at the
@@ -389,14 +412,20 @@ class CtRLSim:
         Under "heads+decoder" (ctrlsim_forward_loss_grads_decoder) the gradients continue with the 18 tensors of each earlier layer and
         the tuple is (sums, gradients, dX, x_out, dMem, mem_out, dX0, x0_out): dMem summed over all ND layers; dX0 and x0_out LISTS of ND
         tensors, entry l the gradient at the rows that enter layer l and those rows (dX0[0]: the gradient at the assembled tokens).  The
-        intermediate taps of the last layer (dU, u_out, dX1, x1_out) do not exist in that scope."""
+        intermediate taps of the last layer (dU, u_out, dX1, x1_out) do not exist in that scope.
+        Under "heads+decoder+encoder" (ctrlsim_forward_loss_grads_encoder) the gradients continue with the 12 tensors of each encoder layer
+        and the tuple is the decoder scope's followed by (dE0, e0_out): LISTS of NE tensors [B*M, 256], entry l the gradient at the scene
+        rows that enter encoder layer l and those rows (dE0[0]: the gradient at [polylines || initial states]); they exist in that
+        scope only."""
         if scope is None:
             scope = self._scope if self._scope != "heads" else "heads+ffn"
-        if scope == self.DECODER_SCOPE:
+        if (dE0 or e0_out) and scope != self.ENCODER_SCOPE:
+            raise ValueError("dE0 and e0_out exist under the scope \"heads+decoder+encoder\" only")
+        if scope in (self.DECODER_SCOPE, self.ENCODER_SCOPE):
             if dU or u_out or dX1 or x1_out:
-                raise ValueError("dU, u_out, dX1 and x1_out do not exist under the scope \"heads+decoder\"")
-            order = ("dX", "x_out", "dMem", "mem_out", "dX0", "x0_out")
-            asked = dict(dX=dX, x_out=x_out, dMem=dMem, mem_out=mem_out, dX0=dX0, x0_out=x0_out)
+                raise ValueError(f"dU, u_out, dX1 and x1_out do not exist under the scope \"{scope}\"")
+            order = ("dX", "x_out", "dMem", "mem_out", "dX0", "x0_out") + (("dE0", "e0_out") if scope == self.ENCODER_SCOPE else ())
+            asked = dict(dX=dX, x_out=x_out, dMem=dMem, mem_out=mem_out, dX0=dX0, x0_out=x0_out, dE0=dE0, e0_out=e0_out)
             sums, named, taps = self._forward_loss_grads(cb, moving, B, scope, [k for k in order if asked[k]], workspace=workspace)
             return (sums, named) + tuple(taps.get(k) for k in order)
         if scope not in self.SCOPES[1:]:
@@ -478,8 +507,8 @@ class CtRLSim:
             scheduler.step()
         optimizer.zero_grad(set_to_none=True)
         new = {k: p.detach().cpu().numpy() for k, p in params.items()}
-        if self._scope == self.DECODER_SCOPE:
-            self.hip.update(new, decoder=True)
+        if self._scope in (self.DECODER_SCOPE, self.ENCODER_SCOPE):
+            self.hip.update(new, decoder=True, encoder=self._scope == self.ENCODER_SCOPE)
         else:
             self.hip.update(new, cross=self._scope in self.SCOPES[2:], self_attn=self._scope == "heads+last_layer")
         self.weights.update({k: v.copy() for k, v in new.items()})

@@ -334,6 +334,24 @@ def self_images(dims: Dims, w: dict, present) -> dict:
     return out
 
 
+# the 12 tensors of a scene-encoder layer (encoder.transformer_encoder.layers.{l}), in ctrlsim_encoder_layer_grad's order
+TRAINABLE_ENCODER_SUFFIXES = (".linear1.weight", ".linear1.bias", ".linear2.weight", ".linear2.bias", ".norm2.weight",
+                              ".norm2.bias") + TRAINABLE_SELF_SUFFIXES
+
+
+def encoder_images(dims: Dims, w: dict, present) -> dict:
+    """The packed images `pack` derives from a scene-encoder layer's weights, re-derived: `w` holds, under their state-dict names,
+    <layer>.self_attn.in_proj_weight, <layer>.self_attn.out_proj.weight, <layer>.linear1.weight and <layer>.linear2.weight.  ->
+    {image name: flat float32 array} for every image name in `present`: the operand planes of both splits of the four matrices, the
+    in_proj's 32-column row blocks, .ffn#w1p / .ffn#w2p of both splits and the ffn_planes_pre images of the layer (.ffn#wop from the
+    self-attention out-projection, .ffn#w1q).  The biases and the two norms have no image but their fp32 rows.  Raises the
+    FloatingPointError of the two-fp16-plane split when a value no longer fits an image that exists."""
+    layer = {k: v for k, v in w.items() if ".multihead_attn." not in k}      # (an encoder layer has none: ffn_images then takes self_attn's)
+    out = self_images(dims, layer, present)
+    out.update(ffn_images(dims, layer, present))
+    return out
+
+
 def pack(dims: Dims, w: dict):
     """-> (flat float32 ndarray, names list, offsets int64 ndarray in floats)."""
     allw = dict(w)

@@ -441,6 +441,63 @@ int64_t ctrlsim_decoder_grads_workspace_bytes(const ctrlsim_dims* dims, int B, i
 int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
                                        const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
                                        float* grads, const ctrlsim_decoder_taps* taps /* nullable */, hipStream_t stream);
+/* ---- training (e): the scene encoder's self-attention sublayer's backward (csrc/scene_attn_grad.hip) -----------------------------------
+ * The op.  Forward being differentiated, per context of L rows — ONE source: the context's own rows are queries, keys and values:
+ *   Q | K | V = X Win^T + bin                                           (in_proj_weight [768,256], in_proj_bias [768])
+ *   O = concat_h softmax_keys(Q_h K_h^T / sqrt(32)) V_h                 (keys with key_pad = 1 excluded; every key excluded: O = 0)
+ *   S = X + O Wo^T + bo,  Y = LayerNorm(S; gamma, beta)
+ * — the first sublayer of torch.nn.TransformerEncoderLayer (post-LN, src_key_padding_mask).  X, dY [B*L, 256] with leading dimensions
+ * >= 256 (floats); key_pad [B, L] bytes, 1 = ignore, NULL = no key padded.  grads: ONE flat float32 buffer d in_proj_weight [768,256],
+ * d in_proj_bias [768], d out_proj.weight [256,256], d out_proj.bias, dgamma, dbeta [256], back to back.  dX (nullable) [B*L, 256] = dS +
+ * dQ Wq + dK Wk + dV Wv; it MAY be dY itself with lddx == lddy.  Any other overlap of an output with an input is undefined.  A dX row of
+ * a padded key whose dY row is zero is exactly zero.  B or L < 1, B*L*768 >= 2^31, a leading dimension below 256 or a null pointer other
+ * than key_pad, dX: CTRLSIM_EINVAL, nothing launched.  The same function as ctrlsim_attn_block_grad(X, Mem = X) with dX + dMem added by
+ * the caller, built as the self-attention op's chunk-local pipeline (one in_proj product, one d in_proj product, one K = 768 product for
+ * dX; no K | V buffers of all contexts): nothing of a forward pass is read but X and key_pad; rows a chunk of whole contexts at a time
+ * (ctrlsim_scene_attn_block_grad_chunk_contexts: <= 8192 rows where a context has no more).  f32-input MFMA from the fp32 masters; no
+ * float atomics, sums in fixed orders: identical bits from run to run, whatever the workspace held. */
+int64_t ctrlsim_scene_attn_block_grad_workspace_bytes(int B, int L);
+int ctrlsim_scene_attn_block_grad_chunk_contexts(int B, int L);
+int ctrlsim_scene_attn_block_grad(const float* X, int ldx, const uint8_t* key_pad, const float* dY, int lddy, const float* in_proj_weight,
+                                  const float* in_proj_bias, const float* out_proj_weight, const float* out_proj_bias, const float* gamma,
+                                  const float* beta, int B, int L, void* workspace, float* grads, float* dX, int lddx, hipStream_t stream);
+/* ---- training (e): one whole scene-encoder layer's backward by recompute (csrc/encoder_layer_grad.hip) ------------------------------
+ * The op.  Forward being differentiated, per context of L rows: U = the sublayer above of X0 (norm1), Y = the feed-forward block of U
+ * (norm2) — torch.nn.TransformerEncoderLayer, post-LN, relu.  X0, dY [B*L, 256] with leading dimensions >= 256; key_pad [B, L] bytes or
+ * NULL.  tensors: a HOST array of the layer's 12 fp32 master tensors (device pointers), grads: ONE flat float32 buffer of their
+ * gradients, both in the decoder layer op's convention: the six feed-forward tensors (linear1.weight, linear1.bias, linear2.weight,
+ * linear2.bias, norm2.weight, norm2.bias), then the six of the attention (self_attn.in_proj_weight, in_proj_bias, out_proj.weight,
+ * out_proj.bias, norm1.weight, norm1.bias).  dX0 (nullable) [B*L, 256]: the gradient at X0; it MAY be dY itself with lddx0 == lddy.
+ * u_out (nullable) [B*L, 256] dense: U as the backward read it.  U is recomputed from X0 (the attention op's own chunk forward, then the
+ * out-projection + norm1), then the two ops run on (U, dY) and (X0, dU); the result equals, bit for bit, the two public ops called by
+ * hand on u_out.  A null pointer other than key_pad, dX0, u_out, a leading dimension below 256, B, L or F < 1, B*L*768 >= 2^31:
+ * CTRLSIM_EINVAL, nothing launched.  No float atomics, sums in fixed orders: identical bits from run to run, whatever the workspace held. */
+int64_t ctrlsim_encoder_layer_grad_workspace_bytes(int B, int L, int F);
+int ctrlsim_encoder_layer_grad(const float* X0, int ldx, const uint8_t* key_pad, const float* dY, int lddy,
+                               const float* const* tensors /* 12 fp32 masters */, int B, int L, int F, void* workspace, float* grads,
+                               float* dX0, int lddx0, float* u_out, hipStream_t stream);
+/* ---- training (e): forward, loss, then the gradients of the heads, EVERY decoder layer and EVERY scene-encoder layer -------------------
+ * ctrlsim_forward_loss_grads_encoder does everything ctrlsim_forward_loss_grads_decoder does — the same launches, with one more row copy
+ * per encoder layer: the scene rows that enter layer l (E0_l), before that layer's in_proj — and then, for l = NE-1 .. 0, the layer op
+ * above on (E0_l, the scene rows' key-padding bytes, dY), dY = dMem for the last layer and dE0[l + 1] otherwise.
+ * grads: the decoder entry's buffer, unchanged, as a prefix; then for l = NE-1 .. 0 the 12 tensors of
+ * encoder.transformer_encoder.layers.{l} in the layer op's order (ctrlsim_encoder_grad_layout: names, offsets and the total).
+ * Taps, each nullable: dec — the decoder entry's; e0_out[l] / dE0[l], l < NE: the rows that enter encoder layer l and the gradient there
+ * ([B*M, 256], M = (P + A + 3) & ~3).  dE0[0] is the gradient at the scene encoder's input rows [polylines || initial states]: rows of
+ * padded keys, the filler rows among them, are exactly zero.  On the same inputs the loss sums, the decoder prefix of grads, dX, every
+ * dX0[l] and dMem are bit for bit the decoder entry's; for NE == 0 the entry IS the decoder entry.  A model the decoder entry refuses,
+ * NE > CTRLSIM_MAX_ENCODER_LAYERS or a tap of a layer >= NE: CTRLSIM_EINVAL, nothing launched.  Workspace:
+ * ctrlsim_encoder_grads_workspace_bytes(dims, B, Tq): the decoder entry's, NE row buffers, a dMem, a dE0, the layer op's. */
+#define CTRLSIM_MAX_ENCODER_LAYERS 8
+typedef struct ctrlsim_encoder_taps {        /* every member nullable */
+  ctrlsim_decoder_taps dec;
+  float *e0_out[CTRLSIM_MAX_ENCODER_LAYERS], *dE0[CTRLSIM_MAX_ENCODER_LAYERS];
+} ctrlsim_encoder_taps;
+int ctrlsim_encoder_grad_layout(const ctrlsim_dims* dims, int has_future_states, int cap, const char** names, int64_t* offsets);
+int64_t ctrlsim_encoder_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq);
+int ctrlsim_forward_loss_grads_encoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                                       const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
+                                       float* grads, const ctrlsim_encoder_taps* taps /* nullable */, hipStream_t stream);
 /* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
  * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
  * scratch: ctrlsim_loss_scratch_bytes. */

@@ -1,0 +1,716 @@
+"""GPU tests of the scene encoder's backward: the single-source key-padded self-attention op (csrc/scene_attn_grad.hip:
+ctrlsim_scene_attn_block_grad), the encoder layer op by recompute (csrc/encoder_layer_grad.hip: ctrlsim_encoder_layer_grad) and
+ctrlsim_forward_loss_grads_encoder (heads + every decoder layer + every encoder layer), the latter under both operand splits of the
+forward.
+
+ACCURACY BOUND (profiles/encoder_grad_parity.md holds every measured ratio).  The form of tests/test_gpu_self_attn_grads.py (_check): for
+every tensor T, relative to max |T_f64| (Frobenius: to ||T_f64||),
+    e_hip = max |T_hip - T_f64|,   e_ref = max |T_torch_fp32_cpu - T_f64|   (tests/enc_layer_grad_ref.py in float64 / float32)
+and e_hip <= K_ENC max(e_ref, 2^-24), likewise in the Frobenius norm.  For the layer the float64 twin and the float32 yardstick use the
+ReLU on / off pattern of the evaluation under test (enc_layer_grad_ref.relu_pattern), as tests/test_gpu_decoder_grads.py does.
+
+AN INDEPENDENT YARDSTICK already in the tree: ctrlsim_attn_block_grad(X, Mem = X) with dX + dMem added on the host is the same function
+built another way (K | V of all contexts, separate query and memory products).  It is held to the same bound on the same inputs."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from ctrlsim_amd import spec, weights, _lib  # noqa: E402
+from ctrlsim_amd.models import CtRLSim  # noqa: E402
+import loss_ref  # noqa: E402
+import head_grad_ref as hgr  # noqa: E402
+import attn_grad_ref as agr  # noqa: E402
+import self_attn_grad_ref as sgr  # noqa: E402
+import layer_grad_ref as lgr  # noqa: E402
+import enc_layer_grad_ref as egr  # noqa: E402
+from gpu_utils import DEV  # noqa: E402
+from helpers import golden  # noqa: E402
+from test_gpu_self_attn_grads import (_check, _bits, _same, _data, _model_case, _mode_of, _split, SPLITS, MODEL_CASES, LOSS_REL, FLOOR,  # noqa: E402
+                                      FIXTURE_CAP, FIXTURE_BOUND)
+from test_gpu_attn_grads import _key_pad, _kw  # noqa: E402
+from test_gpu_decoder_grads import K_LAYER, _dev, _workspace, _rows  # noqa: E402
+
+assert K_LAYER == 6.0       # (the bound K_ENC is compared with in profiles/encoder_grad_parity.md)
+
+K_ENC = 11.0                # largest measured ratio 10.59 (the attention op at 3x12, one context with every key padded, in_proj_weight, max norm; the
+                            # cross op with Mem = X measures the same 10.59 there; the layer op: 3.19, through the model: 3.94 — case 1, f16x3;
+                            # profiles/encoder_grad_parity.md, which also says why this exceeds K_LAYER), rounded up to the next whole number
+STEP_LOSS_REL = LOSS_REL    # the existing form (tests/test_gpu_ffn_grads.py)
+ENC = CtRLSim.ENCODER_SCOPE
+# (B, L, F), key padding: smallest; odd sizes with a padded tail; a whole 64-key tile of scattered keys; one past a tile with the first 64
+# keys padded; one past a 128-query block; one context with every key padded; the model's own sizes; two chunks (36 + 1 contexts)
+SHAPES = [((1, 1, 8), "none"), ((2, 7, 33), "tail"), ((3, 64, 1024), "scattered"), ((1, 65, 64), "tile"), ((2, 129, 64), "tail"),
+          ((3, 12, 1024), "context"), ((1, 224, 1024), "tail"), ((37, 224, 64), "scattered")]
+_ids = lambda s: "x".join(map(str, s[0])) + "-" + s[1]
+
+
+@functools.lru_cache(maxsize=None)
+def _trained_like():
+    d = spec.Dims(spec.make_cfg())
+    w = weights.generate_trained_like(d, 0)
+    return [np.asarray(w[k], np.float32) for k in egr.names(d.NE - 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def _op_inputs(B, L, F, pad):
+    rs = np.random.RandomState(5 + L)
+    return egr.make_case(B, L, F, 41 + (L + F) % 19, _trained_like()) + (agr.make_pad(B, L, pad, rs),)
+
+
+@functools.lru_cache(maxsize=None)
+def _attn_refs(B, L, F, pad):
+    """float64 / float32 references of the attention op on one table shape (computed once, never written)."""
+    X, dY, W, kp = _op_inputs(B, L, F, pad)
+    return egr.attn_grads(X, kp, dY, W[6:12]), egr.attn_grads(X, kp, dY, W[6:12], dtype=torch.float32)
+
+
+def _views(grads, szs, shps):
+    out, o = [], 0
+    for sz, shp in zip(szs, shps):
+        out.append(grads[o:o + sz].view(shp))
+        o += sz
+    return out
+
+
+def _p(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _intact(Xd, dYd, Wd, X, dY, W, alias, outs):
+    assert torch.equal(Xd[:, :256].cpu(), torch.from_numpy(X.reshape(-1, 256)))                       # inputs intact
+    if not alias:
+        assert torch.equal(dYd[:, :256].cpu(), torch.from_numpy(dY.reshape(-1, 256)))
+    assert all(torch.equal(a.cpu(), torch.from_numpy(b)) for a, b in zip(Wd, W))
+    for t in outs + (Xd, dYd):
+        if t is not None and t.shape[1] > 256:
+            assert (t[:, 256:] == 7.0).all()                                   # nothing beyond the 256 columns of a row
+
+
+def _run_attn(X, pad, dY, W6, ldx=256, lddy=256, lddx=256, want_dX=True, fill=0, alias=False):
+    """ctrlsim_scene_attn_block_grad on host arrays -> ([six gradient tensors], dX or None) as device tensors.  fill: a byte, or "nan"."""
+    lib, st = _lib.lib(), _lib.stream_ptr()
+    B, L = X.shape[0], X.shape[1]
+    Xd, dYd = _dev(X, ldx), _dev(dY, lddy)
+    Wd = [torch.from_numpy(t).to(DEV) for t in W6]
+    pd = torch.from_numpy(pad).to(DEV) if pad is not None else None
+    ws = _workspace(int(lib.ctrlsim_scene_attn_block_grad_workspace_bytes(B, L)), fill)
+    grads = torch.full((sum(sgr.SIZES),), float("nan"), device=DEV)
+    dXd = dYd if alias else torch.full((B * L, lddx), 7.0, device=DEV) if want_dX else None
+    _lib.check(lib.ctrlsim_scene_attn_block_grad(Xd.data_ptr(), ldx, _p(pd), dYd.data_ptr(), lddy, *(t.data_ptr() for t in Wd), B, L,
+                                                 ws.data_ptr(), grads.data_ptr(), _p(dXd), lddy if alias else lddx, st), "scene_attn_block_grad")
+    torch.cuda.synchronize()
+    _intact(Xd, dYd, Wd, X, dY, W6, alias, (dXd,))
+    if pd is not None:
+        assert torch.equal(pd.cpu(), torch.from_numpy(pad))
+    return _views(grads, sgr.SIZES, sgr.SHAPE_OF), (dXd[:, :256].contiguous() if dXd is not None else None)
+
+
+def _run_cross(X, pad, dY, W6):
+    """The yardstick: ctrlsim_attn_block_grad(X, Mem = X) -> ([six gradient tensors], dX + dMem added on the host, float64)."""
+    lib, st = _lib.lib(), _lib.stream_ptr()
+    B, L = X.shape[0], X.shape[1]
+    Xd, dYd = _dev(X), _dev(dY)
+    Wd = [torch.from_numpy(t).to(DEV) for t in W6]
+    pd = torch.from_numpy(pad).to(DEV) if pad is not None else None
+    ws = _workspace(int(lib.ctrlsim_attn_block_grad_workspace_bytes(B, L, L)), 0)
+    grads = torch.full((sum(sgr.SIZES),), float("nan"), device=DEV)
+    dX, dMem = (torch.full((B * L, 256), 7.0, device=DEV) for _ in range(2))
+    _lib.check(lib.ctrlsim_attn_block_grad(Xd.data_ptr(), 256, Xd.data_ptr(), 256, _p(pd), dYd.data_ptr(), 256, *(t.data_ptr() for t in Wd), B, L, L,
+                                           ws.data_ptr(), grads.data_ptr(), dX.data_ptr(), 256, dMem.data_ptr(), 256, st), "attn_block_grad")
+    torch.cuda.synchronize()
+    return _views(grads, sgr.SIZES, sgr.SHAPE_OF), dX.cpu().numpy().astype(np.float64) + dMem.cpu().numpy().astype(np.float64)
+
+
+def _run_layer(X0, pad, dY, F, W12, ldx=256, lddy=256, lddx0=256, want_dX0=True, tap=True, fill=0, alias=False):
+    """ctrlsim_encoder_layer_grad on host arrays -> ([12 gradient tensors], dX0, u_out) as device tensors (None where not asked for)."""
+    lib, st = _lib.lib(), _lib.stream_ptr()
+    B, L = X0.shape[0], X0.shape[1]
+    Xd, dYd = _dev(X0, ldx), _dev(dY, lddy)
+    Wd = [torch.from_numpy(t).to(DEV) for t in W12]
+    ptrs = (ctypes.c_void_p * 12)(*(t.data_ptr() for t in Wd))
+    pd = torch.from_numpy(pad).to(DEV) if pad is not None else None
+    ws = _workspace(int(lib.ctrlsim_encoder_layer_grad_workspace_bytes(B, L, F)), fill)
+    grads = torch.full((sum(egr.sizes(F)),), float("nan"), device=DEV)
+    dXd = dYd if alias else torch.full((B * L, lddx0), 7.0, device=DEV) if want_dX0 else None
+    u = torch.full((B * L, 256), float("nan"), device=DEV) if tap else None
+    _lib.check(lib.ctrlsim_encoder_layer_grad(Xd.data_ptr(), ldx, _p(pd), dYd.data_ptr(), lddy, ptrs, B, L, F, ws.data_ptr(), grads.data_ptr(),
+                                              _p(dXd), lddy if alias else lddx0, _p(u), st), "encoder_layer_grad")
+    torch.cuda.synchronize()
+    _intact(Xd, dYd, Wd, X0, dY, W12, alias, (dXd,))
+    return _views(grads, egr.sizes(F), egr.shapes(F)), (dXd[:, :256].contiguous() if dXd is not None else None), u
+
+
+def _check_attn(got, dX, r64, r32, k=None):
+    k = K_ENC if k is None else k
+    worst = {}
+    for name, g, a, b in zip(egr.ATTN_PARTS, got, r64[0], r32[0]):
+        worst[name] = _check(name, g.cpu().numpy() if hasattr(g, "cpu") else g, a, b, k)
+    if dX is not None:
+        worst["dX"] = _check("dX", (dX.cpu().numpy() if hasattr(dX, "cpu") else dX).reshape(r64[1].shape), r64[1], r32[1], k)
+    top = max(worst, key=worst.get)
+    print(f"   worst ratio {worst[top]:.2f} ({top})")
+    return worst[top]
+
+
+def _layer_refs(X0, pad, dY, F, W, got, u_seen):
+    """The float64 twin and the float32 yardstick of one layer op call, under the ReLU pattern the call used (its u_out and db1)."""
+    on, nk = egr.relu_pattern(u_seen.cpu().numpy(), dY, W[0:6], got[1].cpu().numpy())
+    on = on.reshape(-1, F)
+    return egr.grads(X0, pad, dY, W, relu_on=on), egr.grads(X0, pad, dY, W, dtype=torch.float32, relu_on=on), nk
+
+
+def _check_layer(got, dX0, u, r64, r32, k=None):
+    k = K_ENC if k is None else k
+    worst = {}
+    for name, g, a, b in zip(egr.PARTS, got, r64[0], r32[0]):
+        worst[name] = _check(name, g.cpu().numpy(), a, b, k)
+    for name, g, i in (("dX0", dX0, 1), ("u_out", u, 2)):
+        if g is not None:
+            worst[name] = _check(name, g.cpu().numpy().reshape(r64[i].shape), r64[i], r32[i], k)
+    top = max(worst, key=worst.get)
+    print(f"   worst ratio {worst[top]:.2f} ({top})")
+    return worst[top]
+
+
+def _padded_rows_with_zero_dy(pad, dY):
+    return pad.astype(bool) & ~dY.any(axis=2)
+
+
+# ---- 1. the ops
+@pytest.mark.parametrize("shape", SHAPES, ids=_ids)
+def test_scene_attn_block_grad_matches_float64_autograd(shape):
+    """Every shape of the specification's table: all six tensors and dX against float64 autograd of the same fp32 inputs; dX rows of
+    padded keys whose dY row is zero are exactly zero."""
+    (B, L, F), padk = shape
+    X, dY, W, kp = _op_inputs(B, L, F, padk)
+    r64, r32 = _attn_refs(B, L, F, padk)
+    got, dX = _run_attn(X, kp, dY, W[6:12])
+    print(f"attention op B {B} L {L} pad {padk}")
+    _check_attn(got, dX, r64, r32)
+    if kp is not None:
+        dead = _padded_rows_with_zero_dy(kp, dY)
+        assert not dX.cpu().numpy().reshape(B, L, 256)[dead].any()
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=_ids)
+def test_the_cross_op_with_mem_equal_x_meets_the_same_bound(shape):
+    """The independent yardstick: ctrlsim_attn_block_grad(X, Mem = X), dX + dMem added on the host, and its six gradients, on the same
+    inputs against the same float64 reference under the same K_ENC."""
+    (B, L, F), padk = shape
+    X, dY, W, kp = _op_inputs(B, L, F, padk)
+    r64, r32 = _attn_refs(B, L, F, padk)
+    got, dX = _run_cross(X, kp, dY, W[6:12])
+    print(f"cross op with Mem = X, B {B} L {L} pad {padk}")
+    _check_attn(got, dX, r64, r32)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=_ids)
+def test_encoder_layer_grad_matches_float64_autograd(shape):
+    """Every shape of the table: all 12 tensors, dX0 and u_out against float64 autograd of the composed layer on the same fp32 inputs."""
+    (B, L, F), padk = shape
+    X0, dY, W, kp = _op_inputs(B, L, F, padk)
+    got, dX0, u = _run_layer(X0, kp, dY, F, W)
+    r64, r32, nk = _layer_refs(X0, kp, dY, F, W, got, u)
+    print(f"layer op B {B} L {L} F {F} pad {padk}: {nk} hidden elements on a ReLU kink")
+    _check_layer(got, dX0, u, r64, r32)
+    if kp is not None:
+        dead = _padded_rows_with_zero_dy(kp, dY)
+        assert not dX0.cpu().numpy().reshape(B, L, 256)[dead].any()
+
+
+def _two_ops_by_hand(X0, pad, dY, F, W, u):
+    """The two public ops on the layer op's own u_out -> ([12 tensors], dX0)."""
+    lib, st = _lib.lib(), _lib.stream_ptr()
+    B, L = X0.shape[0], X0.shape[1]
+    Xd, dYd = _dev(X0), _dev(dY)
+    Wd = [torch.from_numpy(t).to(DEV) for t in W]
+    pd = torch.from_numpy(pad).to(DEV) if pad is not None else None
+    wp = [t.data_ptr() for t in Wd]
+    sz = egr.sizes(F)
+    grads = torch.full((sum(sz),), float("nan"), device=DEV)
+    dU, dX0 = (torch.full((B * L, 256), 7.0, device=DEV) for _ in range(2))
+    ws = _workspace(int(lib.ctrlsim_ffn_block_grad_workspace_bytes(B * L, F)), 0x55)
+    _lib.check(lib.ctrlsim_ffn_block_grad(u.data_ptr(), 256, dYd.data_ptr(), 256, *wp[0:6], B * L, F, ws.data_ptr(), grads.data_ptr(),
+                                          dU.data_ptr(), 256, st), "ffn_block_grad")
+    ws = _workspace(int(lib.ctrlsim_scene_attn_block_grad_workspace_bytes(B, L)), 0x55)
+    _lib.check(lib.ctrlsim_scene_attn_block_grad(Xd.data_ptr(), 256, _p(pd), dU.data_ptr(), 256, *wp[6:12], B, L, ws.data_ptr(),
+                                                 grads.data_ptr() + 4 * sum(sz[:6]), dX0.data_ptr(), 256, st), "scene_attn_block_grad")
+    torch.cuda.synchronize()
+    return _views(grads, sz, egr.shapes(F)), dX0
+
+
+@pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[5], SHAPES[7]], ids=_ids)
+def test_encoder_layer_grad_equals_the_two_ops_by_hand(shape):
+    """Bit for bit: the 12 tensors and dX0 equal ctrlsim_ffn_block_grad and ctrlsim_scene_attn_block_grad called by hand on the op's own
+    u_out (odd sizes; a context with every key padded; two chunks)."""
+    (B, L, F), padk = shape
+    X0, dY, W, kp = _op_inputs(B, L, F, padk)
+    got, dX0, u = _run_layer(X0, kp, dY, F, W)
+    g2, dX0b = _two_ops_by_hand(X0, kp, dY, F, W, u)
+    assert _same(got, g2) and _same([dX0], [dX0b])
+
+
+@pytest.mark.parametrize("shape", [SHAPES[4], SHAPES[7]], ids=_ids)
+def test_identical_bits_whatever_the_workspace_held(shape):
+    (B, L, F), padk = shape
+    X0, dY, W, kp = _op_inputs(B, L, F, padk)
+    runs = [_run_layer(X0, kp, dY, F, W, fill=f) for f in (0x00, 0xFF, "nan")]
+    flat = lambda r: list(r[0]) + list(r[1:])
+    assert _same(flat(runs[0]), flat(runs[1])) and _same(flat(runs[0]), flat(runs[2]))
+    assert all(torch.isfinite(x).all() for x in flat(runs[0]))
+    runs = [_run_attn(X0, kp, dY, W[6:12], fill=f) for f in (0x00, 0xFF, "nan")]
+    flat = lambda r: list(r[0]) + [r[1]]
+    assert _same(flat(runs[0]), flat(runs[1])) and _same(flat(runs[0]), flat(runs[2]))
+
+
+def test_leading_dimensions_null_optionals_and_aliased_dx():
+    """Leading dimensions above 256 for X / dY / dX give the bits of the dense call with the sentinel columns intact; every optional
+    output NULL leaves the gradient tensors unchanged; dX = dY (same leading dimension) gives the same dX; key_pad is read."""
+    (B, L, F), padk = SHAPES[4]
+    X0, dY, W, kp = _op_inputs(B, L, F, padk)
+    dense = _run_attn(X0, kp, dY, W[6:12])
+    wide = _run_attn(X0, kp, dY, W[6:12], ldx=320, lddy=288, lddx=272)
+    assert _same(dense[0], wide[0]) and _same(dense[1:], wide[1:])
+    bare = _run_attn(X0, kp, dY, W[6:12], want_dX=False)
+    assert bare[1] is None and _same(dense[0], bare[0])
+    ali = _run_attn(X0, kp, dY, W[6:12], lddy=288, alias=True)
+    assert _same(dense[0], ali[0]) and _same(dense[1:], ali[1:])
+    nopad = _run_attn(X0, None, dY, W[6:12])
+    assert not _same(dense[0][:1], nopad[0][:1])
+    dense = _run_layer(X0, kp, dY, F, W)
+    wide = _run_layer(X0, kp, dY, F, W, ldx=320, lddy=288, lddx0=272)
+    assert _same(dense[0], wide[0]) and _same(dense[1:], wide[1:])
+    bare = _run_layer(X0, kp, dY, F, W, want_dX0=False, tap=False)
+    assert bare[1:] == (None, None) and _same(dense[0], bare[0])
+    ali = _run_layer(X0, kp, dY, F, W, lddy=288, alias=True)
+    assert _same(dense[0], ali[0]) and _same(dense[1:], ali[1:])
+
+
+def test_padded_rows_without_a_gradient_are_exactly_zero():
+    """dY zero on every padded row (the encoder's case: a padded scene row is a padded key of the decoder's cross-attention, so dMem is
+    zero there): dX of the attention op and dX0 of the layer op are exactly zero on those rows and on no other row; with every key of
+    a context padded and a non-zero dY, O = 0 and the rows still receive the residual's gradient."""
+    (B, L, F), _ = SHAPES[4]
+    X0, dY, W, _ = _op_inputs(B, L, F, "tail")
+    kp = agr.make_pad(B, L, "scattered", np.random.RandomState(2))
+    dY = dY.copy()
+    dY[~dY.any(axis=2)] = 1e-4                                              # only the padded rows are zero
+    dY[kp.astype(bool)] = 0.0
+    dead = kp.astype(bool)
+    _, dX = _run_attn(X0, kp, dY, W[6:12])
+    dX = dX.cpu().numpy().reshape(B, L, 256)
+    assert not dX[dead].any() and dX[~dead].any(axis=1).all()
+    _, dX0, _ = _run_layer(X0, kp, dY, F, W)
+    dX0 = dX0.cpu().numpy().reshape(B, L, 256)
+    assert not dX0[dead].any() and dX0[~dead].any(axis=1).all()
+    (B, L, F), _ = SHAPES[5]
+    X0, dY, W, kp = _op_inputs(B, L, F, "context")
+    dY = dY.copy()
+    dY[~dY.any(axis=2)] = 1e-4
+    got, dX = _run_attn(X0, kp, dY, W[6:12])
+    assert torch.isfinite(dX).all() and dX.view(B, L, 256)[B // 2].any(dim=1).all()
+    gW = got[0].cpu().numpy()
+    alone = _run_attn(X0[B // 2:B // 2 + 1], kp[B // 2:B // 2 + 1], dY[B // 2:B // 2 + 1], W[6:12])[0]
+    assert not alone[0].any() and not alone[1].any() and alone[3].any()      # no visible key: nothing reaches the in_proj; the out-proj bias is reached
+    assert gW.any()
+
+
+def test_ops_refuse_bad_arguments():
+    lib = _lib.lib()
+    x = torch.zeros(1024 * 256, device=DEV)
+    p = x.data_ptr()
+    #     X  ldx  pad   dY lddy Win bin Wo bo g  be B  L  ws grads dX   lddx stream
+    ok = [p, 256, None, p, 256, p, p, p, p, p, p, 1, 2, p, p, None, 256, None]
+    for i, v in ((0, None), (3, None), (5, None), (6, None), (7, None), (8, None), (9, None), (10, None), (13, None), (14, None), (1, 255),
+                 (4, 255), (11, 0), (12, 0), (11, -1), (11, 1 << 22)):
+        a = list(ok)
+        a[i] = v
+        assert lib.ctrlsim_scene_attn_block_grad(*a) == -22, i       # CTRLSIM_EINVAL
+    a = list(ok)
+    a[15], a[16] = p, 255
+    assert lib.ctrlsim_scene_attn_block_grad(*a) == -22
+    tn = (ctypes.c_void_p * 12)(*([p] * 12))
+    #     X0 ldx  pad   dY lddy tn  B  L  F  ws grads dX0  lddx0 u    stream
+    ok = [p, 256, None, p, 256, tn, 1, 2, 4, p, p, None, 256, None, None]
+    for i, v in ((0, None), (3, None), (5, None), (9, None), (10, None), (1, 255), (4, 255), (6, 0), (7, 0), (8, 0), (6, 1 << 22)):
+        a = list(ok)
+        a[i] = v
+        assert lib.ctrlsim_encoder_layer_grad(*a) == -22, i
+    for i in range(12):                                             # each of the 12 tensors is required
+        bad = (ctypes.c_void_p * 12)(*([p] * 12))
+        bad[i] = None
+        a = list(ok)
+        a[5] = bad
+        assert lib.ctrlsim_encoder_layer_grad(*a) == -22, i
+    a = list(ok)
+    a[11], a[12] = p, 255
+    assert lib.ctrlsim_encoder_layer_grad(*a) == -22
+    torch.cuda.synchronize()
+    assert not x.any()                                              # nothing launched: nothing written
+
+
+# ---- 2. through the model
+def _both(model, cb, moving, B):
+    """("heads+decoder" with every tap, "heads+decoder+encoder" with every tap) on the same contexts."""
+    kw = dict(dX=True, x_out=True, dMem=True, mem_out=True, dX0=True, x0_out=True)
+    rd = model.loss_and_train_grads_ctx(cb, moving, B, scope="heads+decoder", **kw)
+    re = model.loss_and_train_grads_ctx(cb, moving, B, scope=ENC, dE0=True, e0_out=True, **kw)
+    return rd, re
+
+
+def _enc_weights(w, l):
+    return [np.ascontiguousarray(np.asarray(w[k], np.float32)) for k in egr.names(l)]
+
+
+def _decoder_part_equal(rd, re, nd):
+    assert np.array_equal(_bits(rd[0]), _bits(re[0]))
+    assert list(re[1])[:len(rd[1])] == list(rd[1])
+    assert all(np.array_equal(_bits(rd[1][k]), _bits(re[1][k])) for k in rd[1])
+    assert _same(rd[2:6], re[2:6]) and _same(rd[6], re[6]) and _same(rd[7], re[7]) and len(re[6]) == len(re[7]) == nd
+
+
+@pytest.mark.parametrize("split", SPLITS)
+@pytest.mark.parametrize("case", MODEL_CASES)
+def test_forward_loss_grads_encoder_layer_by_layer(case, split):
+    """ctrlsim_forward_loss_grads_encoder on fixture cases 0, 1 (tiny) and 7 (full dims, B 2), NE 2.  Bit for bit: the loss sums, the
+    decoder prefix of the gradients, dX, x_out, dMem, mem_out, every dX0[l] and x0_out[l] equal "heads+decoder"; for l = NE-1 .. 0 the
+    layer's 12 tensors and dE0[l] equal ctrlsim_encoder_layer_grad on the entry's own e0_out[l], the scene rows' key padding and dMem /
+    dE0[l + 1].  Against float64: every layer on those taps, and the whole stack started from e0_out[0] with dMem at its output (the
+    twins use the ReLU pattern each layer's feed-forward block used on the device).  Rows of padded keys, the filler rows among them,
+    have a dE0 of exactly zero."""
+    lib = _lib.lib()
+    cfg, d, w, inp = _model_case(case)
+    _split(lib, split)
+    try:
+        model = CtRLSim(cfg, w, device=DEV)
+        cb, moving, B = model._ctx_of(_data(inp))
+        rd, re = _both(model, cb, moving, B)
+        _decoder_part_equal(rd, re, d.ND)
+        g, dMem, dE0, e0 = re[1], re[4], re[8], re[9]
+        assert list(g)[len(rd[1]):] == [n for l in range(d.NE - 1, -1, -1) for n in egr.names(l)] and len(dE0) == len(e0) == d.NE
+        kp = _key_pad(cfg, d, inp)
+        M = kp.shape[1]
+        on = [None] * d.NE
+        for l in range(d.NE - 1, -1, -1):
+            W = _enc_weights(w, l)
+            X0, dY = _rows(e0[l], B), _rows(dMem if l == d.NE - 1 else dE0[l + 1], B)
+            got, dX0, u = _run_layer(X0, kp, dY, d.F, W, fill=0xA5)
+            assert _same(got, [g[k] for k in egr.names(l)]) and _same([dX0], [dE0[l]]), l
+            r64, r32, nk = _layer_refs(X0, kp, dY, d.F, W, got, u)
+            on[l] = egr.relu_pattern(u.cpu().numpy(), dY, W[0:6], got[1].cpu().numpy())[0]
+            print(f"case {case} {split} encoder layer {l}: {nk} hidden elements on a ReLU kink")
+            _check_layer(got, dX0, u, r64, r32)
+            assert not dX0.cpu().numpy().reshape(B, M, 256)[kp.astype(bool)].any()
+        if d.NE > 1:                                                       # the rows that enter layer l + 1 are layer l's output
+            assert not torch.equal(e0[0], e0[1])
+        layers = [_enc_weights(w, l) for l in range(d.NE)]
+        E0, dOut = _rows(e0[0], B), _rows(dMem, B)
+        g64, dE64 = egr.stack_grads(E0, kp, dOut, layers, relu_on=on)
+        g32, dE32 = egr.stack_grads(E0, kp, dOut, layers, dtype=torch.float32, relu_on=on)
+        worst = {}
+        for l in range(d.NE - 1, -1, -1):
+            r = [_check(f"stack layer {l} {p}", g[k].cpu().numpy(), a, b, K_ENC) for p, k, a, b in zip(egr.PARTS, egr.names(l), g64[l], g32[l])]
+            r.append(_check(f"stack layer {l} dE0", _rows(dE0[l], B), dE64[l], dE32[l], K_ENC))
+            worst[l] = max(r)
+        print("   whole stack, worst ratio per layer, last first: " + " ".join(f"{l}: {worst[l]:.2f}" for l in sorted(worst, reverse=True)))
+    finally:
+        _split(lib, "f16x3")
+
+
+def _fixture_error(gf, P, k, got):
+    scale = np.abs(got).max()
+    if got.ndim == 1:
+        return np.abs(got - gf[P + "g_" + k]).max() / scale
+    rows = gf[P + "r_" + k]
+    err = np.abs(got[rows] - gf[P + "s_" + k]).max() / scale
+    nrm = abs(np.linalg.norm(got.astype(np.float64)) - float(gf[P + "n_" + k])) / float(gf[P + "n_" + k])
+    if P + "c_" + k in gf:
+        err = max(err, np.abs(got.astype(np.float64).sum(0) - gf[P + "c_" + k]).max() / (scale * got.shape[0]))
+    return max(err, nrm)
+
+
+@pytest.mark.parametrize("split", SPLITS)
+@pytest.mark.parametrize("case", MODEL_CASES)
+def test_encoder_gradients_against_the_references_recorded_ones(case, split):
+    """The gradients of every encoder layer and dE0[0] against what the unmodified reference's backward recorded
+    (tests/golden/encoder_grads.part*.npz: its trunk, its float32; tools/gen_golden_encoder_grads.py), with the deviation measure and
+    the bounds of tests/test_gpu_decoder_grads.py: FIXTURE_BOUND where no ReLU — of a head, of a decoder layer or of an encoder layer —
+    sits on a kink, FIXTURE_CAP where a layer's does, and where a HEAD element does, (ND + NE - l) FIXTURE_CAP for encoder layer l (the
+    changed row of dX is carried through every decoder layer and the encoder layers above l) and (ND + NE) FIXTURE_CAP for dE0[0].  The
+    reference has no filler rows: dE0[0] is compared on the P + A real rows of each context; the filler rows and the rows the
+    reference recorded as exactly zero (padded keys) are exactly zero here."""
+    import test_gpu_ffn_grads as tff
+    import test_gpu_decoder_grads as tdg
+    lib = _lib.lib()
+    cfg, d, w, inp = _model_case(case)
+    _split(lib, split)
+    try:
+        model = CtRLSim(cfg, w, device=DEV)
+        cb, moving, B = model._ctx_of(_data(inp))
+        r3, rdd = tdg._both(model, cb, moving, B)
+        re = model.loss_and_train_grads_ctx(cb, moving, B, scope=ENC, x_out=True, dMem=True, dE0=True, e0_out=True)
+        gf = golden("encoder_grads")
+        P = f"c{case}_"
+        worst, depth = {}, {}
+        for l in range(d.NE - 1, -1, -1):
+            for k in egr.names(l):
+                worst[k] = _fixture_error(gf, P, k, re[1][k].cpu().numpy())
+                depth[k] = d.ND + d.NE - l
+                print(f"   {k} against the reference's recorded gradient: {worst[k]:.3e} of max |T|")
+        M, PA = (d.P + d.A + 3) & ~3, d.P + d.A
+        dE0 = re[8][0].cpu().numpy().reshape(B, M, 256)
+        real = dE0[:, :PA].reshape(-1, 256)
+        worst["dE0"] = _fixture_error(gf, P, "dE0", real)
+        depth["dE0"] = d.ND + d.NE
+        print(f"   dE0[0] against the reference's recorded gradient: {worst['dE0']:.3e}")
+        assert not dE0[:, PA:].any() and not real[gf[P + "z_dE0"]].any()           # filler rows; the rows of padded keys
+        kp = _key_pad(cfg, d, inp)
+        nk = tdg._relu_patterns(model, w, d, B, r3, rdd, kp, _mode_of(d))[1]
+        for l in range(d.NE - 1, -1, -1):
+            W = _enc_weights(w, l)
+            dY = _rows(re[4] if l == d.NE - 1 else re[8][l + 1], B)
+            got, _, u = _run_layer(_rows(re[9][l], B), kp, dY, d.F, W, want_dX0=False)
+            nk += egr.relu_pattern(u.cpu().numpy(), dY, W[0:6], got[1].cpu().numpy())[1]
+        hk = tff._head_kinks(re[3].cpu().numpy(), w, d.VARIANT)
+        top = max(worst, key=worst.get)
+        bound = {k: depth[k] * FIXTURE_CAP if hk else FIXTURE_CAP if nk else FIXTURE_BOUND for k in worst}
+        print(f"   worst {worst[top]:.3e} ({top}; bound {bound[top]:.3e}: {hk} head and {nk} layer hidden elements on a ReLU kink)")
+        for k in worst:
+            assert worst[k] <= bound[k], (k, worst[k], bound[k])
+    finally:
+        _split(lib, "f16x3")
+
+
+def _cfg_ne(ne):
+    cfg = loss_ref.case_cfg(0)
+    cfg.model.num_transformer_encoder_layers = ne
+    return cfg
+
+
+@pytest.mark.parametrize("ne", [1, 0])
+def test_one_and_no_encoder_layer(ne):
+    """NE == 1: one layer op from dMem, dE0[0] at the encoder's input.  NE == 0: the entry IS the decoder entry — same layout, same
+    bits, empty tap lists."""
+    cfg = _cfg_ne(ne)
+    d = spec.Dims(cfg)
+    assert d.NE == ne
+    w = weights.generate(d, 5)
+    model = CtRLSim(cfg, w, device=DEV)
+    inp = loss_ref.make_inputs(d, 31, 2)
+    cb, moving, B = model._ctx_of(_data(inp))
+    rd, re = _both(model, cb, moving, B)
+    _decoder_part_equal(rd, re, d.ND)
+    assert len(re[8]) == len(re[9]) == ne
+    if ne == 0:
+        assert model.train_grad_layout(ENC) == model.train_grad_layout("heads+decoder")
+        assert model.train_grad_workspace_bytes(B, ENC) == model.train_grad_workspace_bytes(B, "heads+decoder")
+        return
+    kp = _key_pad(cfg, d, inp)
+    got, dX0, _ = _run_layer(_rows(re[9][0], B), kp, _rows(re[4], B), d.F, _enc_weights(w, 0))
+    assert _same(got, [re[1][k] for k in egr.names(0)]) and _same([dX0], [re[8][0]])
+    assert torch.isfinite(re[8][0]).all() and re[8][0].any()
+
+
+def test_encoder_entry_refuses_taps_beyond_the_layers_and_what_the_decoder_entry_refuses():
+    import ctypes as C
+    lib, st = _lib.lib(), _lib.stream_ptr()
+    cfg, d, w, inp = _model_case(0)
+    model = CtRLSim(cfg, w, device=DEV)
+    cb, moving, B = model._ctx_of(_data(inp))
+    n = model.train_grad_workspace_bytes(B, ENC)
+    assert n > model.train_grad_workspace_bytes(B, "heads+decoder")
+    ws = torch.empty(n, dtype=torch.uint8, device=DEV)
+    sums = torch.zeros(5, 2, dtype=torch.float64, device=DEV)
+    grads = torch.full((model.train_grad_layout(ENC)[1],), float("nan"), device=DEV)
+    buf = torch.full((B * d.T * d.A * 3, 256), 7.0, device=DEV)
+    lc = model.loss_cfg()
+
+    def call(m, taps, *, ws_=ws, sums_=sums, grads_=grads):
+        return lib.ctrlsim_forward_loss_grads_encoder(m.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(lc), 1.0, _lib.ptr(ws_),
+                                                      _lib.ptr(sums_), None, _lib.ptr(grads_), C.byref(taps) if taps is not None else None, st)
+    for k in ("e0_out", "dE0"):
+        t = _lib.EncoderTaps()
+        getattr(t, k)[d.NE] = buf.data_ptr()
+        assert call(model, t) == -22                                       # a tap of an encoder layer the model does not have
+    t = _lib.EncoderTaps()
+    t.dec.dX0[d.ND] = buf.data_ptr()
+    assert call(model, t) == -22                                           # ... of a decoder layer it does not have
+    assert call(model, None, ws_=None) == -22 and call(model, None, sums_=None) == -22 and call(model, None, grads_=None) == -22
+    torch.cuda.synchronize()
+    assert not sums.any() and torch.isnan(grads).all() and (buf == 7.0).all()      # nothing launched
+    assert call(model, None) == 0                                          # taps == NULL: no tap
+    torch.cuda.synchronize()
+    full = model.loss_and_train_grads_ctx(cb, moving, B, scope=ENC, dE0=True, e0_out=True, dMem=True)
+    assert np.array_equal(_bits(sums), _bits(full[0]))
+    assert np.array_equal(_bits(grads), _bits(torch.cat([g.reshape(-1) for g in full[1].values()])))      # the workspace's own dMem: the same bits
+    for other in (4, 5):                                                   # il, trajeglish: baseline token layouts, as the decoder entry
+        cfg2, d2, w2, inp2 = _model_case(other)
+        m2 = CtRLSim(cfg2, w2, device=DEV)
+        with pytest.raises(RuntimeError):
+            m2.loss_and_train_grads(_data(inp2), scope=ENC)
+
+
+# ---- 3. HipModel.update
+@pytest.mark.parametrize("split", SPLITS)
+def test_update_of_every_encoder_layer_equals_a_fresh_model_bit_for_bit(split):
+    lib = _lib.lib()
+    _split(lib, split)
+    try:
+        cfg, d, w, inp = _model_case(1)
+        data = _data(inp)
+        model = CtRLSim(cfg, dict(w), device=DEV)
+        before = model.hip.flat.clone()
+        rs = np.random.RandomState(4)
+        names = [n for l in range(d.NE) for n in egr.names(l)] + lgr.names(0) + hgr.head_names(w)
+        new = {k: (np.asarray(w[k]) * (1 + 0.05 * rs.standard_normal(np.asarray(w[k]).shape))).astype(np.float32) for k in names}
+        for flags in ({}, {"cross": True, "self_attn": True}, {"decoder": True}):
+            with pytest.raises(KeyError):
+                model.hip.update(new, **flags)                          # without encoder=True the encoder layers' names are refused
+            assert torch.equal(before.view(torch.int32), model.hip.flat.view(torch.int32))
+        model.hip.update(new, encoder=True)
+        fresh = CtRLSim(cfg, {**w, **new}, device=DEV)
+        assert torch.equal(model.hip.flat.view(torch.int32), fresh.hip.flat.view(torch.int32))          # every image re-derived in place
+        a, b = model.loss_sums(data)[0].cpu().numpy(), fresh.loss_sums(data)[0].cpu().numpy()
+        assert np.array_equal(a.view(np.int64), b.view(np.int64))
+        assert not np.array_equal(a.view(np.int64), CtRLSim(cfg, dict(w), device=DEV).loss_sums(data)[0].cpu().numpy().view(np.int64))
+        one = egr.names(0)[2]                                           # a later update of one tensor keeps the others' new values
+        newer = {one: (new[one] * np.float32(1.01)).astype(np.float32)}
+        model.hip.update(newer, encoder=True)
+        fresh = CtRLSim(cfg, {**w, **new, **newer}, device=DEV)
+        assert torch.equal(model.hip.flat.view(torch.int32), fresh.hip.flat.view(torch.int32))
+        snap = model.hip.flat.clone()
+        with pytest.raises(FloatingPointError):
+            model.hip.update({one: np.full_like(new[one], 1.0e6)}, encoder=True)
+        assert torch.equal(snap.view(torch.int32), model.hip.flat.view(torch.int32))                    # nothing written
+        with pytest.raises(KeyError):
+            model.hip.update({"encoder.map_encoder.norm1.weight": np.ones(256, np.float32)}, encoder=True)
+    finally:
+        _split(lib, "f16x3")
+
+
+# ---- 4. training loop
+def _twin(cfg, d, w, E0, X0, kp, mode, ctx, kw, steps):
+    """torch float64: the NE encoder layers on the (constant) scene rows E0, the ND decoder layers on the (constant) token rows X0 and
+    the encoder's output, and the heads; the same AdamW groups, clip and schedule."""
+    heads = hgr.head_names(w)
+    dn, en = [lgr.names(l) for l in range(d.ND)], [egr.names(l) for l in range(d.NE)]
+    every = heads + [k for l in range(d.ND - 1, -1, -1) for k in dn[l]] + [k for l in range(d.NE - 1, -1, -1) for k in en[l]]
+    params = {k: torch.nn.Parameter(torch.tensor(np.asarray(w[k]), dtype=torch.float64)) for k in every}
+    decay, no_decay = CtRLSim.param_groups(every)
+    tr = cfg.train
+    opt = torch.optim.AdamW([{"params": [params[k] for k in decay], "weight_decay": tr["weight_decay"]},
+                             {"params": [params[k] for k in no_decay], "weight_decay": 0.0}], lr=tr["lr"], weight_decay=tr["weight_decay"])
+    sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=CtRLSim.lr_lambda(tr))
+    vis, kpt = torch.from_numpy(sgr.mask(d.T, d.A, mode)), torch.from_numpy(kp.astype(bool))
+
+    def evaluate():
+        now = {k: p.detach().numpy() for k, p in params.items()}
+        dec, enc = [[now[k] for k in dn[l]] for l in range(d.ND)], [[now[k] for k in en[l]] for l in range(d.NE)]
+        with torch.no_grad():
+            Mem = egr.stack(torch.tensor(E0), kpt, [[torch.tensor(t) for t in W] for W in enc])[0]
+            Y = lgr.stack(torch.tensor(X0), Mem, kpt, vis, [[torch.tensor(t) for t in W] for W in dec])[0].numpy()
+        Mem = Mem.numpy()
+        _, final, g, dX = hgr.loss_and_grads(Y.reshape(-1, 256), {k: now[k] for k in heads}, ctx, **kw)
+        gl, _, dMem = lgr.stack_grads(X0, Mem, kp, dX.reshape(X0.shape), d.T, d.A, mode, dec)
+        ge, _ = egr.stack_grads(E0, kp, dMem, enc)
+        for l in range(d.ND):
+            g.update(zip(dn[l], gl[l]))
+        for l in range(d.NE):
+            g.update(zip(en[l], ge[l]))
+        return final, g
+
+    losses = []
+    for _ in range(steps):
+        final, g = evaluate()
+        losses.append(final)
+        for k, p in params.items():
+            p.grad = torch.from_numpy(g[k])
+        torch.nn.utils.clip_grad_norm_(list(params.values()), float(tr["gradient_clip_val"]))
+        opt.step()
+        sched.step()
+    return losses + [evaluate()[0]], {k: p.detach().numpy() for k, p in params.items()}
+
+
+def test_five_training_steps_in_the_encoder_scope_follow_the_float64_twin():
+    """training_step / optimizer_step five times on one fixed batch (case 0) with set_trainable("heads+decoder+encoder").  The map
+    encoder and the embeddings are frozen, so the encoder's input rows e0_out[0] and the decoder's x0_out[0] are constant (asserted bit
+    for bit) and a float64 twin can train the heads, all ND decoder layers and all NE encoder layers on them.  Loss per step within
+    STEP_LOSS_REL of the twin's; weights: every element within 2 sum_t lr_t sqrt(t) + 5 x 2^-24 |w| of the twin's (part (a) of
+    tests/test_gpu_ffn_grads.py's criterion), the bulk figure printed."""
+    cfg, d, w, inp = _model_case(0)
+    w0 = {k: np.array(v) for k, v in w.items()}
+    model = CtRLSim(cfg, dict(w0), device=DEV).set_trainable(ENC)
+    data = _data(inp)
+    first = model.loss_and_train_grads(data, x0_out=True, mem_out=True, e0_out=True)
+    x0, e0 = first[7][0], first[9][0]
+    heads = hgr.head_names(w)
+    every = heads + [k for l in range(d.ND - 1, -1, -1) for k in lgr.names(l)] + [k for l in range(d.NE - 1, -1, -1) for k in egr.names(l)]
+    assert list(model.trainable_parameters()) == every and len(every) == len(heads) + 18 * d.ND + 12 * d.NE
+    assert all(model.trainable_parameters()[k] is model.head_parameters()[k] for k in heads)
+    opt, sched = model.configure_optimizers()
+    got = []
+    for step in range(5):
+        got.append(model.training_step(data, step))
+        assert all(p.grad is not None for p in model.trainable_parameters().values())
+        model.optimizer_step(opt, sched)
+    out = model.loss_and_train_grads(data, x0_out=True, mem_out=True, e0_out=True)
+    got.append(model.final_loss(model.losses_from_sums(out[0].cpu().numpy())))
+    assert torch.equal(x0, out[7][0]) and torch.equal(e0, out[9][0])               # everything in front of the two stacks did not move
+    assert not torch.equal(first[5], out[5]) and not torch.equal(first[9][1], out[9][1])      # ... the encoder's layers did
+    B = np.asarray(inp["agent_states"]).shape[0]
+    want, w_twin = _twin(cfg, d, w0, _rows(e0, B).astype(np.float64), _rows(x0, B).astype(np.float64), _key_pad(cfg, d, inp), _mode_of(d),
+                         hgr.ctx_from_inputs(inp), _kw(cfg, d), 5)
+    print(f"loss per step {got}\n twin         {want}")
+    print(" relative     " + " ".join(f"{abs(a - b) / abs(b):.3e}" for a, b in zip(got, want)))
+    for a, b in zip(got, want):
+        assert abs(a - b) <= STEP_LOSS_REL * abs(b)
+    assert got[5] < got[0] and want[5] < want[0]
+    lrs = [cfg.train["lr"] * CtRLSim.lr_lambda(cfg.train)(t) for t in range(5)]
+    worst_case = 2 * sum(lr * np.sqrt(t + 1) for t, lr in enumerate(lrs))
+    bulk = 1e-3 * sum(lrs)
+    n_all = n_off = 0
+    drift = 0.0
+    hip = model.hip
+    for k, v in w_twin.items():
+        have = next(m for m in (hip._heads, hip._ffn, hip._cross, hip._self, hip._early, hip._enc) if k in m)[k].astype(np.float64)
+        assert np.array_equal(have, np.asarray(model.weights[k], np.float64))
+        diff = np.abs(have - v)
+        rnd = 5 * FLOOR * np.abs(v)
+        assert (diff <= worst_case + rnd).all(), k
+        n_all += diff.size
+        n_off += int((diff > bulk + rnd).sum())
+        drift = max(drift, float(diff.max()))
+        assert np.abs(v - np.asarray(w0[k], np.float64)).max() > 0, k
+    print(f"   weights after five steps: max |w - twin| {drift:.3e} (sum lr {sum(lrs):.1e}), {n_off} of {n_all} elements beyond the bulk tolerance")
+
+
+@pytest.mark.parametrize("scope", list(CtRLSim.SCOPES) + [CtRLSim.DECODER_SCOPE])
+def test_narrower_scopes_leave_the_encoder_alone(scope):
+    """Two training steps in each narrower scope, "heads+decoder" among them: the 12 tensors of every encoder layer and every image
+    derived from them keep their bits, and so do the scene rows the forward computes from them; something else moves."""
+    cfg, d, w, inp = _model_case(0)
+    model = CtRLSim(cfg, {k: np.array(v) for k, v in w.items()}, device=DEV).set_trainable(scope)
+    data = _data(inp)
+    enc = {n for l in range(d.NE) for n in egr.names(l)}
+    assert not enc & set(model.trainable_parameters())
+    off = model.hip._offset
+    order = sorted(off.values()) + [model.hip.flat.numel()]
+    mine = torch.zeros(model.hip.flat.numel(), dtype=torch.bool, device=DEV)
+    for name, o in off.items():
+        if name.startswith("encoder.transformer_encoder.layers."):
+            mine[o:order[order.index(o) + 1]] = True
+    assert int(mine.sum()) > d.NE * sum(egr.sizes(d.F))
+    before = model.hip.flat.clone()
+    mem0 = model.loss_and_train_grads(data, mem_out=True, scope="heads+decoder")[5]
+    opt, sched = model.configure_optimizers()
+    for step in range(2):
+        model.training_step(data, step)
+        model.optimizer_step(opt, sched)
+    assert torch.equal(before.view(torch.int32)[mine], model.hip.flat.view(torch.int32)[mine])
+    assert not torch.equal(before.view(torch.int32)[~mine], model.hip.flat.view(torch.int32)[~mine])
+    assert torch.equal(mem0, model.loss_and_train_grads(data, mem_out=True, scope="heads+decoder")[5])

@@ -6,10 +6,13 @@ measurement, all routes warmed and ALTERNATING in one process, three rounds; pri
 differences between neighbouring scopes and the workspace bytes.  Recorded in profiles/train_grad_rate.md, not gated.
 Scope 4 is "heads+decoder" (ctrlsim_forward_loss_grads_decoder: scope 3, then every earlier decoder layer by recompute), with the taps
 dX, dMem and dX0 / x0_out of every layer; its difference to scope 3, divided by ND - 1, is the added time per earlier layer.
+Scope 5 is "heads+decoder+encoder" (ctrlsim_forward_loss_grads_encoder: scope 4, then every scene-encoder layer by recompute), with
+scope 4's taps and dE0 / e0_out of every encoder layer; a run that reaches it also writes profiles/encoder_grad_rate.md: the call's time and
+workspace against "heads+decoder" at the same B, from this run's medians.  A record, not a gate.
 `trace SCOPE`: `reps` calls at that scope only, nothing timed — the run to put under a kernel trace (the difference of two scopes'
 per-kernel tables is what the wider one's backward adds).
 
-    python tools/train_grad_rate.py [B=64] [reps=10] [scope=4 | trace SCOPE]
+    python tools/train_grad_rate.py [B=64] [reps=10] [scope=4 | 5 | trace SCOPE]
 """
 import ctypes as C
 import json
@@ -45,7 +48,7 @@ def main():
     inp = {k: np.concatenate([v] * ((B + len(v) - 1) // len(v)))[:B] for k, v in base.items()}
     cb = ctx_from_reference_layout(d, inp, d.T, dev)
     sizes = {"forward_loss": int(lib.ctrlsim_forward_loss_workspace_bytes(C.byref(model.hip.cdims), B, d.T))}
-    names = model.SCOPES + (model.DECODER_SCOPE,)
+    names = model.SCOPES + (model.DECODER_SCOPE, model.ENCODER_SCOPE)
     sizes.update({f"scope{s}": model.train_grad_workspace_bytes(B, names[s]) for s in range(top + 1)})
     ws = torch.empty(max(sizes.values()), dtype=torch.uint8, device=dev)
     sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
@@ -54,18 +57,26 @@ def main():
     rows3, rowsm = B * d.T * d.A * 3, B * ((d.P + d.A + 3) & ~3)
     bufs = {k: torch.empty(rowsm if k == "dMem" else rows3, d.D, device=dev) for ks in TAPS[:top + 1] for k in ks}
     taps = [_lib.TrainTaps(**{k: bufs[k].data_ptr() for ks in TAPS[:s + 1] for k in ks}) for s in range(min(top, 3) + 1)]
-    if top == 4:
+    if top >= 4:
         layer_bufs = [torch.empty(rows3, d.D, device=dev) for _ in range(2 * (d.ND - 1))]
         dtaps = _lib.DecoderTaps(dX=bufs["dX"].data_ptr(), dMem=bufs["dMem"].data_ptr())
         for l in range(d.ND):
             dtaps.dX0[l] = (bufs["dX0"] if l == d.ND - 1 else layer_bufs[2 * l]).data_ptr()
             dtaps.x0_out[l] = (bufs["x0_out"] if l == d.ND - 1 else layer_bufs[2 * l + 1]).data_ptr()
+    if top == 5:
+        enc_bufs = [torch.empty(rowsm, d.D, device=dev) for _ in range(2 * d.NE)]
+        etaps = _lib.EncoderTaps(dec=dtaps)
+        for l in range(d.NE):
+            etaps.dE0[l], etaps.e0_out[l] = enc_bufs[2 * l].data_ptr(), enc_bufs[2 * l + 1].data_ptr()
     h, ctx = model.hip.handle, C.byref(cb.struct)
 
     def loss_only():
         _lib.check(lib.ctrlsim_forward_loss(h, B, d.T, ctx, None, C.byref(lc), ws.data_ptr(), sums.data_ptr(), None, None, st))
 
     def loss_grads(s):
+        if s == 5:
+            return lambda: _lib.check(lib.ctrlsim_forward_loss_grads_encoder(h, B, d.T, ctx, None, C.byref(lc), 1.0, ws.data_ptr(), sums.data_ptr(),
+                                                                             None, grads.data_ptr(), C.byref(etaps), st))
         if s == 4:
             return lambda: _lib.check(lib.ctrlsim_forward_loss_grads_decoder(h, B, d.T, ctx, None, C.byref(lc), 1.0, ws.data_ptr(), sums.data_ptr(),
                                                                              None, grads.data_ptr(), C.byref(dtaps), st))
@@ -103,9 +114,29 @@ def main():
     order = [name for name, _ in routes]
     out = {"B": B, "token_rows": rows3, "memory_rows": rowsm, "medians_ms": med, "workspace_bytes": sizes,
            "added_ms": {f"{b[:-3]}_over_{a[:-3]}": med[b] - med[a] for a, b in zip(order, order[1:])}}
-    if top == 4 and d.ND > 1:
+    if top >= 4 and d.ND > 1:
         out["added_ms_per_earlier_layer"] = (med["scope4_ms"] - med["scope3_ms"]) / (d.ND - 1)
+    if top == 5:
+        out["added_ms_per_encoder_layer"] = (med["scope5_ms"] - med["scope4_ms"]) / max(d.NE, 1)
+        write_encoder_record(out, d, reps)
     print(json.dumps(out))
+
+
+def write_encoder_record(out, d, reps):
+    med, sz = out["medians_ms"], out["workspace_bytes"]
+    lines = ["# Training (e): the encoder scope's call against \"heads+decoder\"", "",
+             f"`python tools/train_grad_rate.py {out['B']} {reps} 5` on one MI355X: trained-like weights, full-size windows, B = {out['B']}",
+             f"({out['token_rows']} token rows, {out['memory_rows']} scene rows, ND = {d.ND}, NE = {d.NE}).  Medians of three rounds of {reps} calls,",
+             "all routes warmed and alternating in one process; both scopes measured in the same run.  A record, not a gate.", "",
+             "| call | ms | workspace bytes |", "|---|---|---|",
+             f"| ctrlsim_forward_loss_grads_decoder (\"heads+decoder\") | {med['scope4_ms']:.3f} | {sz['scope4']} |",
+             f"| ctrlsim_forward_loss_grads_encoder (\"heads+decoder+encoder\") | {med['scope5_ms']:.3f} | {sz['scope5']} |", "",
+             f"The encoder layers add {med['scope5_ms'] - med['scope4_ms']:.3f} ms ({out['added_ms_per_encoder_layer']:.3f} ms per layer, "
+             f"{100 * (med['scope5_ms'] / med['scope4_ms'] - 1):.2f} % of the decoder scope's call) and "
+             f"{sz['scope5'] - sz['scope4']} bytes of workspace ({100 * (sz['scope5'] / sz['scope4'] - 1):.2f} %).", "",
+             "```", json.dumps(out), "```", ""]
+    with open(os.path.join(ROOT, "profiles", "encoder_grad_rate.md"), "w") as f:
+        f.write("\n".join(lines))
 
 
 if __name__ == "__main__":
