@@ -56,17 +56,8 @@ class LossCfg(C.Structure):
 
 class TrainTaps(C.Structure):
     """ctrlsim_train_taps (include/ctrlsim.h): the optional outputs of ctrlsim_forward_loss_grads, device pointers, each NULL by default."""
-    _fields_ = [(k, C.c_void_p) for k in ("dX", "x_out", "dU", "u_out", "dX1", "dMem", "x1_out", "mem_out", "dX0", "x0_out")]
-
-
-class DecoderTaps(C.Structure):
-    """ctrlsim_decoder_taps (include/ctrlsim.h): the optional outputs of ctrlsim_forward_loss_grads_decoder, device pointers, each NULL by default."""
-    _fields_ = [("x0_out", C.c_void_p * 8), ("dX0", C.c_void_p * 8)] + [(k, C.c_void_p) for k in ("dMem", "mem_out", "dX", "x_out")]
-
-
-class EncoderTaps(C.Structure):
-    """ctrlsim_encoder_taps (include/ctrlsim.h): the optional outputs of ctrlsim_forward_loss_grads_encoder, device pointers, each NULL by default."""
-    _fields_ = [("dec", DecoderTaps), ("e0_out", C.c_void_p * 8), ("dE0", C.c_void_p * 8)]
+    _fields_ = [(k, C.c_void_p) for k in ("dX", "x_out", "dU", "u_out", "dX1", "x1_out", "dMem", "mem_out")] + \
+               [(k, C.c_void_p * 8) for k in ("dX0", "x0_out", "dE0", "e0_out")]      # per layer: CTRLSIM_MAX_{DECODER,ENCODER}_LAYERS
 
 
 P, I, L, D, F = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_float
@@ -166,17 +157,11 @@ SIGNATURES = {
     "ctrlsim_self_attn_block_grad": (I, [P, I, P, I, P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
     "ctrlsim_decoder_layer_grad_workspace_bytes": (L, [I, I, I, I, I]),
     "ctrlsim_decoder_layer_grad": (I, [P, I, P, I, P, P, I, P, I, I, I, I, I, I, P, P, P, I, P, I, I, P, P, P]),
-    "ctrlsim_decoder_grad_layout": (I, [C.POINTER(Dims), I, I, P, P]),
-    "ctrlsim_decoder_grads_workspace_bytes": (L, [C.POINTER(Dims), I, I]),
-    "ctrlsim_forward_loss_grads_decoder": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, C.POINTER(DecoderTaps), P]),
     "ctrlsim_scene_attn_block_grad_workspace_bytes": (L, [I, I]),
     "ctrlsim_scene_attn_block_grad_chunk_contexts": (I, [I, I]),
     "ctrlsim_scene_attn_block_grad": (I, [P, I, P, P, I, P, P, P, P, P, P, I, I, P, P, P, I, P]),
     "ctrlsim_encoder_layer_grad_workspace_bytes": (L, [I, I, I]),
     "ctrlsim_encoder_layer_grad": (I, [P, I, P, P, I, P, I, I, I, P, P, P, I, P, P]),
-    "ctrlsim_encoder_grad_layout": (I, [C.POINTER(Dims), I, I, P, P]),
-    "ctrlsim_encoder_grads_workspace_bytes": (L, [C.POINTER(Dims), I, I]),
-    "ctrlsim_forward_loss_grads_encoder": (I, [P, I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), F, P, P, P, P, C.POINTER(EncoderTaps), P]),
     "ctrlsim_head_ce": (I, [P, I, P, P, P, I, I, I, P, P]),
     "ctrlsim_loss_scratch_bytes": (L, [I, I, I]),
     "ctrlsim_loss_from_preds": (I, [C.POINTER(Dims), I, I, C.POINTER(Ctx), P, C.POINTER(LossCfg), P, P, P, P, P, P, P, P]),

@@ -603,7 +603,7 @@ int map_inputs(const ctrlsim_model* m, const Batch& bt, const Ws& w, hipStream_t
 }
 
 // map encoder + scene encoder + per-layer memory K/V (everything that only depends on the frame of the context)
-// e0_layers (the training entry of the encoder scope): e0_layers[i] (nullable) receives the scene rows that enter encoder layer i
+// e0_layers (the training entry at scope 5): e0_layers[i] (nullable) receives the scene rows that enter encoder layer i
 int scene_side(const ctrlsim_model* m, const Batch& bt, const Ws& w, float* dbg_seg_emb, hipStream_t st, float* const* e0_layers = nullptr) {
   const ctrlsim_dims& d = m->d;
   const int rM = (int)bt.rM, rP = (int)bt.rP;
@@ -993,9 +993,11 @@ extern "C" int ctrlsim_forward_loss(const ctrlsim_model* m, int B, int Tq, const
   FullReq rq; rq.loss = &lq;
   return forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq);
 }
-// ---- training: the gradient of final_loss (models/ctrl_sim.py:207-214) through the heads (csrc/head_grad.hip) and, one scope each, back
-// through the LAST decoder layer: its feed-forward block (scope >= 1, csrc/ffn_grad.hip), its cross-attention sublayer (scope >= 2,
-// csrc/attn_grad.hip) and its self-attention sublayer (scope 3, csrc/self_attn_grad.hip)
+// ---- training: the gradient of final_loss (models/ctrl_sim.py:207-214) through the heads (csrc/head_grad.hip) and, one scope each, further
+// back: the LAST decoder layer's feed-forward block (scope >= 1, csrc/ffn_grad.hip), its cross-attention sublayer (scope >= 2,
+// csrc/attn_grad.hip) and its self-attention sublayer (scope >= 3, csrc/self_attn_grad.hip); every earlier decoder layer by recompute
+// (scope >= 4, csrc/decoder_layer_grad.hip); every scene-encoder layer by recompute (scope 5, csrc/encoder_layer_grad.hip).  One tensor
+// table, one workspace layout and one entry serve every scope.
 namespace {
 struct GradHeadDesc { const char* name; int n, nsm, k, kind, sm0; };
 // the heads a model of these dims has, in weights.py order, and the float offset of each head's six tensors in `grads`
@@ -1013,38 +1015,63 @@ int grad_nmax(const ctrlsim_dims& d) {
   const int a = d.V > d.R * d.C ? d.V : d.R * d.C;
   return a > 2 * d.T ? a : 2 * d.T;
 }
-// the groups behind the heads in `grads`, group g from scope g + 1 on: six tensors of decoder.transformer_decoder.layers.{ND-1}, back to
-// back in state-dict order, perF * F + fixed floats each
+// The tensors behind the heads in `grads`: groups of six, back to back in state-dict order, perF * F + fixed floats each.  A group
+// belongs to a decoder layer (decoder.transformer_decoder.layers.{l}) or an encoder layer (encoder.transformer_encoder.layers.{l}); the
+// LAST decoder layer has it from scope `first` on, an earlier decoder layer from scope 4 on, an encoder layer at scope 5.
 struct GradPart { const char* suffix; long perF, fixed; };
-const GradPart kGroups[3][6] = {
-    {{".linear1.weight", DM, 0}, {".linear1.bias", 1, 0}, {".linear2.weight", DM, 0}, {".linear2.bias", 0, DM}, {".norm3.weight", 0, DM},
-     {".norm3.bias", 0, DM}},
-    {{".multihead_attn.in_proj_weight", 0, 3L * DM * DM}, {".multihead_attn.in_proj_bias", 0, 3 * DM},
-     {".multihead_attn.out_proj.weight", 0, (long)DM * DM}, {".multihead_attn.out_proj.bias", 0, DM}, {".norm2.weight", 0, DM},
-     {".norm2.bias", 0, DM}},
-    {{".self_attn.in_proj_weight", 0, 3L * DM * DM}, {".self_attn.in_proj_bias", 0, 3 * DM}, {".self_attn.out_proj.weight", 0, (long)DM * DM},
-     {".self_attn.out_proj.bias", 0, DM}, {".norm1.weight", 0, DM}, {".norm1.bias", 0, DM}}};
-// float offset in `grads` of group g's first tensor (= the length of scope g's buffer)
-long group_base(const ctrlsim_dims& d, bool has_fut, int g) {
+struct GradGroup { bool enc; int first; GradPart p[6]; };
+const GradGroup kGroups[5] = {
+    {false, 1, {{".linear1.weight", DM, 0}, {".linear1.bias", 1, 0}, {".linear2.weight", DM, 0}, {".linear2.bias", 0, DM},
+                {".norm3.weight", 0, DM}, {".norm3.bias", 0, DM}}},
+    {false, 2, {{".multihead_attn.in_proj_weight", 0, 3L * DM * DM}, {".multihead_attn.in_proj_bias", 0, 3 * DM},
+                {".multihead_attn.out_proj.weight", 0, (long)DM * DM}, {".multihead_attn.out_proj.bias", 0, DM}, {".norm2.weight", 0, DM},
+                {".norm2.bias", 0, DM}}},
+    {false, 3, {{".self_attn.in_proj_weight", 0, 3L * DM * DM}, {".self_attn.in_proj_bias", 0, 3 * DM},
+                {".self_attn.out_proj.weight", 0, (long)DM * DM}, {".self_attn.out_proj.bias", 0, DM}, {".norm1.weight", 0, DM},
+                {".norm1.bias", 0, DM}}},
+    {true, 5, {{".linear1.weight", DM, 0}, {".linear1.bias", 1, 0}, {".linear2.weight", DM, 0}, {".linear2.bias", 0, DM},
+               {".norm2.weight", 0, DM}, {".norm2.bias", 0, DM}}},
+    {true, 5, {{".self_attn.in_proj_weight", 0, 3L * DM * DM}, {".self_attn.in_proj_bias", 0, 3 * DM},
+               {".self_attn.out_proj.weight", 0, (long)DM * DM}, {".self_attn.out_proj.bias", 0, DM}, {".norm1.weight", 0, DM},
+               {".norm1.bias", 0, DM}}}};
+constexpr int kMaxGroups = 3 * CTRLSIM_MAX_DECODER_LAYERS + 2 * CTRLSIM_MAX_ENCODER_LAYERS;
+// Every group of a scope in `grads` order — the last decoder layer's, then the layers ND-2 .. 0, then the encoder layers NE-1 .. 0 —
+// as visit(group, layer, float offset of its first tensor); returns the length of the scope's buffer
+template <class Visit>
+long walk_groups(const ctrlsim_dims& d, bool has_fut, int scope, Visit visit) {
   GradHeadDesc hd[3];
   long off[4];
   long o = off[grad_heads(d, has_fut, hd, off)];
-  for (int k = 0; k < g; ++k)
-    for (const GradPart& p : kGroups[k]) o += p.perF * d.F + p.fixed;
+  auto layer = [&](bool enc, int l) {
+    for (const GradGroup& g : kGroups) {
+      if (g.enc != enc || g.first > scope) continue;
+      visit(g, l, o);
+      for (const GradPart& p : g.p) o += p.perF * d.F + p.fixed;
+    }
+  };
+  if (scope >= 1) layer(false, d.ND - 1);
+  for (int l = d.ND - 2; scope >= 4 && l >= 0; --l) layer(false, l);
+  for (int l = d.NE - 1; scope >= 5 && l >= 0; --l) layer(true, l);
   return o;
 }
 // The workspace of a scope: the forward's own, the loss buffers, the head-gradient carve, then per scope from 1 on the rows the forward
 // stores for its op (U, X1, X0), a dY [B*Tq*A*3, 256] for that op where the caller takes no tap (dX, dU, dX1), and the op's carve
-// (cross-attention: queries a context's 3 Tq A token rows, keys its M scene rows)
+// (cross-attention: queries a context's 3 Tq A token rows, keys its M scene rows).  Scope 4: the ND-1 row buffers X0_l, one dX0 buffer
+// (a layer's dX0 overwrites its dY where the caller takes neither as a tap) and the decoder layer op's carve.  Scope 5 with NE >= 1:
+// the NE scene-row buffers E0_l, a dMem (where the caller takes no tap), one dE0 buffer (as dX0) and the encoder layer op's carve.
 struct TrainLayout {
   size_t rows3, bytes;                  // B*Tq*A*3 token rows; the end of the widest carved scope
   LossWs l; HeadGradWs g;
   size_t U, dX; FfnGradWs f;            // scope >= 1
   size_t X1, dU; AttnGradWs a; int M;   // scope >= 2
-  size_t X0, dX1; SelfAttnGradWs s;     // scope 3
+  size_t X0, dX1; SelfAttnGradWs s;     // scope >= 3
+  size_t X0l[CTRLSIM_MAX_DECODER_LAYERS], dX0; DecLayerGradWs w;         // scope >= 4
+  size_t E0[CTRLSIM_MAX_ENCODER_LAYERS], dMem, dE0; EncLayerGradWs e;   // scope 5
 };
 bool train_layout(const ctrlsim_dims& d, int B, int Tq, int scope, TrainLayout& o) {
-  if (scope < 0 || scope > 3 || (scope >= 1 && d.F < 1)) return false;
+  if (scope < 0 || scope >= CTRLSIM_TRAIN_SCOPES || (scope >= 1 && d.F < 1)) return false;
+  if (scope >= 4 && (d.ND < 1 || d.ND > CTRLSIM_MAX_DECODER_LAYERS)) return false;
+  if (scope >= 5 && (d.NE < 0 || d.NE > CTRLSIM_MAX_ENCODER_LAYERS)) return false;
   const int64_t base = ctrlsim_forward_workspace_bytes(&d, B, Tq);
   if (base < 0) return false;
   o.rows3 = (size_t)B * Tq * d.A * 3;
@@ -1060,6 +1087,27 @@ bool train_layout(const ctrlsim_dims& d, int B, int Tq, int scope, TrainLayout& 
   if (scope >= 1) { o.f = ffn_grad_carve(rows_and_dy(o.U, o.dX), (long)o.rows3, d.F); o.bytes = o.f.bytes; }
   if (scope >= 2) { o.a = attn_grad_carve(rows_and_dy(o.X1, o.dU), B, L, o.M); o.bytes = o.a.bytes; }
   if (scope >= 3) { o.s = self_attn_grad_carve(rows_and_dy(o.X0, o.dX1), B, L); o.bytes = o.s.bytes; }
+  if (scope >= 4) {
+    size_t off = up(o.bytes);
+    for (int l = 0; l < d.ND - 1; ++l, off += n) o.X0l[l] = off;
+    o.dX0 = off;
+    o.bytes = off + n;
+    if (d.ND > 1) {
+      if (!decoder_layer_grad_dims_ok(B, Tq, d.A, o.M, d.F)) return false;
+      o.w = decoder_layer_grad_carve(o.bytes, B, Tq, d.A, o.M, d.F);
+      o.bytes = o.w.bytes;
+    }
+  }
+  if (scope >= 5 && d.NE > 0) {
+    if (!encoder_layer_grad_dims_ok(B, o.M, d.F)) return false;
+    const size_t nm = up((size_t)B * o.M * DM * sizeof(float));
+    size_t off = up(o.bytes);
+    for (int l = 0; l < d.NE; ++l, off += nm) o.E0[l] = off;
+    o.dMem = off;
+    o.dE0 = off + nm;
+    o.e = encoder_layer_grad_carve(off + 2 * nm, B, o.M, d.F);
+    o.bytes = o.e.bytes;
+  }
   return true;
 }
 int head_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving, const ctrlsim_loss_cfg& cfg,
@@ -1092,34 +1140,45 @@ LossReq grad_loss_req(const unsigned char* moving, const ctrlsim_loss_cfg& cfg, 
 bool grad_args_ok(const ctrlsim_model* m, int B, int Tq) {
   return m && B >= 1 && Tq >= 1 && Tq <= m->d.T && !(tok_variant(m->d.variant) == 0 && m->d.C != 3);
 }
+// `rows` rows [., 256] into a caller's buffer, where the caller gave one
+int copy_rows(float* dst, const float* src, size_t rows, hipStream_t st) {
+  if (dst && hipMemcpyAsync(dst, src, rows * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
+  return CTRLSIM_OK;
+}
 }  // namespace
 
 extern "C" int ctrlsim_train_grad_layout(const ctrlsim_dims* d, int has_future_states, int scope, int cap, const char** names,
                                          int64_t* offsets) {
   static const char* const parts[6] = {".mlp.0.weight", ".mlp.0.bias", ".mlp.1.weight", ".mlp.1.bias", ".mlp.3.weight", ".mlp.3.bias"};
-  static std::string store[36];        // the heads' names by kind, then the groups'
-  if (!d || scope < 0 || scope > 3 || (scope >= 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
+  static std::vector<std::string> store;        // the names handed out: valid until the next query that asks for names
+  if (!d || scope < 0 || scope >= CTRLSIM_TRAIN_SCOPES || (scope >= 1 && (d->ND < 1 || d->F < 1))) return CTRLSIM_EINVAL;
+  if ((scope >= 4 && d->ND > CTRLSIM_MAX_DECODER_LAYERS) || (scope >= 5 && (d->NE < 0 || d->NE > CTRLSIM_MAX_ENCODER_LAYERS)))
+    return CTRLSIM_EINVAL;
+  const bool has_fut = has_future_states != 0;
   GradHeadDesc hd[3];
   long off[4];
-  const int nh = grad_heads(*d, has_future_states != 0, hd, off), n = 6 * (nh + scope);
+  const int nh = grad_heads(*d, has_fut, hd, off);
+  int n = 6 * nh;
+  walk_groups(*d, has_fut, scope, [&](const GradGroup&, int, long) { n += 6; });
   if ((names || offsets) && cap < n) return CTRLSIM_EINVAL;
-  auto put = [&](int i, int slot, const std::string& name, long o) {
-    if (names) { store[slot] = name; names[i] = store[slot].c_str(); }
+  if (names) store.assign(n, std::string());
+  int i = 0;
+  auto put = [&](const std::string& name, long o) {
+    if (names) { store[i] = name; names[i] = store[i].c_str(); }
     if (offsets) offsets[i] = o;
+    ++i;
   };
-  for (int i = 0; i < nh; ++i) {
-    const long w = (long)hd[i].n * hd[i].nsm;
+  for (int h = 0; h < nh; ++h) {
+    const long w = (long)hd[h].n * hd[h].nsm;
     const long sz[6] = {(long)DM * DM, DM, DM, DM, w * DM, w};
-    long o = off[i];
-    for (int j = 0; j < 6; o += sz[j], ++j) put(6 * i + j, 6 * hd[i].kind + j, std::string(hd[i].name) + parts[j], o);
+    long o = off[h];
+    for (int j = 0; j < 6; o += sz[j], ++j) put(std::string(hd[h].name) + parts[j], o);
   }
-  const std::string pre = "decoder.transformer_decoder.layers." + std::to_string(d->ND - 1);
-  for (int g = 0; g < scope; ++g) {
-    long o = group_base(*d, has_future_states != 0, g);
-    for (int j = 0; j < 6; o += kGroups[g][j].perF * d->F + kGroups[g][j].fixed, ++j)
-      put(6 * (nh + g) + j, 18 + 6 * g + j, pre + kGroups[g][j].suffix, o);
-  }
-  if (offsets && cap > n) offsets[n] = group_base(*d, has_future_states != 0, scope);      // (room for one more: the total)
+  const long total = walk_groups(*d, has_fut, scope, [&](const GradGroup& g, int l, long o) {
+    const std::string pre = (g.enc ? "encoder.transformer_encoder.layers." : "decoder.transformer_decoder.layers.") + std::to_string(l);
+    for (const GradPart& p : g.p) { put(pre + p.suffix, o); o += p.perF * d->F + p.fixed; }
+  });
+  if (offsets && cap > n) offsets[n] = total;          // (room for one more: the total)
   return n;
 }
 extern "C" int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq, int scope) {
@@ -1138,278 +1197,97 @@ extern "C" int ctrlsim_heads_loss_grad(const ctrlsim_model* m, int B, int Tq, co
   CHK(heads_loss(m, X, B * Tq * m->d.A, reinterpret_cast<float*>(ws + L.g.H), lq, c, B, Tq, st));
   return head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L, sums, grads, dX, st);
 }
-namespace {
-// `rows` rows [., 256] into a caller's buffer, where the caller gave one
-int copy_rows(float* dst, const float* src, size_t rows, hipStream_t st) {
-  if (dst && hipMemcpyAsync(dst, src, rows * DM * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return CTRLSIM_ELAUNCH;
-  return CTRLSIM_OK;
-}
-}  // namespace
-// The teacher-forced forward, the loss, the head gradients, then the ops of the scope from the layer's output back; each op's dY is the dX
-// of the op behind it — the caller's tap, or the workspace's buffer.  Scope 0's forward is ctrlsim_forward_loss's.  From scope 1 on the
+// The teacher-forced forward, the loss, the head gradients, then the ops of the scope from the decoder's output back; each op's dY is the
+// dX of the op behind it — the caller's tap, or the workspace's buffer.  Scope 0's forward is ctrlsim_forward_loss's.  From scope 1 on the
 // last decoder layer's out-projection + norm2 and its feed-forward block run as two kernels with U copied to the workspace between them
 // (FullReq::u_store); scope 2 copies the rows behind norm1 (X1) before the out-projection + norm2 overwrite them, scope 3 the rows that
-// enter the layer (X0) before its in_proj.  Mem and its padding bytes are read where the scene side left them: forward_full writes w.src /
-// w.src_pad in scene_side only, the decoder and the heads read them.
-// x0_layers / mem_seen / pad_seen (the all-layers entry below): the per-layer row stores of the forward, and where Mem and its padding
-// bytes lie in the workspace; the public entry passes none.  e0_layers (the encoder entry): the scene side's per-layer row stores.
-namespace {
-int loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving, const ctrlsim_loss_cfg* cfg,
-               float loss_action_coef, int scope, void* workspace, double* sums, double* per_ctx, float* grads, const ctrlsim_train_taps& t,
-               float* const* x0_layers, const float** mem_seen, const unsigned char** pad_seen, hipStream_t st,
-               float* const* e0_layers = nullptr) {
-  if (scope < 0 || scope > 3 || !grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
-  if ((scope < 1 && (t.dU || t.u_out)) || (scope < 2 && (t.dX1 || t.dMem || t.x1_out || t.mem_out)) || (scope < 3 && (t.dX0 || t.x0_out)))
-    return CTRLSIM_EINVAL;                                                        // a tap of a wider scope than the call's
+// enter the layer (X0) before its in_proj.  Scope 4 has the forward copy the rows that enter each earlier decoder layer too
+// (FullReq::x0_layers; those layers keep their fused forward) and runs the layer op for l = ND-2 .. 0, dMem accumulated onto the last
+// layer's; scope 5 has the scene side copy the rows that enter each encoder layer (FullReq::e0_layers) and runs the encoder layer op for
+// l = NE-1 .. 0 from dMem back.  Mem and its padding bytes are read where the scene side left them: forward_full writes w.src / w.src_pad
+// in scene_side only, the decoder and the heads read them.  Everything refused is refused before anything is launched.
+extern "C" int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
+                                          const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
+                                          double* per_ctx, float* grads, const ctrlsim_train_taps* taps, hipStream_t st) {
+  static const ctrlsim_train_taps none{};
+  const ctrlsim_train_taps& t = taps ? *taps : none;
+  if (scope < 0 || scope >= CTRLSIM_TRAIN_SCOPES || !grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return CTRLSIM_EINVAL;
   const ctrlsim_dims& d = m->d;
+  const int last = d.ND - 1, NE = scope >= 5 ? d.NE : 0;
   if (scope >= 1 && d.ND < 1) return CTRLSIM_EINVAL;
   if (scope >= 3 && (tok_variant(d.variant) != 0 || (d.variant != 0 && d.variant != 4))) return CTRLSIM_EINVAL;   // CtRL-Sim tokens: (t, a, k), k < 3
-  const DecLayer* Ld = scope >= 1 ? &m->dec[d.ND - 1] : nullptr;
-  // the in_proj master [768, 256] = (Wq; Wk; Wv): the query projection's rows, then the memory projection's
-  if (scope >= 2 && (Ld->ckv.w != Ld->cq.w + (long)DM * DM || Ld->ckv.b != Ld->cq.b + DM)) return CTRLSIM_EINVAL;
   TrainLayout L;
   if (!train_layout(d, B, Tq, scope, L)) return CTRLSIM_EINVAL;
+  // the in_proj master [768, 256] = (Wq; Wk; Wv): the query projection's rows, then the memory projection's — of every layer differentiated
+  for (int l = scope >= 4 ? 0 : last; scope >= 2 && l <= last; ++l)
+    if (m->dec[l].ckv.w != m->dec[l].cq.w + (long)DM * DM || m->dec[l].ckv.b != m->dec[l].cq.b + DM) return CTRLSIM_EINVAL;
+  // a tap outside its scopes, or of a layer the scope does not differentiate
+  if (((t.dU || t.u_out) && (scope < 1 || scope > 3)) || ((t.dX1 || t.x1_out) && (scope < 2 || scope > 3)) || ((t.dMem || t.mem_out) && scope < 2))
+    return CTRLSIM_EINVAL;
+  for (int l = 0; l < CTRLSIM_MAX_DECODER_LAYERS; ++l)
+    if ((t.dX0[l] || t.x0_out[l]) && !(scope >= 4 ? l <= last : scope == 3 && l == last)) return CTRLSIM_EINVAL;
+  for (int l = 0; l < CTRLSIM_MAX_ENCODER_LAYERS; ++l)
+    if ((t.dE0[l] || t.e0_out[l]) && l >= NE) return CTRLSIM_EINVAL;
   char* ws = static_cast<char*>(workspace);
   auto at = [&](bool have, size_t o) { return have ? reinterpret_cast<float*>(ws + o) : nullptr; };
   const LossReq lq = grad_loss_req(moving, *cfg, sums, per_ctx, ws, L.l);
-  const int A = d.A;
+  const int A = d.A, mask_mode = d.variant == 4 ? 1 : 0;
+  const bool tap_last = scope >= 3 && last < CTRLSIM_MAX_DECODER_LAYERS;      // (scope 3 takes any ND; the taps have 8 layers)
   float *X = nullptr, *U = at(scope >= 1, L.U), *X1 = at(scope >= 2, L.X1), *X0 = at(scope >= 3, L.X0);
+  float *x0[CTRLSIM_MAX_DECODER_LAYERS] = {}, *e0[CTRLSIM_MAX_ENCODER_LAYERS] = {};      // the rows that enter the earlier decoder / the encoder layers
+  for (int l = 0; scope >= 4 && l < last; ++l) x0[l] = at(true, L.X0l[l]);
+  for (int l = 0; l < NE; ++l) e0[l] = at(true, L.E0[l]);
   float *dX = t.dX ? t.dX : at(scope >= 1, L.dX), *dU = t.dU ? t.dU : at(scope >= 2, L.dU), *dX1 = t.dX1 ? t.dX1 : at(scope >= 3, L.dX1);
+  float* dX0 = tap_last && t.dX0[last] ? t.dX0[last] : at(scope >= 4 && last > 0, L.dX0);
+  float* dMem = t.dMem ? t.dMem : at(NE > 0, L.dMem);
   const float* Mem = nullptr;
   const unsigned char* pad = nullptr;
-  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = X0; rq.x0_layers = x0_layers; rq.e0_layers = e0_layers;
+  FullReq rq; rq.loss = &lq; rq.x_seen = &X; rq.u_store = U; rq.x1_store = X1; rq.x0_store = X0;
   if (scope >= 2) { rq.mem_seen = &Mem; rq.pad_seen = &pad; }
+  if (scope >= 4 && last > 0) rq.x0_layers = x0;
+  if (NE > 0) rq.e0_layers = e0;
   CHK(forward_full(m, 1, &B, &A, c, Tq, workspace, st, rq));
   if (!X || (scope >= 2 && (!Mem || !pad))) return CTRLSIM_EINVAL;
-  if (mem_seen) *mem_seen = Mem;
-  if (pad_seen) *pad_seen = pad;
   CHK(copy_rows(t.x_out, X, L.rows3, st));
   CHK(copy_rows(t.u_out, U, L.rows3, st));
   CHK(copy_rows(t.x1_out, X1, L.rows3, st));
   CHK(copy_rows(t.mem_out, Mem, (size_t)B * L.M, st));
   CHK(head_grads(m, B, Tq, c, moving, *cfg, loss_action_coef, X, ws, L, sums, grads, dX, st));
-  auto group = [&](int g) { return grads + group_base(d, m->has_fut, g); };
-  if (scope >= 1)
-    CHK(launch_ffn_block_grad(U, DM, dX, DM, Ld->lin1.w, Ld->lin1.b, Ld->lin2.w, Ld->lin2.b, Ld->n3.g, Ld->n3.b, (long)L.rows3, d.F, ws, L.f,
-                              group(0), dU, DM, st));
-  if (scope >= 2)
-    CHK(launch_attn_block_grad(X1, DM, Mem, DM, pad, dU, DM, Ld->cq.w, Ld->cq.b, Ld->cout.w, Ld->cout.b, Ld->n2.g, Ld->n2.b, B, Tq * A * 3, L.M,
-                               ws, L.a, group(1), dX1, DM, t.dMem, DM, 0, st));
-  if (scope >= 3) {
-    CHK(copy_rows(t.x0_out, X0, L.rows3, st));
-    CHK(launch_self_attn_block_grad(X0, DM, dX1, DM, Ld->qkv.w, Ld->qkv.b, Ld->out.w, Ld->out.b, Ld->n1.g, Ld->n1.b, B, Tq, A,
-                                    d.variant == 4 ? 1 : 0, ws, L.s, group(2), t.dX0, DM, st));
-  }
-  return CTRLSIM_OK;
-}
-// the 18 tensors of a decoder layer behind scope 3's buffer, in the layer op's order: kGroups, group by group
-const GradPart* layer_part(int j) { return &kGroups[j / 6][j % 6]; }
-long layer_floats(const ctrlsim_dims& d) {
-  long o = 0;
-  for (int j = 0; j < 18; ++j) o += layer_part(j)->perF * d.F + layer_part(j)->fixed;
-  return o;
-}
-// The workspace of the all-layers entry: scope 3's, then the ND-1 row buffers X0_l, one dX0 buffer (a layer's dX0 overwrites its dY
-// where the caller takes neither as a tap) and the layer op's carve
-struct DecoderLayout { TrainLayout t; size_t X0[CTRLSIM_MAX_DECODER_LAYERS], dX0, bytes; DecLayerGradWs w; };
-bool decoder_layout(const ctrlsim_dims& d, int B, int Tq, DecoderLayout& o) {
-  if (d.ND < 1 || d.ND > CTRLSIM_MAX_DECODER_LAYERS || !train_layout(d, B, Tq, 3, o.t)) return false;
-  const size_t n = (o.t.rows3 * DM * sizeof(float) + 255) & ~size_t(255);
-  size_t off = (o.t.bytes + 255) & ~size_t(255);
-  for (int l = 0; l < d.ND - 1; ++l, off += n) o.X0[l] = off;
-  o.dX0 = off; off += n;
-  o.bytes = off;
-  if (d.ND > 1) {
-    if (!decoder_layer_grad_dims_ok(B, Tq, d.A, o.t.M, d.F)) return false;
-    o.w = decoder_layer_grad_carve(off, B, Tq, d.A, o.t.M, d.F);
-    o.bytes = o.w.bytes;
-  }
-  return true;
-}
-}  // namespace
-
-extern "C" int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                          const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
-                                          double* per_ctx, float* grads, const ctrlsim_train_taps* taps, hipStream_t st) {
-  static const ctrlsim_train_taps none{};
-  return loss_grads(m, B, Tq, c, moving, cfg, loss_action_coef, scope, workspace, sums, per_ctx, grads, taps ? *taps : none, nullptr, nullptr,
-                    nullptr, st);
-}
-
-// ---- training (d): every decoder layer.  Scope 3 with the rows that enter each earlier layer copied by the forward, then the layer op
-// (csrc/decoder_layer_grad.hip) for l = ND-2 .. 0 on those rows: dY = the dX0 of layer l + 1, dMem accumulated onto the last layer's.
-extern "C" int ctrlsim_decoder_grad_layout(const ctrlsim_dims* d, int has_future_states, int cap, const char** names, int64_t* offsets) {
-  static std::string store[18 * (CTRLSIM_MAX_DECODER_LAYERS - 1)];
-  if (!d || d->ND < 1 || d->ND > CTRLSIM_MAX_DECODER_LAYERS || d->F < 1) return CTRLSIM_EINVAL;
-  const int n3 = ctrlsim_train_grad_layout(d, has_future_states, 3, 0, nullptr, nullptr);
-  if (n3 < 0) return n3;
-  const int n = n3 + 18 * (d->ND - 1);
-  if ((names || offsets) && cap < n) return CTRLSIM_EINVAL;
-  if (names || offsets) ctrlsim_train_grad_layout(d, has_future_states, 3, n3, names, offsets);
-  long o = group_base(*d, has_future_states != 0, 3);
-  int i = n3;
-  for (int l = d->ND - 2; l >= 0; --l) {
-    const std::string pre = "decoder.transformer_decoder.layers." + std::to_string(l);
-    for (int j = 0; j < 18; o += layer_part(j)->perF * d->F + layer_part(j)->fixed, ++j, ++i) {
-      if (names) { store[i - n3] = pre + layer_part(j)->suffix; names[i] = store[i - n3].c_str(); }
-      if (offsets) offsets[i] = o;
+  long go[kMaxGroups];                   // the float offset of every group of the scope, in `grads` order
+  int ng = 0;
+  walk_groups(d, m->has_fut, scope, [&](const GradGroup&, int, long o) { go[ng++] = o; });
+  if (scope >= 1) {
+    const DecLayer& Ld = m->dec[last];
+    CHK(launch_ffn_block_grad(U, DM, dX, DM, Ld.lin1.w, Ld.lin1.b, Ld.lin2.w, Ld.lin2.b, Ld.n3.g, Ld.n3.b, (long)L.rows3, d.F, ws, L.f,
+                              grads + go[0], dU, DM, st));
+    if (scope >= 2)
+      CHK(launch_attn_block_grad(X1, DM, Mem, DM, pad, dU, DM, Ld.cq.w, Ld.cq.b, Ld.cout.w, Ld.cout.b, Ld.n2.g, Ld.n2.b, B, Tq * A * 3, L.M,
+                                 ws, L.a, grads + go[1], dX1, DM, dMem, DM, 0, st));
+    if (scope >= 3) {
+      CHK(copy_rows(tap_last ? t.x0_out[last] : nullptr, X0, L.rows3, st));
+      CHK(launch_self_attn_block_grad(X0, DM, dX1, DM, Ld.qkv.w, Ld.qkv.b, Ld.out.w, Ld.out.b, Ld.n1.g, Ld.n1.b, B, Tq, A, mask_mode, ws, L.s,
+                                      grads + go[2], dX0, DM, st));
     }
   }
-  if (offsets && cap > n) offsets[n] = o;              // (room for one more: the total)
-  return n;
-}
-extern "C" int64_t ctrlsim_decoder_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq) {
-  DecoderLayout L;
-  if (!d || B < 1 || Tq < 1 || !decoder_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
-  return (int64_t)L.bytes;
-}
-namespace {
-// what the decoder entry refuses, before anything runs
-bool decoder_grads_ok(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const ctrlsim_loss_cfg* cfg, const void* workspace,
-                      const double* sums, const float* grads, const ctrlsim_decoder_taps& t, DecoderLayout& L) {
-  if (!grad_args_ok(m, B, Tq) || !c || !cfg || !workspace || !sums || !grads) return false;
-  const ctrlsim_dims& d = m->d;
-  if (!decoder_layout(d, B, Tq, L)) return false;
-  if (tok_variant(d.variant) != 0 || (d.variant != 0 && d.variant != 4)) return false;      // (scope 3's own refusal, before anything runs)
-  for (int l = d.ND; l < CTRLSIM_MAX_DECODER_LAYERS; ++l)
-    if (t.x0_out[l] || t.dX0[l]) return false;
-  for (int l = 0; l < d.ND - 1; ++l)
-    if (m->dec[l].ckv.w != m->dec[l].cq.w + (long)DM * DM || m->dec[l].ckv.b != m->dec[l].cq.b + DM) return false;
-  return true;
-}
-// The decoder entry behind its checks.  e0_layers / pad_seen (the encoder entry below): the scene side's per-layer row stores, and where
-// the scene rows' key-padding bytes lie in the workspace; the public decoder entry passes none.
-int decoder_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving, const ctrlsim_loss_cfg* cfg,
-                  float loss_action_coef, void* workspace, double* sums, double* per_ctx, float* grads, const ctrlsim_decoder_taps& t,
-                  const DecoderLayout& L, float* const* e0_layers, const unsigned char** pad_seen, hipStream_t st) {
-  const ctrlsim_dims& d = m->d;
-  char* ws = static_cast<char*>(workspace);
-  auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
-  const int last = d.ND - 1;
-  float* x0[CTRLSIM_MAX_DECODER_LAYERS] = {};
-  for (int l = 0; l < last; ++l) x0[l] = f(L.X0[l]);
-  ctrlsim_train_taps t3{};
-  t3.dX = t.dX; t3.x_out = t.x_out; t3.dMem = t.dMem; t3.mem_out = t.mem_out; t3.x0_out = t.x0_out[last];
-  t3.dX0 = t.dX0[last] ? t.dX0[last] : last > 0 ? f(L.dX0) : nullptr;
-  const float* Mem = nullptr;
-  const unsigned char* pad = nullptr;
-  CHK(loss_grads(m, B, Tq, c, moving, cfg, loss_action_coef, 3, workspace, sums, per_ctx, grads, t3, last > 0 ? x0 : nullptr, &Mem, &pad, st,
-                 e0_layers));
-  if (pad_seen) *pad_seen = pad;
-  const float* dY = t3.dX0;
-  float* g = grads + group_base(d, m->has_fut, 3);
-  for (int l = last - 1; l >= 0; --l, g += layer_floats(d)) {
+  const float* dY = dX0;
+  for (int l = last - 1, g = 3; scope >= 4 && l >= 0; --l, g += 3) {
     const DecLayer& Ld = m->dec[l];
     const float* tn[18] = {Ld.lin1.w, Ld.lin1.b, Ld.lin2.w, Ld.lin2.b, Ld.n3.g, Ld.n3.b, Ld.cq.w, Ld.cq.b, Ld.cout.w, Ld.cout.b, Ld.n2.g, Ld.n2.b,
                            Ld.qkv.w, Ld.qkv.b, Ld.out.w, Ld.out.b, Ld.n1.g, Ld.n1.b};
-    CHK(copy_rows(t.x0_out[l], x0[l], L.t.rows3, st));
-    float* dX0 = t.dX0[l] ? t.dX0[l] : l > 0 ? f(L.dX0) : nullptr;       // (layer 0's, untapped, is nobody's dY)
-    CHK(launch_decoder_layer_grad(x0[l], DM, Mem, DM, pad, dY, DM, tn, B, Tq, d.A, L.t.M, d.F, d.variant == 4 ? 1 : 0, ws, L.w, g, dX0, DM, t.dMem,
-                                  DM, 1, nullptr, nullptr, st));
-    dY = dX0;
+    CHK(copy_rows(t.x0_out[l], x0[l], L.rows3, st));
+    float* dx = t.dX0[l] ? t.dX0[l] : at(l > 0, L.dX0);                    // (layer 0's, untapped, is nobody's dY)
+    CHK(launch_decoder_layer_grad(x0[l], DM, Mem, DM, pad, dY, DM, tn, B, Tq, A, L.M, d.F, mask_mode, ws, L.w, grads + go[g], dx, DM, dMem, DM,
+                                  1, nullptr, nullptr, st));
+    dY = dx;
   }
-  return CTRLSIM_OK;
-}
-}  // namespace
-extern "C" int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                                  const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
-                                                  double* per_ctx, float* grads, const ctrlsim_decoder_taps* taps, hipStream_t st) {
-  static const ctrlsim_decoder_taps none{};
-  const ctrlsim_decoder_taps& t = taps ? *taps : none;
-  DecoderLayout L;
-  if (!decoder_grads_ok(m, B, Tq, c, cfg, workspace, sums, grads, t, L)) return CTRLSIM_EINVAL;
-  return decoder_grads(m, B, Tq, c, moving, cfg, loss_action_coef, workspace, sums, per_ctx, grads, t, L, nullptr, nullptr, st);
-}
-
-// ---- training (e): every scene-encoder layer.  The decoder entry with the scene rows that enter each encoder layer copied by the
-// forward, then the layer op (csrc/encoder_layer_grad.hip) for l = NE-1 .. 0 on those rows: dY = dMem, then the dE0 of layer l + 1.
-namespace {
-const GradPart kEncParts[12] = {
-    {".linear1.weight", DM, 0}, {".linear1.bias", 1, 0}, {".linear2.weight", DM, 0}, {".linear2.bias", 0, DM}, {".norm2.weight", 0, DM},
-    {".norm2.bias", 0, DM}, {".self_attn.in_proj_weight", 0, 3L * DM * DM}, {".self_attn.in_proj_bias", 0, 3 * DM},
-    {".self_attn.out_proj.weight", 0, (long)DM * DM}, {".self_attn.out_proj.bias", 0, DM}, {".norm1.weight", 0, DM}, {".norm1.bias", 0, DM}};
-// the length of the decoder entry's buffer: scope 3's, then ND-1 layers of 18 tensors
-long decoder_grads_floats(const ctrlsim_dims& d, bool has_fut) { return group_base(d, has_fut, 3) + (d.ND - 1) * layer_floats(d); }
-long enc_layer_floats(const ctrlsim_dims& d) {
-  long o = 0;
-  for (const GradPart& p : kEncParts) o += p.perF * d.F + p.fixed;
-  return o;
-}
-// The workspace of the encoder entry: the decoder entry's, then the NE row buffers E0_l, a dMem (where the caller takes no tap), one dE0
-// buffer (a layer's dE0 overwrites its dY where the caller takes neither as a tap) and the layer op's carve
-struct EncoderLayout { DecoderLayout dl; size_t E0[CTRLSIM_MAX_ENCODER_LAYERS], dMem, dE0, bytes; int M; EncLayerGradWs w; };
-bool encoder_layout(const ctrlsim_dims& d, int B, int Tq, EncoderLayout& o) {
-  if (d.NE < 0 || d.NE > CTRLSIM_MAX_ENCODER_LAYERS || !decoder_layout(d, B, Tq, o.dl)) return false;
-  o.M = o.dl.t.M;
-  o.bytes = o.dl.bytes;
-  if (d.NE == 0) return true;
-  if (!encoder_layer_grad_dims_ok(B, o.M, d.F)) return false;
-  const size_t n = ((size_t)B * o.M * DM * sizeof(float) + 255) & ~size_t(255);
-  size_t off = (o.dl.bytes + 255) & ~size_t(255);
-  for (int l = 0; l < d.NE; ++l, off += n) o.E0[l] = off;
-  o.dMem = off; off += n;
-  o.dE0 = off; off += n;
-  o.w = encoder_layer_grad_carve(off, B, o.M, d.F);
-  o.bytes = o.w.bytes;
-  return true;
-}
-}  // namespace
-extern "C" int ctrlsim_encoder_grad_layout(const ctrlsim_dims* d, int has_future_states, int cap, const char** names, int64_t* offsets) {
-  static std::string store[12 * CTRLSIM_MAX_ENCODER_LAYERS];
-  if (!d || d->NE < 0 || d->NE > CTRLSIM_MAX_ENCODER_LAYERS) return CTRLSIM_EINVAL;
-  const int nd = ctrlsim_decoder_grad_layout(d, has_future_states, 0, nullptr, nullptr);
-  if (nd < 0) return nd;
-  const int n = nd + 12 * d->NE;
-  if ((names || offsets) && cap < n) return CTRLSIM_EINVAL;
-  if (names || offsets) ctrlsim_decoder_grad_layout(d, has_future_states, nd, names, offsets);
-  long o = decoder_grads_floats(*d, has_future_states != 0);
-  int i = nd;
-  for (int l = d->NE - 1; l >= 0; --l) {
-    const std::string pre = "encoder.transformer_encoder.layers." + std::to_string(l);
-    for (int j = 0; j < 12; o += kEncParts[j].perF * d->F + kEncParts[j].fixed, ++j, ++i) {
-      if (names) { store[i - nd] = pre + kEncParts[j].suffix; names[i] = store[i - nd].c_str(); }
-      if (offsets) offsets[i] = o;
-    }
-  }
-  if (offsets && cap > n) offsets[n] = o;              // (room for one more: the total)
-  return n;
-}
-extern "C" int64_t ctrlsim_encoder_grads_workspace_bytes(const ctrlsim_dims* d, int B, int Tq) {
-  EncoderLayout L;
-  if (!d || B < 1 || Tq < 1 || !encoder_layout(*d, B, Tq, L)) return CTRLSIM_EINVAL;
-  return (int64_t)L.bytes;
-}
-extern "C" int ctrlsim_forward_loss_grads_encoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* c, const unsigned char* moving,
-                                                  const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums,
-                                                  double* per_ctx, float* grads, const ctrlsim_encoder_taps* taps, hipStream_t st) {
-  static const ctrlsim_encoder_taps none{};
-  const ctrlsim_encoder_taps& t = taps ? *taps : none;
-  if (!m) return CTRLSIM_EINVAL;
-  const ctrlsim_dims& d = m->d;
-  EncoderLayout L;
-  if (!decoder_grads_ok(m, B, Tq, c, cfg, workspace, sums, grads, t.dec, L.dl) || !encoder_layout(d, B, Tq, L)) return CTRLSIM_EINVAL;
-  for (int l = d.NE; l < CTRLSIM_MAX_ENCODER_LAYERS; ++l)
-    if (t.e0_out[l] || t.dE0[l]) return CTRLSIM_EINVAL;
-  if (d.NE == 0) return decoder_grads(m, B, Tq, c, moving, cfg, loss_action_coef, workspace, sums, per_ctx, grads, t.dec, L.dl, nullptr, nullptr, st);
-  char* ws = static_cast<char*>(workspace);
-  auto f = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
-  float* e0[CTRLSIM_MAX_ENCODER_LAYERS] = {};
-  for (int l = 0; l < d.NE; ++l) e0[l] = f(L.E0[l]);
-  ctrlsim_decoder_taps td = t.dec;
-  if (!td.dMem) td.dMem = f(L.dMem);
-  const unsigned char* pad = nullptr;
-  CHK(decoder_grads(m, B, Tq, c, moving, cfg, loss_action_coef, workspace, sums, per_ctx, grads, td, L.dl, e0, &pad, st));
-  if (!pad) return CTRLSIM_EINVAL;
-  const float* dY = td.dMem;
-  float* g = grads + decoder_grads_floats(d, m->has_fut);
-  const size_t rowsM = (size_t)B * L.M;
-  for (int l = d.NE - 1; l >= 0; --l, g += enc_layer_floats(d)) {
+  dY = dMem;
+  for (int l = NE - 1, g = 3 * d.ND; l >= 0; --l, g += 2) {
     const EncLayer& Le = m->enc[l];
     const float* tn[12] = {Le.lin1.w, Le.lin1.b, Le.lin2.w, Le.lin2.b, Le.n2.g, Le.n2.b, Le.qkv.w, Le.qkv.b, Le.out.w, Le.out.b, Le.n1.g, Le.n1.b};
-    CHK(copy_rows(t.e0_out[l], e0[l], rowsM, st));
-    float* dE0 = t.dE0[l] ? t.dE0[l] : l > 0 ? f(L.dE0) : nullptr;       // (layer 0's, untapped, is nobody's dY)
-    CHK(launch_encoder_layer_grad(e0[l], DM, pad, dY, DM, tn, B, L.M, d.F, ws, L.w, g, dE0, DM, nullptr, st));
-    dY = dE0;
+    CHK(copy_rows(t.e0_out[l], e0[l], (size_t)B * L.M, st));
+    float* de = t.dE0[l] ? t.dE0[l] : at(l > 0, L.dE0);                    // (layer 0's, untapped, is nobody's dY)
+    CHK(launch_encoder_layer_grad(e0[l], DM, pad, dY, DM, tn, B, L.M, d.F, ws, L.e, grads + go[g], de, DM, nullptr, st));
+    dY = de;
   }
   return CTRLSIM_OK;
 }

@@ -15,12 +15,12 @@ block (linear1, linear2, norm3): scope 1 (csrc/ffn_grad.hip) differentiates it t
 starts from `dU` and returns `dX1` and `dMem`, the gradients at the layer's norm1 output and at the scene encoder's output;
 `set_trainable("heads+last_layer")` adds its self-attention sublayer (self_attn, norm1), so that the whole last decoder layer trains:
 scope 3 (csrc/self_attn_grad.hip) starts from `dX1` and returns `dX0`, the gradient at the layer's input rows.
-`set_trainable("heads+decoder")` (CtRLSim.DECODER_SCOPE) trains every decoder layer: ctrlsim_forward_loss_grads_decoder does what scope 3
+`set_trainable("heads+decoder")` (CtRLSim.DECODER_SCOPE) trains every decoder layer: scope 4 does what scope 3
 does and then, for each earlier layer from the last but one down, recomputes the layer's inside from the rows that entered it and runs the
 three backward ops (csrc/decoder_layer_grad.hip); it returns `dX0` of every layer and `dMem` summed over all of them, the gradients the
 encoder's and the embeddings' backward start from.
-`set_trainable("heads+decoder+encoder")` (CtRLSim.ENCODER_SCOPE) also trains every scene-encoder layer: ctrlsim_forward_loss_grads_encoder
-does what the decoder entry does and then, from `dMem` back, recomputes each encoder layer's inside from the scene rows that entered it and
+`set_trainable("heads+decoder+encoder")` (CtRLSim.ENCODER_SCOPE) also trains every scene-encoder layer: scope 5
+does what scope 4 does and then, from `dMem` back, recomputes each encoder layer's inside from the scene rows that entered it and
 runs the two backward ops (csrc/encoder_layer_grad.hip); it returns `dE0` of every encoder layer — `dE0[0]` is the gradient at the rows
 [polylines || initial states], where the map encoder's and the embeddings' backward — not built — would start."""
 from __future__ import annotations
@@ -236,8 +236,12 @@ class CtRLSim:
     def head_grad_workspace_bytes(self, B):
         return self.train_grad_workspace_bytes(B, "heads")
 
-    # the optional outputs of ctrlsim_forward_loss_grads in the order the result tuples list them: name -> the first scope that has it
-    _TAPS = {"dX": 0, "dU": 1, "x_out": 0, "u_out": 1, "dX1": 2, "dMem": 2, "x1_out": 2, "mem_out": 2, "dX0": 3, "x0_out": 3}
+    # the optional outputs of ctrlsim_forward_loss_grads (ctrlsim_train_taps) in the order the result tuples list them: name -> (first
+    # scope, last scope, rows: B*T*A*3 token rows or B*M scene rows, the Dims count of a per-layer tap: a list from scope 4 on, at
+    # scope 3 the last layer's tensor alone)
+    _TAPS = {"dX": (0, 5, "rows3", None), "dU": (1, 3, "rows3", None), "x_out": (0, 5, "rows3", None), "u_out": (1, 3, "rows3", None),
+             "dX1": (2, 3, "rows3", None), "dMem": (2, 5, "rowsm", None), "x1_out": (2, 3, "rows3", None), "mem_out": (2, 5, "rowsm", None),
+             "dX0": (3, 5, "rows3", "ND"), "x0_out": (3, 5, "rows3", "ND"), "dE0": (5, 5, "rowsm", "NE"), "e0_out": (5, 5, "rowsm", "NE")}
 
     def _forward_loss_grads(self, cb, moving, B, scope, want=(), fused=True, workspace=None, X=None):
         """The one call behind every loss_and_*_grads: forward + loss + the gradients of `scope` with the taps named in `want` ->
@@ -251,42 +255,32 @@ class CtRLSim:
         layout, total = self.train_grad_layout(scope)
         sums = torch.zeros(5, 2, dtype=torch.float64, device=dev)
         grads = torch.empty(total, device=dev)
-        rows3, rowsm = B * d.T * d.A * 3, B * ((d.P + d.A + 3) & ~3)
-        taps = {k: torch.empty(rowsm if k in ("dMem", "mem_out") else rows3, d.D, device=dev) for k in self._TAPS if k in want}
+        sc = self._scope_index(scope)
+        rows = {"rows3": B * d.T * d.A * 3, "rowsm": B * ((d.P + d.A + 3) & ~3)}
+        ct, taps = _lib.TrainTaps(), {}
+        for k in (k for k in self._TAPS if k in want):
+            _, _, r, per = self._TAPS[k]
+            if per is None:
+                taps[k] = torch.empty(rows[r], d.D, device=dev)
+                setattr(ct, k, taps[k].data_ptr())
+                continue
+            n = getattr(d, per)
+            layers = range(n) if sc >= 4 else (n - 1,)
+            ts = [torch.empty(rows[r], d.D, device=dev) for _ in layers]
+            for l, t in zip(layers, ts):
+                getattr(ct, k)[l] = t.data_ptr()
+            taps[k] = ts if sc >= 4 else ts[0]
         cfg = self.loss_cfg(fused)
         coef = float(self.cfg.model.get("loss_action_coef", 1.0))
         n = self.train_grad_workspace_bytes(B, scope)
         ws = workspace if workspace is not None else torch.empty(n, dtype=torch.uint8, device=dev)
         assert ws.dtype == torch.uint8 and ws.numel() >= n
         head = (self.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(cfg), coef)
-        if scope in (self.DECODER_SCOPE, self.ENCODER_SCOPE):
-            assert X is None
-            taps = {k: torch.empty(rowsm if k in ("dMem", "mem_out") else rows3, d.D, device=dev) for k in ("dX", "x_out", "dMem", "mem_out")
-                    if k in want}
-            ct = _lib.DecoderTaps(**{k: t.data_ptr() for k, t in taps.items()})
-            for k in ("dX0", "x0_out"):
-                if k in want:
-                    taps[k] = [torch.empty(rows3, d.D, device=dev) for _ in range(d.ND)]
-                    for l, t in enumerate(taps[k]):
-                        getattr(ct, k)[l] = t.data_ptr()
-            if scope == self.ENCODER_SCOPE:
-                et = _lib.EncoderTaps(dec=ct)
-                for k in ("dE0", "e0_out"):
-                    if k in want:
-                        taps[k] = [torch.empty(rowsm, d.D, device=dev) for _ in range(d.NE)]
-                        for l, t in enumerate(taps[k]):
-                            getattr(et, k)[l] = t.data_ptr()
-                _lib.check(lib.ctrlsim_forward_loss_grads_encoder(*head, ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), C.byref(et),
-                                                                  st), "forward_loss_grads_encoder")
-            else:
-                _lib.check(lib.ctrlsim_forward_loss_grads_decoder(*head, ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), C.byref(ct),
-                                                                  st), "forward_loss_grads_decoder")
-        elif X is None:
-            ct = _lib.TrainTaps(**{k: t.data_ptr() for k, t in taps.items()})
-            _lib.check(lib.ctrlsim_forward_loss_grads(*head, self.SCOPES.index(scope), ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(),
-                                                      C.byref(ct), st), "forward_loss_grads")
+        if X is None:
+            _lib.check(lib.ctrlsim_forward_loss_grads(*head, sc, ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), C.byref(ct), st),
+                       "forward_loss_grads")
         else:
-            assert X.dtype == torch.float32 and tuple(X.shape) == (rows3, d.D)
+            assert sc == 0 and X.dtype == torch.float32 and tuple(X.shape) == (rows["rows3"], d.D)
             _lib.check(lib.ctrlsim_heads_loss_grad(*head, _lib.ptr(X), ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(),
                                                    _lib.ptr(taps.get("dX")), st), "heads_loss_grad")
         named = {k: grads[o:o + int(np.prod(shp))].view(shp) for k, o, shp in layout}
@@ -329,10 +323,17 @@ class CtRLSim:
 
     # ---- training, second stage (a): the heads and the last decoder layer's feed-forward block
     SCOPES = ("heads", "heads+ffn", "heads+ffn+cross", "heads+last_layer")
-    # training (d): the heads and EVERY decoder layer (ctrlsim_forward_loss_grads_decoder); accepted wherever a scope name is taken
+    # training (d): the heads and EVERY decoder layer (scope 4); accepted wherever a scope name is taken
     DECODER_SCOPE = "heads+decoder"
-    # training (e): and EVERY scene-encoder layer (ctrlsim_forward_loss_grads_encoder); accepted wherever a scope name is taken
+    # training (e): and EVERY scene-encoder layer (scope 5); accepted wherever a scope name is taken
     ENCODER_SCOPE = "heads+decoder+encoder"
+    # scope name -> the scope index of ctrlsim_train_grad_layout, ctrlsim_train_grads_workspace_bytes and ctrlsim_forward_loss_grads
+    _SCOPE_INDEX = {s: i for i, s in enumerate(SCOPES + (DECODER_SCOPE, ENCODER_SCOPE))}
+
+    def _scope_index(self, scope):
+        if scope not in self._SCOPE_INDEX:
+            raise ValueError(f"trainable scope {scope!r}: one of {tuple(self._SCOPE_INDEX)}")
+        return self._SCOPE_INDEX[scope]
 
     def set_trainable(self, scope="heads"):
         """What training_step / configure_optimizers / optimizer_step train: "heads" (the default: the three MLP heads), "heads+ffn"
@@ -340,17 +341,16 @@ class CtRLSim:
         multihead_attn.in_proj / out_proj and norm2) or "heads+last_layer" (and its self-attention: self_attn.in_proj / out_proj and
         norm1 — the whole last decoder layer) or "heads+decoder" (and the 18 tensors of every earlier decoder layer) or
         "heads+decoder+encoder" (and the 12 tensors of every scene-encoder layer).  Choose before configure_optimizers."""
-        if scope not in self.SCOPES + (self.DECODER_SCOPE, self.ENCODER_SCOPE):
-            raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES + (self.DECODER_SCOPE, self.ENCODER_SCOPE)}")
+        self._scope_index(scope)
         self._scope = scope
         return self
 
     def train_grad_layout(self, scope=None):
         """head_grad_layout for a scope (ctrlsim_train_grad_layout): "heads" gives exactly head_grad_layout's answer, "heads+ffn" appends
         the six tensors of the last decoder layer's feed-forward block, "heads+ffn+cross" the six of its cross-attention sublayer behind
-        them, "heads+last_layer" the six of its self-attention sublayer behind those; "heads+decoder" (ctrlsim_decoder_grad_layout)
+        them, "heads+last_layer" the six of its self-attention sublayer behind those; "heads+decoder"
         behind those, for the layers ND-2 down to 0, each layer's 18 tensors in the same group order; "heads+decoder+encoder"
-        (ctrlsim_encoder_grad_layout) behind those, for the encoder layers NE-1 down to 0, each layer's 12 tensors (the feed-forward
+        behind those, for the encoder layers NE-1 down to 0, each layer's 12 tensors (the feed-forward
         six, then the attention six).  Needs no device."""
         import ctypes as C
         from .. import _lib
@@ -359,15 +359,8 @@ class CtRLSim:
         scope = self._scope if scope is None else scope
         has_fut = int("decoder.predict_future_states.mlp.0.weight" in self.weights)
         cd = _dims_struct(self.dims)
-        if scope == self.DECODER_SCOPE:
-            query = lambda cap, names, offs: lib.ctrlsim_decoder_grad_layout(C.byref(cd), has_fut, cap, names, offs)
-        elif scope == self.ENCODER_SCOPE:
-            query = lambda cap, names, offs: lib.ctrlsim_encoder_grad_layout(C.byref(cd), has_fut, cap, names, offs)
-        else:
-            if scope not in self.SCOPES:
-                raise ValueError(f"trainable scope {scope!r}: one of {self.SCOPES + (self.DECODER_SCOPE, self.ENCODER_SCOPE)}")
-            sc = self.SCOPES.index(scope)
-            query = lambda cap, names, offs: lib.ctrlsim_train_grad_layout(C.byref(cd), has_fut, sc, cap, names, offs)
+        sc = self._scope_index(scope)
+        query = lambda cap, names, offs: lib.ctrlsim_train_grad_layout(C.byref(cd), has_fut, sc, cap, names, offs)
         n = query(0, None, None)
         names, offs = (C.c_char_p * max(n, 1))(), (C.c_int64 * (max(n, 0) + 1))()
         if n < 0 or query(n + 1, names, offs) != n:
@@ -386,12 +379,7 @@ class CtRLSim:
     def train_grad_workspace_bytes(self, B, scope="heads+ffn"):
         import ctypes as C
         from .. import _lib
-        if scope == self.DECODER_SCOPE:
-            n = _lib.lib().ctrlsim_decoder_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T)
-        elif scope == self.ENCODER_SCOPE:
-            n = _lib.lib().ctrlsim_encoder_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T)
-        else:
-            n = _lib.lib().ctrlsim_train_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T, self.SCOPES.index(scope))
+        n = _lib.lib().ctrlsim_train_grads_workspace_bytes(C.byref(self.hip.cdims), B, self.dims.T, self._scope_index(scope))
         if n < 0:
             raise RuntimeError(f"training gradient workspace query failed: {n}")
         return int(n)
@@ -409,11 +397,11 @@ class CtRLSim:
         & ~3, and the two inputs themselves; everything the narrower scope returns is bit for bit what it returns.  Under
         "heads+last_layer" (scope 3) the gradients continue with the six self-attention tensors and the tuple
         with (dX0, x0_out): the gradient at the layer's input rows [B*T*A*3, 256] and those rows themselves.
-        Under "heads+decoder" (ctrlsim_forward_loss_grads_decoder) the gradients continue with the 18 tensors of each earlier layer and
+        Under "heads+decoder" (scope 4) the gradients continue with the 18 tensors of each earlier layer and
         the tuple is (sums, gradients, dX, x_out, dMem, mem_out, dX0, x0_out): dMem summed over all ND layers; dX0 and x0_out LISTS of ND
         tensors, entry l the gradient at the rows that enter layer l and those rows (dX0[0]: the gradient at the assembled tokens).  The
         intermediate taps of the last layer (dU, u_out, dX1, x1_out) do not exist in that scope.
-        Under "heads+decoder+encoder" (ctrlsim_forward_loss_grads_encoder) the gradients continue with the 12 tensors of each encoder layer
+        Under "heads+decoder+encoder" (scope 5) the gradients continue with the 12 tensors of each encoder layer
         and the tuple is the decoder scope's followed by (dE0, e0_out): LISTS of NE tensors [B*M, 256], entry l the gradient at the scene
         rows that enter encoder layer l and those rows (dE0[0]: the gradient at [polylines || initial states]); they exist in that
         scope only."""
@@ -424,20 +412,18 @@ class CtRLSim:
         if scope in (self.DECODER_SCOPE, self.ENCODER_SCOPE):
             if dU or u_out or dX1 or x1_out:
                 raise ValueError(f"dU, u_out, dX1 and x1_out do not exist under the scope \"{scope}\"")
-            order = ("dX", "x_out", "dMem", "mem_out", "dX0", "x0_out") + (("dE0", "e0_out") if scope == self.ENCODER_SCOPE else ())
-            asked = dict(dX=dX, x_out=x_out, dMem=dMem, mem_out=mem_out, dX0=dX0, x0_out=x0_out, dE0=dE0, e0_out=e0_out)
-            sums, named, taps = self._forward_loss_grads(cb, moving, B, scope, [k for k in order if asked[k]], workspace=workspace)
-            return (sums, named) + tuple(taps.get(k) for k in order)
-        if scope not in self.SCOPES[1:]:
+        elif scope not in self.SCOPES[1:]:
             raise ValueError(f"loss_and_train_grads scope {scope!r}: one of {self.SCOPES[1:]}")
-        sc = self.SCOPES.index(scope)
-        asked = dict(dX=dX, dU=dU, x_out=x_out, u_out=u_out, dX1=dX1, dMem=dMem, x1_out=x1_out, mem_out=mem_out, dX0=dX0, x0_out=x0_out)
+        sc = self._scope_index(scope)
         if sc < 2 and (dX1 or dMem or x1_out or mem_out):
             raise ValueError("dX1, dMem, x1_out and mem_out exist from the scope \"heads+ffn+cross\" on only")
         if sc < 3 and (dX0 or x0_out):
             raise ValueError("dX0 and x0_out exist under the scope \"heads+last_layer\" only")
-        sums, named, taps = self._forward_loss_grads(cb, moving, B, scope, [k for k, on in asked.items() if on], workspace=workspace)
-        return (sums, named) + tuple(taps.get(k) for k, first in self._TAPS.items() if first <= sc)
+        asked = dict(dX=dX, dU=dU, x_out=x_out, u_out=u_out, dX1=dX1, dMem=dMem, x1_out=x1_out, mem_out=mem_out, dX0=dX0, x0_out=x0_out,
+                     dE0=dE0, e0_out=e0_out)
+        order = [k for k, (first, last, _, _) in self._TAPS.items() if first <= sc <= last]
+        sums, named, taps = self._forward_loss_grads(cb, moving, B, scope, [k for k in order if asked[k]], workspace=workspace)
+        return (sums, named) + tuple(taps.get(k) for k in order)
 
     def loss_and_train_grads(self, data, dX=False, dU=False, x_out=False, u_out=False, **more):
         """loss_and_train_grads_ctx over reference-layout windows `data` (more: dX1, dMem, x1_out, mem_out, dX0, x0_out, scope)."""

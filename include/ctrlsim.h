@@ -359,42 +359,6 @@ int ctrlsim_self_attn_block_grad(const float* X, int ldx, const float* dY, int l
                                  const float* in_proj_bias, const float* out_proj_weight, const float* out_proj_bias, const float* gamma,
                                  const float* beta, int B, int T, int A, int mask_mode, void* workspace, float* grads, float* dX, int lddx,
                                  hipStream_t stream);
-/* ---- training: forward, loss, then the gradients of the first `scope` groups behind the heads ---------------------------------------
- * ctrlsim_forward_loss_grads runs the teacher-forced forward on its own X, the loss (sums bit-identical to ctrlsim_forward_loss on the
- * same inputs) and the head gradients as described for ctrlsim_heads_loss_grad, then the three ops above on the LAST decoder layer
- * from its output back, as far as `scope` says; each op's dY is the dX of the op behind it.  grads: ONE flat float32 buffer, the head
- * tensors and then, per scope from 1 on, six tensors of decoder.transformer_decoder.layers.{ND-1}:
- *   scope | group added to grads             | taps added       | forward, against the scope before      | models accepted   | workspace
- *   0     | the heads' tensors               | dX, x_out        | ctrlsim_forward_loss's                 | that entry's      | head-gradient carve
- *   1     | .linear1, .linear2 (weight,      | dU, u_out        | out-projection + norm2 and the feed-   | + ND >= 1, F >= 1 | + U, a dX, the
- *         | bias), .norm3                    |                  | forward block as two kernels, U copied |                   | feed-forward op's
- *   2     | .multihead_attn in_proj_weight,  | dX1, dMem,       | + one row copy: X1, the norm1 output   | as scope 1        | + X1, a dU, the
- *         | in_proj_bias, out_proj, .norm2   | x1_out, mem_out  |                                        |                   | attention op's
- *   3     | .self_attn (the same), .norm1    | dX0, x0_out      | + one row copy: X0, before the layer's | + dims.variant 0  | + X0, a dX1, the self-
- *         |                                  |                  | first kernel                           | or 4 (mask_mode)  | attention op's
- * The gradient taps, [B*Tq*A*3, 256] each: dX at the decoder output; dU at the feed-forward block's input, the layer's norm2 output; dX1
- * at the layer's norm1 output; dX0 at the layer's input rows (for ND == 1 the assembled tokens).  dMem [B*M, 256], M = (P + A + 3) & ~3
- * scene rows per context: this layer's contribution to the gradient at the scene encoder's output.  x_out, u_out, x1_out, x0_out and
- * mem_out receive the rows those gradients belong to, as the backward read them.  A non-null tap of a wider scope than the call's, a scope
- * outside 0..3 or a model the scope does not accept: CTRLSIM_EINVAL, nothing launched.  taps == NULL: no tap.  Whatever a narrower scope
- * returns, a wider one returns bit for bit.  The gradients are those of the function THIS call evaluated: each op applied to its input
- * rows as stored.  Rows of dX no head reads are zero; their dU is what the block's Jacobian makes of a zero row.  A term with count 0
- * gives NaN gradients.
- * The layout query fills names[i] (state-dict names, static storage: valid until the next layout query) and offsets[i] (in floats) for
- * cap >= count entries and, if cap > count, offsets[count] = the total length; it returns the count and needs no device.  Workspace:
- * ctrlsim_train_grads_workspace_bytes(dims, B, Tq, scope); the dX / dU / dX1 of its own is the next op's dY where the caller takes no
- * such tap.  Scope 3 also refuses B*Tq*A*3 * 768 >= 2^31. */
-typedef struct ctrlsim_train_taps {          /* every member nullable */
-  float *dX, *x_out;                         /* scope >= 0 */
-  float *dU, *u_out;                         /* scope >= 1 */
-  float *dX1, *dMem, *x1_out, *mem_out;      /* scope >= 2 */
-  float *dX0, *x0_out;                       /* scope 3    */
-} ctrlsim_train_taps;
-int ctrlsim_train_grad_layout(const ctrlsim_dims* dims, int has_future_states, int scope, int cap, const char** names, int64_t* offsets);
-int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq, int scope);
-int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
-                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
-                               double* per_ctx, float* grads, const ctrlsim_train_taps* taps /* nullable */, hipStream_t stream);
 /* ---- training (d): one whole decoder layer's backward by recompute (csrc/decoder_layer_grad.hip) ---------------------------------------
  * The op.  Forward being differentiated, per context of L = 3 T A token rows and Lk memory rows: the three sublayers above in a row,
  *   X1 = the self-attention sublayer of X0 (norm1),  U = the cross-attention sublayer of X1 and Mem (norm2),  Y = the feed-forward block
@@ -419,28 +383,6 @@ int ctrlsim_decoder_layer_grad(const float* X0, int ldx, const float* Mem, int l
                                const float* const* tensors /* 18 fp32 masters */, int B, int T, int A, int Lk, int F, int mask_mode,
                                void* workspace, float* grads, float* dX0, int lddx0, float* dMem, int lddm, int accumulate_dmem,
                                float* x1_out, float* u_out, hipStream_t stream);
-/* ---- training (d): forward, loss, then the gradients of the heads and of EVERY decoder layer -------------------------------------------
- * ctrlsim_forward_loss_grads_decoder does everything scope 3 of ctrlsim_forward_loss_grads does — the same launches, with one more row
- * copy per earlier layer: the rows that enter layer l (X0_l), before that layer's first kernel; layers 0 .. ND-2 keep their fused
- * forward — and then, for l = ND-2 .. 0, the layer op above on (X0_l, Mem, dY = dX0 of layer l + 1) with accumulate_dmem = 1.
- * grads: scope 3's buffer, unchanged, as a prefix; then for l = ND-2 .. 0 the 18 tensors of decoder.transformer_decoder.layers.{l} in
- * the layer op's order (ctrlsim_decoder_grad_layout: names, offsets and the total, as ctrlsim_train_grad_layout).
- * Taps, each nullable: x0_out[l] / dX0[l], l < ND: the rows that enter layer l and the gradient there ([B*Tq*A*3, 256]; dX0[0] is the
- * gradient at the assembled token rows); dMem [B*M, 256]: the gradient at the scene encoder's output, the sum over all ND layers — the
- * last layer's contribution first, then descending l; mem_out, dX, x_out as scope 3's.  On the same inputs the loss sums, the scope-3
- * prefix of grads, dX and dX0[ND-1] are bit for bit scope 3's; for ND == 1 the entry IS scope 3.  A model scope 3 refuses, ND >
- * CTRLSIM_MAX_DECODER_LAYERS or a tap of a layer >= ND: CTRLSIM_EINVAL, nothing launched.  Workspace:
- * ctrlsim_decoder_grads_workspace_bytes(dims, B, Tq): scope 3's, ND-1 row buffers, a dX0 pair, the layer op's. */
-#define CTRLSIM_MAX_DECODER_LAYERS 8
-typedef struct ctrlsim_decoder_taps {        /* every member nullable */
-  float *x0_out[CTRLSIM_MAX_DECODER_LAYERS], *dX0[CTRLSIM_MAX_DECODER_LAYERS];
-  float *dMem, *mem_out, *dX, *x_out;
-} ctrlsim_decoder_taps;
-int ctrlsim_decoder_grad_layout(const ctrlsim_dims* dims, int has_future_states, int cap, const char** names, int64_t* offsets);
-int64_t ctrlsim_decoder_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq);
-int ctrlsim_forward_loss_grads_decoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
-                                       const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
-                                       float* grads, const ctrlsim_decoder_taps* taps /* nullable */, hipStream_t stream);
 /* ---- training (e): the scene encoder's self-attention sublayer's backward (csrc/scene_attn_grad.hip) -----------------------------------
  * The op.  Forward being differentiated, per context of L rows — ONE source: the context's own rows are queries, keys and values:
  *   Q | K | V = X Win^T + bin                                           (in_proj_weight [768,256], in_proj_bias [768])
@@ -476,28 +418,60 @@ int64_t ctrlsim_encoder_layer_grad_workspace_bytes(int B, int L, int F);
 int ctrlsim_encoder_layer_grad(const float* X0, int ldx, const uint8_t* key_pad, const float* dY, int lddy,
                                const float* const* tensors /* 12 fp32 masters */, int B, int L, int F, void* workspace, float* grads,
                                float* dX0, int lddx0, float* u_out, hipStream_t stream);
-/* ---- training (e): forward, loss, then the gradients of the heads, EVERY decoder layer and EVERY scene-encoder layer -------------------
- * ctrlsim_forward_loss_grads_encoder does everything ctrlsim_forward_loss_grads_decoder does — the same launches, with one more row copy
- * per encoder layer: the scene rows that enter layer l (E0_l), before that layer's in_proj — and then, for l = NE-1 .. 0, the layer op
- * above on (E0_l, the scene rows' key-padding bytes, dY), dY = dMem for the last layer and dE0[l + 1] otherwise.
- * grads: the decoder entry's buffer, unchanged, as a prefix; then for l = NE-1 .. 0 the 12 tensors of
- * encoder.transformer_encoder.layers.{l} in the layer op's order (ctrlsim_encoder_grad_layout: names, offsets and the total).
- * Taps, each nullable: dec — the decoder entry's; e0_out[l] / dE0[l], l < NE: the rows that enter encoder layer l and the gradient there
- * ([B*M, 256], M = (P + A + 3) & ~3).  dE0[0] is the gradient at the scene encoder's input rows [polylines || initial states]: rows of
- * padded keys, the filler rows among them, are exactly zero.  On the same inputs the loss sums, the decoder prefix of grads, dX, every
- * dX0[l] and dMem are bit for bit the decoder entry's; for NE == 0 the entry IS the decoder entry.  A model the decoder entry refuses,
- * NE > CTRLSIM_MAX_ENCODER_LAYERS or a tap of a layer >= NE: CTRLSIM_EINVAL, nothing launched.  Workspace:
- * ctrlsim_encoder_grads_workspace_bytes(dims, B, Tq): the decoder entry's, NE row buffers, a dMem, a dE0, the layer op's. */
+/* ---- training: forward, loss, then the gradients of everything `scope` names behind the heads ---------------------------------------
+ * ctrlsim_forward_loss_grads runs the teacher-forced forward on its own X, the loss (sums bit-identical to ctrlsim_forward_loss on the
+ * same inputs) and the head gradients as described for ctrlsim_heads_loss_grad, then the ops above from the decoder's output back, as
+ * far as `scope` says; each op's dY is the dX of the op behind it.  grads: ONE flat float32 buffer, the head tensors and then what each
+ * scope appends, a narrower scope's buffer unchanged as a prefix of a wider one's:
+ *   scope | tensors added to grads           | taps added       | forward, against the scope before      | models accepted   | workspace
+ *   0     | the heads' tensors               | dX, x_out        | ctrlsim_forward_loss's                 | that entry's      | head-gradient carve
+ *   1     | layers.{ND-1}: .linear1, .linear2| dU, u_out        | out-projection + norm2 and the feed-   | + ND >= 1, F >= 1 | + U, a dX, the
+ *         | (weight, bias), .norm3           |                  | forward block as two kernels, U copied |                   | feed-forward op's
+ *   2     | .multihead_attn in_proj_weight,  | dX1, dMem,       | + one row copy: X1, the norm1 output   | as scope 1        | + X1, a dU, the
+ *         | in_proj_bias, out_proj, .norm2   | x1_out, mem_out  |                                        |                   | attention op's
+ *   3     | .self_attn (the same), .norm1    | dX0[ND-1],       | + one row copy: X0, before the layer's | + dims.variant 0  | + X0, a dX1, the self-
+ *         |                                  | x0_out[ND-1]     | first kernel                           | or 4 (mask_mode)  | attention op's
+ *   4     | for l = ND-2 .. 0 the 18 tensors | dX0[l], x0_out[l]| + one row copy per earlier layer: X0_l,| + ND <= CTRLSIM_  | + ND-1 row buffers, a
+ *         | of decoder layer l, in the layer | for l < ND; not  | before that layer's first kernel (the  | MAX_DECODER_LAYERS| dX0, the decoder layer
+ *         | op's order                       | dU .. x1_out     | layers keep their fused forward)       |                   | op's
+ *   5     | for l = NE-1 .. 0 the 12 tensors | dE0[l], e0_out[l]| + one row copy per encoder layer: E0_l,| + 0 <= NE <=      | + NE row buffers, a
+ *         | of encoder layer l, in the layer | for l < NE       | before that layer's in_proj            | CTRLSIM_MAX_      | dMem, a dE0, the encoder
+ *         | op's order                       |                  |                                        | ENCODER_LAYERS    | layer op's
+ * Scopes 1 to 3 differentiate the LAST decoder layer (decoder.transformer_decoder.layers.{ND-1}) with the three sublayer ops.  Scope 4
+ * then runs ctrlsim_decoder_layer_grad for l = ND-2 .. 0 on (X0_l, Mem, dY = dX0 of layer l + 1) with accumulate_dmem = 1; scope 5 then
+ * runs ctrlsim_encoder_layer_grad for l = NE-1 .. 0 on (E0_l, the scene rows' key-padding bytes, dY), dY = dMem for the last encoder
+ * layer and dE0[l + 1] otherwise.  For ND == 1 scope 4 IS scope 3, for NE == 0 scope 5 IS scope 4.
+ * The gradient taps, [B*Tq*A*3, 256] each: dX at the decoder output; dU at the last layer's feed-forward block's input, its norm2 output;
+ * dX1 at its norm1 output; dX0[l] at the rows that enter decoder layer l (dX0[0]: the assembled tokens).  dMem [B*M, 256], M = (P + A + 3)
+ * & ~3 scene rows per context: the gradient at the scene encoder's output from every decoder layer the scope differentiates — the last
+ * layer's contribution first, then descending l.  dE0[l] [B*M, 256]: the gradient at the scene rows that enter encoder layer l; dE0[0]
+ * is the gradient at [polylines || initial states], rows of padded keys, the filler rows among them, exactly zero.  x_out, u_out,
+ * x1_out, x0_out[l], mem_out and e0_out[l] receive the rows those gradients belong to, as the backward read them.  A non-null tap
+ * outside the scopes named beside it below, a tap of a layer the scope does not differentiate (scope 3: any l but ND-1; l >= ND; l >=
+ * NE), a scope outside 0 .. CTRLSIM_TRAIN_SCOPES - 1 or a model the scope does not accept: CTRLSIM_EINVAL, nothing launched.  taps ==
+ * NULL: no tap.  Whatever a narrower scope returns, a wider one returns bit for bit.  The gradients are those of the function THIS call
+ * evaluated: each op applied to its input rows as stored.  Rows of dX no head reads are zero; their dU is what the block's Jacobian
+ * makes of a zero row.  A term with count 0 gives NaN gradients.
+ * The layout query fills names[i] (state-dict names, static storage: valid until the next layout query) and offsets[i] (in floats) for
+ * cap >= count entries and, if cap > count, offsets[count] = the total length; it returns the count and needs no device.  Workspace:
+ * ctrlsim_train_grads_workspace_bytes(dims, B, Tq, scope); a dX / dU / dX1 / dX0 / dMem / dE0 of its own is the next op's dY where the
+ * caller takes no such tap.  Scopes >= 3 also refuse B*Tq*A*3 * 768 >= 2^31. */
+#define CTRLSIM_TRAIN_SCOPES 6
+#define CTRLSIM_MAX_DECODER_LAYERS 8
 #define CTRLSIM_MAX_ENCODER_LAYERS 8
-typedef struct ctrlsim_encoder_taps {        /* every member nullable */
-  ctrlsim_decoder_taps dec;
-  float *e0_out[CTRLSIM_MAX_ENCODER_LAYERS], *dE0[CTRLSIM_MAX_ENCODER_LAYERS];
-} ctrlsim_encoder_taps;
-int ctrlsim_encoder_grad_layout(const ctrlsim_dims* dims, int has_future_states, int cap, const char** names, int64_t* offsets);
-int64_t ctrlsim_encoder_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq);
-int ctrlsim_forward_loss_grads_encoder(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
-                                       const ctrlsim_loss_cfg* cfg, float loss_action_coef, void* workspace, double* sums, double* per_ctx,
-                                       float* grads, const ctrlsim_encoder_taps* taps /* nullable */, hipStream_t stream);
+typedef struct ctrlsim_train_taps {          /* every member nullable */
+  float *dX, *x_out;                         /* scope >= 0 */
+  float *dU, *u_out;                         /* scopes 1..3 */
+  float *dX1, *x1_out;                       /* scopes 2..3 */
+  float *dMem, *mem_out;                     /* scope >= 2 */
+  float *dX0[CTRLSIM_MAX_DECODER_LAYERS], *x0_out[CTRLSIM_MAX_DECODER_LAYERS];   /* scope 3: index ND-1 only; scope >= 4: 0..ND-1 */
+  float *dE0[CTRLSIM_MAX_ENCODER_LAYERS], *e0_out[CTRLSIM_MAX_ENCODER_LAYERS];   /* scope 5: 0..NE-1 */
+} ctrlsim_train_taps;
+int ctrlsim_train_grad_layout(const ctrlsim_dims* dims, int has_future_states, int scope, int cap, const char** names, int64_t* offsets);
+int64_t ctrlsim_train_grads_workspace_bytes(const ctrlsim_dims* dims, int B, int Tq, int scope);
+int ctrlsim_forward_loss_grads(const ctrlsim_model* m, int B, int Tq, const ctrlsim_ctx* ctx, const uint8_t* moving,
+                               const ctrlsim_loss_cfg* cfg, float loss_action_coef, int scope, void* workspace, double* sums,
+                               double* per_ctx, float* grads, const ctrlsim_train_taps* taps /* nullable */, hipStream_t stream);
 /* The same sums and counts from the logits of ctrlsim_forward_all in memory (compute_loss(data, preds) in the reference's call shape):
  * action_preds [B,Tq,A,V], rtg_preds [B,Tq,A,R*C] bin-major / component-minor, state_preds [B,Tq,A,2T]; the last two nullable.
  * scratch: ctrlsim_loss_scratch_bytes. */

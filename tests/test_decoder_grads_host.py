@@ -1,11 +1,12 @@
 """CPU tests of the all-decoder-layers gradient path's host side and of its checker:
   * tests/layer_grad_ref.py: the composed layer against torch.nn.TransformerDecoderLayer in float64, outputs and gradients, and the
     stack against the layer applied twice;
-  * ctrlsim_decoder_grad_layout through CtRLSim.train_grad_layout("heads+decoder"): the scope-3 layout as a prefix, then the earlier
+  * ctrlsim_train_grad_layout at scope 4 through CtRLSim.train_grad_layout("heads+decoder"): the scope-3 layout as a prefix, then the earlier
     layers in descending order with the parameter table's names and shapes; SCOPES and the refused names unchanged;
   * pack.ffn_images / cross_images / self_images applied to EVERY decoder layer against a fresh pack.pack, bit for bit;
   * the names HipModel.update accepts with and without decoder=True;
-  * the new C symbols: declared, bound and exported, with the declared argument counts;
+  * the C symbols: declared, bound and exported, with the declared argument counts; the six entries folded into the scope-indexed ones
+    absent from the header, the binding and the library;
   * the AdamW parameter groups with every layer's names."""
 import os
 import re
@@ -91,7 +92,7 @@ def test_stack_is_the_layer_applied_in_turn():
 
 @pytest.mark.parametrize("case", [0, 3, 7])
 def test_decoder_layout_extends_the_last_layer_scope(case):
-    """train_grad_layout("heads+decoder") (ctrlsim_decoder_grad_layout; needs the library, not a device): "heads+last_layer" as a prefix,
+    """train_grad_layout("heads+decoder") (ctrlsim_train_grad_layout, scope 4; needs the library, not a device): "heads+last_layer" as a prefix,
     then for l = ND-2 .. 0 the 18 tensors of layer l, back to back, with the parameter table's shapes; the total is the sum."""
     cfg = loss_ref.case_cfg(case)
     d = spec.Dims(cfg)
@@ -126,17 +127,17 @@ def test_decoder_layout_refuses_what_it_cannot_lay_out():
     lib = _lib.lib()
     d = spec.Dims(loss_ref.case_cfg(0))
     cd = _dims_struct(d)
-    n = lib.ctrlsim_decoder_grad_layout(C.byref(cd), 1, 0, None, None)
-    assert n > 0 and lib.ctrlsim_decoder_grad_layout(None, 1, 0, None, None) == -22
+    n = lib.ctrlsim_train_grad_layout(C.byref(cd), 1, 4, 0, None, None)
+    assert n > 0 and lib.ctrlsim_train_grad_layout(None, 1, 4, 0, None, None) == -22
     names, offs = (C.c_char_p * n)(), (C.c_int64 * (n + 1))()
-    assert lib.ctrlsim_decoder_grad_layout(C.byref(cd), 1, n - 1, names, offs) == -22          # too small a capacity
-    assert lib.ctrlsim_decoder_grad_layout(C.byref(cd), 1, n, names, offs) == n
+    assert lib.ctrlsim_train_grad_layout(C.byref(cd), 1, 4, n - 1, names, offs) == -22         # too small a capacity
+    assert lib.ctrlsim_train_grad_layout(C.byref(cd), 1, 4, n, names, offs) == n
     cd.ND = 9                                                              # more than CTRLSIM_MAX_DECODER_LAYERS
-    assert lib.ctrlsim_decoder_grad_layout(C.byref(cd), 1, 0, None, None) == -22
-    assert lib.ctrlsim_decoder_grads_workspace_bytes(C.byref(cd), 1, 1) == -22
-    assert lib.ctrlsim_decoder_grads_workspace_bytes(None, 1, 1) == -22
-    assert lib.ctrlsim_forward_loss_grads_decoder(None, 1, 1, None, None, None, 1.0, None, None, None, None, None, None) == -22
-    for scope in (4, -1):                                                  # the scope-indexed entry still ends at 3
+    assert lib.ctrlsim_train_grad_layout(C.byref(cd), 1, 4, 0, None, None) == -22
+    assert lib.ctrlsim_train_grads_workspace_bytes(C.byref(cd), 1, 1, 4) == -22
+    assert lib.ctrlsim_train_grads_workspace_bytes(None, 1, 1, 4) == -22
+    assert lib.ctrlsim_forward_loss_grads(None, 1, 1, None, None, None, 1.0, 4, None, None, None, None, None, None) == -22
+    for scope in (6, -1):                                                  # the scope-indexed entry ends at 5
         assert lib.ctrlsim_train_grad_layout(C.byref(_dims_struct(d)), 1, scope, 0, None, None) == -22
         assert lib.ctrlsim_train_grads_workspace_bytes(C.byref(_dims_struct(d)), 1, 1, scope) == -22
 
@@ -221,15 +222,18 @@ def test_new_symbols_are_declared_bound_and_exported_with_the_declared_argument_
     hdr = open(os.path.join(ROOT, "include", "ctrlsim.h")).read()
     hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
     for sym, nargs in (("ctrlsim_decoder_layer_grad_workspace_bytes", 5), ("ctrlsim_decoder_layer_grad", 24),
-                       ("ctrlsim_decoder_grad_layout", 5), ("ctrlsim_decoder_grads_workspace_bytes", 3),
-                       ("ctrlsim_forward_loss_grads_decoder", 13)):
+                       ("ctrlsim_train_grad_layout", 6), ("ctrlsim_train_grads_workspace_bytes", 4), ("ctrlsim_forward_loss_grads", 14)):
         m = re.search(r"\b" + sym + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.S)
         assert m, sym
         assert len(m.group(1).split(",")) == nargs == len(_lib.SIGNATURES[sym][1]), sym
         assert hasattr(lib, sym)
-    assert "#define CTRLSIM_MAX_DECODER_LAYERS 8" in hdr
+    for sym in ("ctrlsim_decoder_grad_layout", "ctrlsim_decoder_grads_workspace_bytes", "ctrlsim_forward_loss_grads_decoder",
+                "ctrlsim_encoder_grad_layout", "ctrlsim_encoder_grads_workspace_bytes", "ctrlsim_forward_loss_grads_encoder"):
+        assert not re.search(r"\b" + sym + r"\b", hdr) and sym not in _lib.SIGNATURES and not hasattr(lib, sym), sym      # (dlsym finds none)
+    assert "#define CTRLSIM_MAX_DECODER_LAYERS 8" in hdr and "#define CTRLSIM_TRAIN_SCOPES 6" in hdr
     import ctypes as C
-    assert C.sizeof(_lib.DecoderTaps) == (2 * 8 + 4) * C.sizeof(C.c_void_p)
+    assert C.sizeof(_lib.TrainTaps) == (8 + 4 * 8) * C.sizeof(C.c_void_p)
+    assert _lib.TrainTaps.dX0.offset == 8 * C.sizeof(C.c_void_p) and not hasattr(_lib, "DecoderTaps") and not hasattr(_lib, "EncoderTaps")
     assert lib.ctrlsim_decoder_layer_grad_workspace_bytes(1, 1, 1, 1, 0) == -22 and lib.ctrlsim_decoder_layer_grad_workspace_bytes(2, 3, 4, 7, 64) > 0
     # the workspace holds the four row buffers and the widest of the three ops' carves
     B, T, A, Lk, F = 9, 10, 32, 12, 1024

@@ -1,11 +1,11 @@
 """CPU tests of the scene-encoder gradient path's host side and of its checker:
   * tests/enc_layer_grad_ref.py: the composed layer against torch.nn.TransformerEncoderLayer (batch_first, src_key_padding_mask) in
     float64 on the non-padded rows, outputs and gradients, and the stack against the layer applied in turn;
-  * ctrlsim_encoder_grad_layout through CtRLSim.train_grad_layout("heads+decoder+encoder"): the decoder layout as a prefix, then the
+  * ctrlsim_train_grad_layout at scope 5 through CtRLSim.train_grad_layout("heads+decoder+encoder"): the decoder layout as a prefix, then the
     encoder layers in descending order with the parameter table's names and shapes; SCOPES unchanged; refusals;
   * pack.encoder_images applied to EVERY encoder layer against a fresh pack.pack, bit for bit (both splits' images are in one pack);
   * the names HipModel.update accepts with and without encoder=True;
-  * the new C symbols: declared, bound and exported, with the declared argument counts;
+  * the C symbols: declared, bound and exported, with the declared argument counts; the six folded entries absent;
   * the AdamW parameter groups over the encoder names;
   * fixture self-consistency: the float64 twin of the encoder stack, run on the encoder input rows and the output gradient the tiny
     cases record, against every recorded gradient; and the fixture's structure in every case (each tensor of each layer, the rows of
@@ -96,7 +96,7 @@ def test_stack_is_the_layer_applied_in_turn():
 
 @pytest.mark.parametrize("case", [0, 3, 7])
 def test_encoder_layout_extends_the_decoder_scope(case):
-    """train_grad_layout("heads+decoder+encoder") (ctrlsim_encoder_grad_layout; needs the library, not a device): "heads+decoder" as a
+    """train_grad_layout("heads+decoder+encoder") (ctrlsim_train_grad_layout, scope 5; needs the library, not a device): "heads+decoder" as a
     prefix, then for l = NE-1 .. 0 the 12 tensors of encoder layer l, back to back, with the parameter table's shapes."""
     cfg = loss_ref.case_cfg(case)
     d = spec.Dims(cfg)
@@ -130,25 +130,29 @@ def test_encoder_layout_refuses_what_it_cannot_lay_out():
     lib = _lib.lib()
     d = spec.Dims(loss_ref.case_cfg(0))
     cd = _dims_struct(d)
-    n = lib.ctrlsim_encoder_grad_layout(C.byref(cd), 1, 0, None, None)
-    nd = lib.ctrlsim_decoder_grad_layout(C.byref(cd), 1, 0, None, None)
-    assert n == nd + 12 * d.NE and lib.ctrlsim_encoder_grad_layout(None, 1, 0, None, None) == -22
+    layout = lambda dims, scope, cap=0, names=None, offs=None: lib.ctrlsim_train_grad_layout(dims, 1, scope, cap, names, offs)
+    ws = lib.ctrlsim_train_grads_workspace_bytes
+    n = layout(C.byref(cd), 5)
+    nd = layout(C.byref(cd), 4)
+    assert n == nd + 12 * d.NE and layout(None, 5) == -22
     names, offs = (C.c_char_p * n)(), (C.c_int64 * (n + 1))()
-    assert lib.ctrlsim_encoder_grad_layout(C.byref(cd), 1, n - 1, names, offs) == -22          # too small a capacity
-    assert lib.ctrlsim_encoder_grad_layout(C.byref(cd), 1, n, names, offs) == n
-    assert lib.ctrlsim_encoder_grads_workspace_bytes(C.byref(cd), 2, d.T) > lib.ctrlsim_decoder_grads_workspace_bytes(C.byref(cd), 2, d.T)
+    assert layout(C.byref(cd), 5, n - 1, names, offs) == -22               # too small a capacity
+    assert layout(C.byref(cd), 5, n, names, offs) == n
+    assert ws(C.byref(cd), 2, d.T, 5) > ws(C.byref(cd), 2, d.T, 4)
     cd.NE = 9                                                              # more than CTRLSIM_MAX_ENCODER_LAYERS
-    assert lib.ctrlsim_encoder_grad_layout(C.byref(cd), 1, 0, None, None) == -22
-    assert lib.ctrlsim_encoder_grads_workspace_bytes(C.byref(cd), 1, 1) == -22
-    cd.NE = 0                                                              # no encoder layer: the decoder entry's answers
-    assert lib.ctrlsim_encoder_grad_layout(C.byref(cd), 1, 0, None, None) == nd
-    assert lib.ctrlsim_encoder_grads_workspace_bytes(C.byref(cd), 2, d.T) == lib.ctrlsim_decoder_grads_workspace_bytes(C.byref(cd), 2, d.T)
+    assert layout(C.byref(cd), 5) == -22
+    assert ws(C.byref(cd), 1, 1, 5) == -22
+    cd.NE = 0                                                              # no encoder layer: the decoder scope's answers
+    assert layout(C.byref(cd), 5) == nd
+    assert ws(C.byref(cd), 2, d.T, 5) == ws(C.byref(cd), 2, d.T, 4)
     cd = _dims_struct(d)
-    cd.ND = 9                                                              # what the decoder entry refuses
-    assert lib.ctrlsim_encoder_grad_layout(C.byref(cd), 1, 0, None, None) == -22
-    assert lib.ctrlsim_encoder_grads_workspace_bytes(C.byref(cd), 1, 1) == -22
-    assert lib.ctrlsim_encoder_grads_workspace_bytes(None, 1, 1) == -22
-    assert lib.ctrlsim_forward_loss_grads_encoder(None, 1, 1, None, None, None, 1.0, None, None, None, None, None, None) == -22
+    cd.ND = 9                                                              # what the decoder scope refuses
+    assert layout(C.byref(cd), 5) == -22
+    assert ws(C.byref(cd), 1, 1, 5) == -22
+    assert ws(None, 1, 1, 5) == -22
+    assert lib.ctrlsim_forward_loss_grads(None, 1, 1, None, None, None, 1.0, 5, None, None, None, None, None, None) == -22
+    for scope in (6, -1):
+        assert layout(C.byref(_dims_struct(d)), scope) == -22 and ws(C.byref(_dims_struct(d)), 1, 1, scope) == -22
 
 
 def test_op_workspace_and_chunk_queries():
@@ -249,15 +253,18 @@ def test_new_symbols_are_declared_bound_and_exported_with_the_declared_argument_
     hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
     for sym, nargs in (("ctrlsim_scene_attn_block_grad_workspace_bytes", 2), ("ctrlsim_scene_attn_block_grad_chunk_contexts", 2),
                        ("ctrlsim_scene_attn_block_grad", 18), ("ctrlsim_encoder_layer_grad_workspace_bytes", 3),
-                       ("ctrlsim_encoder_layer_grad", 15), ("ctrlsim_encoder_grad_layout", 5), ("ctrlsim_encoder_grads_workspace_bytes", 3),
-                       ("ctrlsim_forward_loss_grads_encoder", 13)):
+                       ("ctrlsim_encoder_layer_grad", 15), ("ctrlsim_train_grad_layout", 6), ("ctrlsim_train_grads_workspace_bytes", 4),
+                       ("ctrlsim_forward_loss_grads", 14)):
         m = re.search(r"\b" + sym + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.S)
         assert m, sym
         assert len(m.group(1).split(",")) == nargs == len(_lib.SIGNATURES[sym][1]), sym
         assert hasattr(lib, sym)
     assert "#define CTRLSIM_MAX_ENCODER_LAYERS 8" in hdr
-    assert C.sizeof(_lib.EncoderTaps) == C.sizeof(_lib.DecoderTaps) + 2 * 8 * C.sizeof(C.c_void_p)
-    assert _lib.EncoderTaps.dec.offset == 0                               # the decoder taps lead the struct
+    for sym in ("ctrlsim_decoder_grad_layout", "ctrlsim_decoder_grads_workspace_bytes", "ctrlsim_forward_loss_grads_decoder",
+                "ctrlsim_encoder_grad_layout", "ctrlsim_encoder_grads_workspace_bytes", "ctrlsim_forward_loss_grads_encoder"):
+        assert not re.search(r"\b" + sym + r"\b", hdr) and sym not in _lib.SIGNATURES and not hasattr(lib, sym), sym      # (dlsym finds none)
+    assert C.sizeof(_lib.TrainTaps) == (8 + 4 * 8) * C.sizeof(C.c_void_p)
+    assert _lib.TrainTaps.dE0.offset == (8 + 2 * 8) * C.sizeof(C.c_void_p)  # the encoder taps end the struct
 
 
 def test_param_groups_over_the_encoder_names():

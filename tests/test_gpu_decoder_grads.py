@@ -1,5 +1,5 @@
 """GPU tests of the decoder layer's backward by recompute (csrc/decoder_layer_grad.hip: ctrlsim_decoder_layer_grad) and of
-ctrlsim_forward_loss_grads_decoder (heads + every decoder layer), the latter under both operand splits of the forward.
+ctrlsim_forward_loss_grads at scope 4 (heads + every decoder layer), the latter under both operand splits of the forward.
 
 ACCURACY BOUND (profiles/decoder_grad_parity.md holds every measured ratio).  The form of tests/test_gpu_self_attn_grads.py (_check): for
 every tensor T, relative to max |T_f64| (Frobenius: to ||T_f64||),
@@ -290,7 +290,7 @@ def _rows(t, B):
 @pytest.mark.parametrize("split", SPLITS)
 @pytest.mark.parametrize("case", MODEL_CASES)
 def test_forward_loss_grads_decoder_layer_by_layer(case, split):
-    """ctrlsim_forward_loss_grads_decoder on fixture cases 0, 1 (tiny, ND 4) and 7 (full dims, B 2, ND 4).  Bit for bit: the loss sums,
+    """ctrlsim_forward_loss_grads at scope 4 on fixture cases 0, 1 (tiny, ND 4) and 7 (full dims, B 2, ND 4).  Bit for bit: the loss sums,
     the scope-3 prefix of the gradients, dX, x_out, mem_out, the last layer's dX0 and x0_out equal "heads+last_layer"; for l = ND-2 .. 0
     the layer's 18 tensors and dX0[l] equal ctrlsim_decoder_layer_grad on the entry's own x0_out[l], mem_out and dX0[l + 1]; dMem equals
     the accumulate chain (the last layer's dMem, then each earlier layer added in descending order).  Against float64: every earlier
@@ -365,10 +365,10 @@ def test_decoder_entry_refuses_taps_beyond_the_layers_and_models_scope_3_refuses
     lc = model.loss_cfg()
 
     def call(m, taps, *, ws_=ws, sums_=sums, grads_=grads):
-        return lib.ctrlsim_forward_loss_grads_decoder(m.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(lc), 1.0, _lib.ptr(ws_),
-                                                      _lib.ptr(sums_), None, _lib.ptr(grads_), C.byref(taps) if taps is not None else None, st)
+        return lib.ctrlsim_forward_loss_grads(m.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(lc), 1.0, 4, _lib.ptr(ws_),
+                                              _lib.ptr(sums_), None, _lib.ptr(grads_), C.byref(taps) if taps is not None else None, st)
     for k in ("x0_out", "dX0"):
-        t = _lib.DecoderTaps()
+        t = _lib.TrainTaps()
         getattr(t, k)[d.ND] = buf.data_ptr()
         assert call(model, t) == -22                                       # a tap of a layer the model does not have
     assert call(model, None, ws_=None) == -22 and call(model, None, sums_=None) == -22 and call(model, None, grads_=None) == -22

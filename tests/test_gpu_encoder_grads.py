@@ -1,6 +1,6 @@
 """GPU tests of the scene encoder's backward: the single-source key-padded self-attention op (csrc/scene_attn_grad.hip:
 ctrlsim_scene_attn_block_grad), the encoder layer op by recompute (csrc/encoder_layer_grad.hip: ctrlsim_encoder_layer_grad) and
-ctrlsim_forward_loss_grads_encoder (heads + every decoder layer + every encoder layer), the latter under both operand splits of the
+ctrlsim_forward_loss_grads at scope 5 (heads + every decoder layer + every encoder layer), the latter under both operand splits of the
 forward.
 
 ACCURACY BOUND (profiles/encoder_grad_parity.md holds every measured ratio).  The form of tests/test_gpu_self_attn_grads.py (_check): for
@@ -377,7 +377,7 @@ def _decoder_part_equal(rd, re, nd):
 @pytest.mark.parametrize("split", SPLITS)
 @pytest.mark.parametrize("case", MODEL_CASES)
 def test_forward_loss_grads_encoder_layer_by_layer(case, split):
-    """ctrlsim_forward_loss_grads_encoder on fixture cases 0, 1 (tiny) and 7 (full dims, B 2), NE 2.  Bit for bit: the loss sums, the
+    """ctrlsim_forward_loss_grads at scope 5 on fixture cases 0, 1 (tiny) and 7 (full dims, B 2), NE 2.  Bit for bit: the loss sums, the
     decoder prefix of the gradients, dX, x_out, dMem, mem_out, every dX0[l] and x0_out[l] equal "heads+decoder"; for l = NE-1 .. 0 the
     layer's 12 tensors and dE0[l] equal ctrlsim_encoder_layer_grad on the entry's own e0_out[l], the scene rows' key padding and dMem /
     dE0[l + 1].  Against float64: every layer on those taps, and the whole stack started from e0_out[0] with dMem at its output (the
@@ -531,14 +531,14 @@ def test_encoder_entry_refuses_taps_beyond_the_layers_and_what_the_decoder_entry
     lc = model.loss_cfg()
 
     def call(m, taps, *, ws_=ws, sums_=sums, grads_=grads):
-        return lib.ctrlsim_forward_loss_grads_encoder(m.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(lc), 1.0, _lib.ptr(ws_),
-                                                      _lib.ptr(sums_), None, _lib.ptr(grads_), C.byref(taps) if taps is not None else None, st)
+        return lib.ctrlsim_forward_loss_grads(m.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(lc), 1.0, 5, _lib.ptr(ws_),
+                                              _lib.ptr(sums_), None, _lib.ptr(grads_), C.byref(taps) if taps is not None else None, st)
     for k in ("e0_out", "dE0"):
-        t = _lib.EncoderTaps()
+        t = _lib.TrainTaps()
         getattr(t, k)[d.NE] = buf.data_ptr()
         assert call(model, t) == -22                                       # a tap of an encoder layer the model does not have
-    t = _lib.EncoderTaps()
-    t.dec.dX0[d.ND] = buf.data_ptr()
+    t = _lib.TrainTaps()
+    t.dX0[d.ND] = buf.data_ptr()
     assert call(model, t) == -22                                           # ... of a decoder layer it does not have
     assert call(model, None, ws_=None) == -22 and call(model, None, sums_=None) == -22 and call(model, None, grads_=None) == -22
     torch.cuda.synchronize()

@@ -372,7 +372,7 @@ def test_scopes_before_this_one_answer_as_before():
 
 
 def test_the_entry_refuses_a_tap_of_a_wider_scope_and_needs_no_taps():
-    """The raw ctrlsim_forward_loss_grads call on case 0: scope 1 with taps.dX0 set, scope 4 and scope -1 return CTRLSIM_EINVAL and
+    """The raw ctrlsim_forward_loss_grads call on case 0: scope 1 with taps.dX0[ND-1] set, scope 6 and scope -1 return CTRLSIM_EINVAL and
     launch nothing (zeroed sums, a NaN-poisoned grads buffer and the tap keep their bits); taps = NULL at scope 3 gives the sums and
     gradients of the call with every tap, bit for bit."""
     import ctypes as C
@@ -391,8 +391,10 @@ def test_the_entry_refuses_a_tap_of_a_wider_scope_and_needs_no_taps():
         return lib.ctrlsim_forward_loss_grads(model.hip.handle, B, d.T, C.byref(cb.struct), _lib.ptr(moving), C.byref(lc), coef, scope,
                                               ws.data_ptr(), sums.data_ptr(), None, grads.data_ptr(), taps, st)
 
-    assert call(1, C.byref(_lib.TrainTaps(dX0=dX0.data_ptr()))) == -22          # CTRLSIM_EINVAL
-    assert call(4, None) == -22 and call(-1, None) == -22
+    taps = _lib.TrainTaps()
+    taps.dX0[d.ND - 1] = dX0.data_ptr()
+    assert call(1, C.byref(taps)) == -22                                   # CTRLSIM_EINVAL
+    assert call(6, None) == -22 and call(-1, None) == -22
     torch.cuda.synchronize()
     assert not sums.any() and torch.isnan(grads).all() and (dX0 == 7.0).all()
     assert call(3, None) == 0

@@ -4,9 +4,9 @@ sublayer, 3: + its self-attention sublayer) on the same batch of B full-size win
 taps it adds (dX; dU; dX1, dMem; dX0 and x0_out), as the per-scope tools this one replaces did.  Device events around `reps` calls per
 measurement, all routes warmed and ALTERNATING in one process, three rounds; prints one JSON line per round, then the medians, the
 differences between neighbouring scopes and the workspace bytes.  Recorded in profiles/train_grad_rate.md, not gated.
-Scope 4 is "heads+decoder" (ctrlsim_forward_loss_grads_decoder: scope 3, then every earlier decoder layer by recompute), with the taps
+Scope 4 is "heads+decoder" (scope 3, then every earlier decoder layer by recompute), with the taps
 dX, dMem and dX0 / x0_out of every layer; its difference to scope 3, divided by ND - 1, is the added time per earlier layer.
-Scope 5 is "heads+decoder+encoder" (ctrlsim_forward_loss_grads_encoder: scope 4, then every scene-encoder layer by recompute), with
+Scope 5 is "heads+decoder+encoder" (scope 4, then every scene-encoder layer by recompute), with
 scope 4's taps and dE0 / e0_out of every encoder layer; a run that reaches it also writes profiles/encoder_grad_rate.md: the call's time and
 workspace against "heads+decoder" at the same B, from this run's medians.  A record, not a gate.
 `trace SCOPE`: `reps` calls at that scope only, nothing timed — the run to put under a kernel trace (the difference of two scopes'
@@ -56,30 +56,23 @@ def main():
     grads = torch.empty(model.train_grad_layout(names[top])[1], device=dev)
     rows3, rowsm = B * d.T * d.A * 3, B * ((d.P + d.A + 3) & ~3)
     bufs = {k: torch.empty(rowsm if k == "dMem" else rows3, d.D, device=dev) for ks in TAPS[:top + 1] for k in ks}
-    taps = [_lib.TrainTaps(**{k: bufs[k].data_ptr() for ks in TAPS[:s + 1] for k in ks}) for s in range(min(top, 3) + 1)]
-    if top >= 4:
-        layer_bufs = [torch.empty(rows3, d.D, device=dev) for _ in range(2 * (d.ND - 1))]
-        dtaps = _lib.DecoderTaps(dX=bufs["dX"].data_ptr(), dMem=bufs["dMem"].data_ptr())
-        for l in range(d.ND):
-            dtaps.dX0[l] = (bufs["dX0"] if l == d.ND - 1 else layer_bufs[2 * l]).data_ptr()
-            dtaps.x0_out[l] = (bufs["x0_out"] if l == d.ND - 1 else layer_bufs[2 * l + 1]).data_ptr()
-    if top == 5:
-        enc_bufs = [torch.empty(rowsm, d.D, device=dev) for _ in range(2 * d.NE)]
-        etaps = _lib.EncoderTaps(dec=dtaps)
-        for l in range(d.NE):
-            etaps.dE0[l], etaps.e0_out[l] = enc_bufs[2 * l].data_ptr(), enc_bufs[2 * l + 1].data_ptr()
+    layer_bufs = [torch.empty(rows3, d.D, device=dev) for _ in range(2 * (d.ND - 1) if top >= 4 else 0)]
+    enc_bufs = [torch.empty(rowsm, d.D, device=dev) for _ in range(2 * d.NE if top == 5 else 0)]
+    taps = []
+    for s in range(top + 1):
+        t = _lib.TrainTaps(**{k: bufs[k].data_ptr() for ks in TAPS[:min(s, 2) + 1] for k in ks if s < 4 or k in ("dX", "dMem")})
+        for l in range(d.ND - 1 if s == 3 else 0 if s >= 4 else d.ND, d.ND):
+            t.dX0[l] = (bufs["dX0"] if l == d.ND - 1 else layer_bufs[2 * l]).data_ptr()
+            t.x0_out[l] = (bufs["x0_out"] if l == d.ND - 1 else layer_bufs[2 * l + 1]).data_ptr()
+        for l in range(d.NE if s == 5 else 0):
+            t.dE0[l], t.e0_out[l] = enc_bufs[2 * l].data_ptr(), enc_bufs[2 * l + 1].data_ptr()
+        taps.append(t)
     h, ctx = model.hip.handle, C.byref(cb.struct)
 
     def loss_only():
         _lib.check(lib.ctrlsim_forward_loss(h, B, d.T, ctx, None, C.byref(lc), ws.data_ptr(), sums.data_ptr(), None, None, st))
 
     def loss_grads(s):
-        if s == 5:
-            return lambda: _lib.check(lib.ctrlsim_forward_loss_grads_encoder(h, B, d.T, ctx, None, C.byref(lc), 1.0, ws.data_ptr(), sums.data_ptr(),
-                                                                             None, grads.data_ptr(), C.byref(etaps), st))
-        if s == 4:
-            return lambda: _lib.check(lib.ctrlsim_forward_loss_grads_decoder(h, B, d.T, ctx, None, C.byref(lc), 1.0, ws.data_ptr(), sums.data_ptr(),
-                                                                             None, grads.data_ptr(), C.byref(dtaps), st))
         return lambda: _lib.check(lib.ctrlsim_forward_loss_grads(h, B, d.T, ctx, None, C.byref(lc), 1.0, s, ws.data_ptr(), sums.data_ptr(),
                                                                  None, grads.data_ptr(), C.byref(taps[s]), st))
 
@@ -129,8 +122,8 @@ def write_encoder_record(out, d, reps):
              f"({out['token_rows']} token rows, {out['memory_rows']} scene rows, ND = {d.ND}, NE = {d.NE}).  Medians of three rounds of {reps} calls,",
              "all routes warmed and alternating in one process; both scopes measured in the same run.  A record, not a gate.", "",
              "| call | ms | workspace bytes |", "|---|---|---|",
-             f"| ctrlsim_forward_loss_grads_decoder (\"heads+decoder\") | {med['scope4_ms']:.3f} | {sz['scope4']} |",
-             f"| ctrlsim_forward_loss_grads_encoder (\"heads+decoder+encoder\") | {med['scope5_ms']:.3f} | {sz['scope5']} |", "",
+             f"| ctrlsim_forward_loss_grads, scope 4 (\"heads+decoder\") | {med['scope4_ms']:.3f} | {sz['scope4']} |",
+             f"| ctrlsim_forward_loss_grads, scope 5 (\"heads+decoder+encoder\") | {med['scope5_ms']:.3f} | {sz['scope5']} |", "",
              f"The encoder layers add {med['scope5_ms'] - med['scope4_ms']:.3f} ms ({out['added_ms_per_encoder_layer']:.3f} ms per layer, "
              f"{100 * (med['scope5_ms'] / med['scope4_ms'] - 1):.2f} % of the decoder scope's call) and "
              f"{sz['scope5'] - sz['scope4']} bytes of workspace ({100 * (sz['scope5'] / sz['scope4'] - 1):.2f} %).", "",
