@@ -582,6 +582,9 @@ int launch_group_build(int S, int N, int A, int T, int t, int Tmax1, double dist
                        unsigned char* tilted, hipStream_t st) {
   if (S <= 0) return CTRLSIM_OK;
   if (N < 1 || N > 64 || A < 1 || A > 64) return CTRLSIM_EINVAL;
+  if (T < 1 || t < 0 || t >= Tmax1) return CTRLSIM_EINVAL;             // window row w0 and existence row t lie in [0, Tmax1)
+  if (!hist_states || !eval_order || !persist || !n_groups || !grp_focal || !grp_ids || !grp_members || !own_g || !mem_g || !tilted)
+    return CTRLSIM_EINVAL;
   hipLaunchKernelGGL(group_build_kernel, dim3(S), dim3(64), 0, st, N, A, T, t, Tmax1, dist_thresh, hist_states, eval_order,
                      has_roads, persist, n_groups, grp_focal, grp_ids, grp_members, own_g, mem_g, tilted);
   return ctrlsim_launch_status();

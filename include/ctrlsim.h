@@ -155,7 +155,22 @@ int ctrlsim_replay_actions_views(int S, int N, int R, int t, int T1, int Tmax, i
 
 /* ---- focal grouping + context tensors ------------------------------------------------------------------------
  * Replaces AutoregressivePolicy.get_data (policies/autoregressive_policy.py:51-165) with
- * RLWaymoDataset.select_relevant_agents / normalize_scene (datasets/rl_waymo/dataset.py:278-319,390-428). */
+ * RLWaymoDataset.select_relevant_agents / normalize_scene (datasets/rl_waymo/dataset.py:278-319,390-428).
+ * ctrlsim_group_build, step t of S scenarios (one wavefront each).  hist_states [S,N,Tmax1,8] f32: positions are read from window row
+ * w0 = (t < T ? 0 : t - (T - 1)), existence (column 7) from row t.  eval_order [S,N]: the evaluated vehicles in processing order, packed
+ * at the front, -1 behind them, every entry unique and in [0, N) — anything else is undefined.  persist [S,N] is IN/OUT, bit v of
+ * persist[s,i] = vehicle v belongs to the set vehicle i carries from step to step; 0 = "no set yet" (what the caller starts a rollout
+ * with).  A focal vehicle with t == 0 or an empty set takes the A nearest vehicles (ascending distance in float64, ties to the lower
+ * index) that lie strictly closer than dist_thresh; any other focal takes its set minus the vehicles at dist_thresh or beyond — a vehicle
+ * that left does not come back.  Every evaluated vehicle folded into the group (the reference's list-mutated-while-iterated loop: the
+ * entry behind a folded one is skipped) inherits the set.  Group g of scenario s: grp_focal / grp_ids / grp_members [s,g]; entries at
+ * and beyond n_groups[s] are not written.  own_g [s,v] = first group whose ids hold v (-1: none), tilted [s,v] = v is a member of that
+ * group, mem_g [s,v] = the group v is a member of (-1: none — a focal that does not exist at row t, or has_roads == 0, forms no
+ * group).  Rows [s, 0..N) of own_g / mem_g / tilted / persist are always written.
+ * Late vehicles: an evaluated vehicle that did not exist at step 0 and was folded into nobody's group still has persist == 0 when it
+ * first exists at t > 0; it then makes the fresh nearest-A selection and carries that set on.  This is this library's rule: the
+ * reference has no behaviour there (self.relevant_agent_idxs[focal_id] raises KeyError).
+ * N or A outside [1, 64], T < 1, t < 0, t >= Tmax1 or a null pointer: CTRLSIM_EINVAL, nothing launched.  S <= 0: CTRLSIM_OK. */
 int ctrlsim_group_build(int S, int N, int A, int T, int t, int Tmax1, double dist_thresh, const float* hist_states,
                         const int* eval_order /*[S,N] -1 padded*/, int has_roads, uint64_t* persist /*[S,N]*/,
                         int* n_groups /*[S]*/, int* grp_focal /*[S,N]*/, uint64_t* grp_ids, uint64_t* grp_members,
